@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- M cell-updates/s of the flux + SSP-RK3 step on the synthetic Kelvin-Helmholtz AMR mesh.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one rank per GPU. Either launch it under torch.distributed.run yourself (RANK / WORLD_SIZE in the
 environment), or just run the line above: bench.py then starts `python -m torch.distributed.run
@@ -10,8 +10,11 @@ and returns its exit code (the reference's analogue is `mpirun -n 8`, README.md:
 
 One "step" = one full iterate() (3 flux evaluations + 3 RK stages) over the whole mesh; one
 cell-update = one element advanced by one step. Inputs are resident in HBM before
-the timed region. Rank 0 prints ONE JSON line carrying `roofline` (dominant kernel, HIP-event timed
-inside the timed region) and `cpu_baseline` (the CPU oracle on a bounded sample, N = 1 only).
+the timed region. The timed region is exactly K steps (--reps R: R such regions, the median reported);
+`ms_per_step` is the wall time of one of them. Rank 0 prints ONE JSON line carrying `roofline` (dominant kernel,
+HIP-event timed inside the timed region) and `cpu_baseline` (the CPU oracle on a bounded sample, N = 1 only).
+The warm-up and the timed steps start from the initial state whatever the untimed pre-warm did, so the same
+arguments give the same outputs in every run; --dump-outputs DIR writes those of the last timed step.
 """
 import argparse
 import ctypes
@@ -30,6 +33,8 @@ import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_COPY_GBS = 6300.0  # same guide: ~6.3 TB/s achievable (copy); SURVEY 8d asks for both fractions
+DUMP_MAX_BYTES = 60 << 20  # --dump-outputs: all files of one run together, all ranks included
+DUMP_SEED = 20240601       # --dump-outputs: which columns of a larger array are written
 
 # Workloads. c4 is the north-star mesh (~10 M elements, strong-scaled over the ranks).
 WORKLOADS = {
@@ -72,9 +77,13 @@ def algorithmic_bytes(kind, ft, phi, d=3, phi_c=3.0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="K: the number of timed steps")
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the K-step timed region; the median is reported")
+    ap.add_argument("--reps", type=int, default=1, help="repetitions of the K-step timed region; the median is reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (state: the "
+                         "conserved variables [5, cells]; speed: the per-face speed estimates of a plain mesh), at most "
+                         f"{DUMP_MAX_BYTES >> 20} MiB in all: a seeded sample of columns where an array is larger")
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
     ap.add_argument("--mode", default=os.environ.get("T8GPU_BENCH_MODE", "auto"), choices=["auto", "compat", "fused"])
     ap.add_argument("--flux", default="kepes", choices=["kepes", "hll", "hllc"])
@@ -83,6 +92,8 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--prewarm-seconds", type=float, default=1.0)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus))      # child torchrun; nothing has touched the GPU in this process
@@ -175,6 +186,10 @@ def main():
             if stepper is not None:
                 halo, halo_kind = None, "native rccl (C++ stepper)"
     setup_s = time.time() - t0
+    # the state of step 0 as constructed: the pre-warm below runs for a wall-clock budget, so its step count differs from run
+    # to run and from build to build; the warm-up and the timed steps start again from here, so that what they compute
+    # depends on the arguments alone (--dump-outputs)
+    initial = solver.planes[0:5].clone()
 
     # HIP-event timing of the dominant kernel (events recorded on the launch stream)
     timers = []
@@ -229,10 +244,14 @@ def main():
     with roctx("bench.prewarm"):
         run(more, False)
     prewarm = 10 + more
+    fence()
+    restore_initial_state(solver, initial)
+    del initial
+    fence()
     with roctx("bench.warmup"):
         run(args.warmup, False)
     # the timed region: EXACTLY K steps between barrier + synchronize on both sides, MAX over ranks -- repeated
-    # `--reps` times back to back (median of 5); value / ms_per_step are the MEDIAN repetition's.
+    # `--reps` times back to back (median of 5 with --reps 5); value / ms_per_step are the MEDIAN repetition's.
     rep_s = []
     for rep in range(max(1, args.reps)):
         fence()
@@ -258,6 +277,8 @@ def main():
 
     # sanity: the solution must still be finite (a diverged run is not a measurement)
     finite = bool(torch.isfinite(solver.state()).all().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver, rank, world)
 
     total_cells = n_global * cells
     value = total_cells * args.steps / elapsed / 1e6
@@ -350,6 +371,40 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def restore_initial_state(solver, initial):
+    """The solver as constructed: step 0 holds `initial` ([5, stride]), every other step, stage and flux plane and the speed
+    estimates are zero, step 0 is the current step (solver.h:100-101). The plan, the volumes and the step driver are kept."""
+    from t8gpu_amd.solver import STEP0, STEP3
+    solver.planes[:25].zero_()
+    solver.planes[0:5].copy_(initial)
+    if hasattr(solver, "speed"):
+        solver.speed.zero_()
+    solver.next, solver.prev = STEP0, STEP3
+
+
+def dump_outputs(out_dir, solver, rank, world):
+    """--dump-outputs DIR: what the last timed step computed, as a caller of the solver receives it -- state(), the conserved
+    variables of the owned cells [5, cells], and on a plain mesh the speed estimates of its third stage [faces + boundary
+    faces] -- as DIR/<name>.npy in the solver's float type. An array larger than its share of DUMP_MAX_BYTES is written as a
+    sample of its columns: sorted, drawn with DUMP_SEED, so the same mesh gives the same columns in every run. With several
+    ranks every rank writes its own part as DIR/<name>_rank<r>.npy."""
+    torch.cuda.synchronize()
+    arrays = {"state": solver.state()}
+    if hasattr(solver, "speed"):
+        arrays["speed"] = solver.speed[:solver.F + solver.B]
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // (len(arrays) * world) - 4096          # (room for the .npy header)
+    for name, t in arrays.items():
+        n = t.shape[-1]
+        rows = t.numel() // n if n else 1
+        keep = max(1, share // (t.element_size() * rows))
+        if n > keep:
+            cols = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+            t = t[..., torch.from_numpy(cols).to(t.device)]
+        suffix = "" if world == 1 else f"_rank{rank}"
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), t.cpu().numpy())
 
 
 def launch_ranks(n):
@@ -484,6 +539,8 @@ def bench_adaptive(args, w, dts, tdtype, kindf, mode, rank, world, dist, rehears
     sync()
     elapsed = total(time.perf_counter() - tstart, "max")
     finite = bool(torch.isfinite(solver.state()).all().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver, rank, world)
     # every rank takes part in the reductions; rank 0 prints
     tot_cells, n_end = total(cells), int(total(solver.N))
     step_s, cycle_s = total(t_step, "max"), total(t_cycle, "max")

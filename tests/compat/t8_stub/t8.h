@@ -1,6 +1,6 @@
 // TEST STUB -- not t8code, not product code. Opaque handles only, so that the reference's example translation
 // units (which `#include <t8.h>`) can be COMPILED against include/t8gpu in an image without t8code
-// (tests/test_reference_examples_compile.py: syntax / code generation only; nothing here can be linked or run).
+// (scripts/check_reference_examples.py: syntax / code generation only; nothing here can be linked or run).
 #ifndef T8GPU_TEST_T8_STUB_H
 #define T8GPU_TEST_T8_STUB_H
 #include <cstdint>

@@ -158,3 +158,38 @@ def test_bench_self_launch_reports_missing_gpus():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=120)
     assert out.returncode == 2 and "needs 2 GPUs" in out.stderr
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """--dump-outputs DIR: the state and speed estimates of the last timed step, in the solver's float type and within the
+    size budget; the warm-up and the K timed steps start from the initial state whatever the wall-clock pre-warm ran (two
+    runs with different pre-warm budgets write the same bits), so the dump is the oracle's state after W + K steps. --steps K
+    is the step count of the one timed region."""
+    import numpy as np
+    import _oracle as O
+    from _gpu import rel_err
+    from t8gpu_amd.synth import SynthMesh
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "T8GPU_REHEARSAL")}
+    dumps = []
+    for i, prewarm in enumerate(("0.05", "0.5")):
+        d = tmp_path / f"out{i}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c1", "--steps", "7",
+                              "--warmup", "2", "--prewarm-seconds", prewarm, "--no-cpu-baseline", "--dump-outputs", str(d)],
+                             cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
+        assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+        rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["steps"] == 7 and rec["repetitions"] == 1 and rec["ms_per_step"] > 0 and rec["config"]["finite"] is True
+        assert sorted(os.listdir(d)) == ["speed.npy", "state.npy"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in ("state", "speed"))
+    mesh = SynthMesh(2, 8, 8, band=0.0)                # c1
+    part = mesh.partition()
+    o = O.PlainCase(part, np.float64)
+    for _ in range(2 + 7):
+        o.iterate(0.1 * 2.0 ** -mesh.finest_level)
+    state, speed = dumps[0]["state"], dumps[0]["speed"]
+    assert state.dtype == np.float64 and state.shape == (5, part.N) and speed.shape == (part.F + part.B,)
+    assert rel_err(state, o.current()[:, :part.N]) < 1e-10
+    assert rel_err(speed[None], o.speed[None]) < 1e-10
