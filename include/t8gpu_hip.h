@@ -311,11 +311,7 @@ int t8gpu_hip_plain_stepper_iterate_steps_f64(void* stepper, int flux_kind, doub
  * hipGraphLaunch afterwards; enable = 0 -> direct enqueue (default); enable < 0 -> query only. counts (may be NULL)
  * receives {captures, replays}. A capture the runtime refuses returns its error code. delta_t is part of the argument set
  * (a CFL-adaptive step size re-captures per value: use the direct enqueue there).
- * A stepper WITH a halo enqueues directly whatever this switch says, unless T8GPU_GRAPH_RCCL=1 is in the environment
- * (opt-in): the RCCL groups are then captured too, on the ORIGIN stream of the capture (the deep tiles fork off instead; an
- * RCCL group on a forked stream of a capture crashes hipStreamEndCapture on this stack, HIP 7.0.51831 / RCCL 2.26.6 of the
- * torch wheel). That has only ever run on one GPU with a one-rank communicator exchanging with itself
- * (tests/test_gpu_graph.py), never across xGMI, and costs more host time than the two-lane direct enqueue. */
+ * A stepper WITH a halo always enqueues directly (the two-lane driver), whatever this switch says. */
 int t8gpu_hip_plain_stepper_graph(void* stepper, int enable, int* counts);
 int t8gpu_hip_plain_stepper_timing(void* stepper, int enable);
 /* Diagnostics (scripts/halo_overhead.py): with T8GPU_STEPPER_PROFILE=1 in the environment the step drivers time their own
@@ -370,7 +366,7 @@ int t8gpu_hip_subgrid_fused_stage_f64(int flux_kind, int stage, const T8gpuSubgr
 
 /* Native step driver for Subgrid blocks: SubgridCompressibleEulerSolver::iterate (examples/subgrid/solver.inl:152-266)
  * in one host call, the pipeline of t8gpu_hip_plain_stepper_* over the block classes of the plan (deep interior /
- * near-boundary / ghost-touching blocks on three streams, one RCCL exchange of whole ghost blocks per stage;
+ * near-boundary / ghost-touching blocks on the two lanes, one RCCL exchange of whole ghost blocks per stage;
  * halo->cells_per_element = 4^rank). `planes` = 25 variable planes of `stride` values (stride >= (N + G) * 4^rank),
  * `volumes` the per-block volume array. The handle is destroyed / timed with the t8gpu_hip_plain_stepper_destroy,
  * _timing, _elapsed and _timed_stages entry points above. */

@@ -120,19 +120,9 @@ def build_oracle(force=False):
     return ORACLE_LIB
 
 
-NO_RCCL_LIB = os.path.join(LIB, "variants", "libt8gpu_hip_norccl.so")
-
-
-def build_diagnostic_variants(force=False):
-    """Diagnostic builds the GPU test-suite loads in child processes (never the product path): `norccl` = the step driver
-    with the RCCL group compiled out (tests/test_gpu_graph.py: the three-stream capture without RCCL)."""
-    return build_hip(force, variant="norccl", defines=["-DT8GPU_EXP_NO_RCCL"], only=["stepper.hip"])
-
-
 def build_all(force=False):
     build_host(force)
     build_hip(force)
-    build_diagnostic_variants(force)
     build_oracle(force)
 
 

@@ -3,7 +3,7 @@
 // Mirrors CompressibleEulerSolver::iterate (examples/compressible_euler/solver.cu:75-175) for the fused
 // tier: 3 x [ghost exchange || interior tiles -> ghost-reading tiles]. Where the reference brackets
 // every kernel with cudaDeviceSynchronize + MPI_Barrier (5 pairs per step) this driver only enqueues:
-// ordering is carried by two HIP streams and two events, the ghost exchange is one RCCL group of
+// ordering is carried by two HIP streams and their events, the ghost exchange is one RCCL group of
 // ncclSend/ncclRecv per neighbour rank over xGMI, and the host returns immediately.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -67,20 +67,14 @@ struct Stepper {
   T8gpuPlainPlan   plan{};      // plain elements: units = tiles of the plan
   T8gpuSubgridPlan splan{};     // Subgrid blocks: units = blocks in block_order position order
   bool             subgrid = false;
-  bool           has_halo = false;
+  bool           has_halo = false;  // the stepper has peers: iterate() runs the two-lane driver
   T8gpuHalo      halo{};
   std::vector<int32_t> peers, send_off, recv_off;
-  hipStream_t    comm_stream = nullptr;   // pack, RCCL, unpack, class A tiles
-  hipStream_t    near_stream = nullptr;   // class B tiles
-  hipEvent_t     ev_state = nullptr, ev_ghost = nullptr;   // step entry / last boundary launch
-  hipEvent_t     ev_interior = nullptr;                  // last class B launch
-  hipEvent_t     ev_deep = nullptr;                      // last class C launch
+  hipStream_t    comm_stream = nullptr;   // the comm lane's stream
+  hipEvent_t     ev_state = nullptr;      // step entry
   int            timing = 0;        // 0 = off, n = time the stage kernels of every n-th step
-  bool           sample = false;    // the step being enqueued is one of those
-  std::vector<hipEvent_t> pool;   // start/stop pairs of the stage-kernel launches
-  size_t         used = 0;
   int            stages_timed = 0;
-  // hipGraph replay of a whole iterate_steps() call (t8gpu_hip_plain_stepper_graph): the enqueue sequence is
+  // hipGraph replay of a whole single-rank iterate_steps() call (t8gpu_hip_plain_stepper_graph): the enqueue sequence is
   // captured once per distinct argument set on an internal origin stream and replayed with one hipGraphLaunch
   int             graph_mode = 0;       // 0 off, 1 on
   hipStream_t     graph_stream = nullptr;
@@ -93,19 +87,14 @@ struct Stepper {
   GraphEntry      graph_cache[4];
   unsigned long   graph_clock = 0;
   int             graph_captures = 0, graph_replays = 0;
-  bool            capturing = false;    // iterate() is being recorded into a graph
-  int             capture_variant = 0;  // diagnostics (T8GPU_GRAPH_VARIANT): 2 = global capture mode, 3 = thread-local capture mode,
-                                        // 5 = exchange chain on a FORKED stream of the capture (the layout that crashes)
-  void*           scratch = nullptr;
-  std::vector<hipEvent_t> capture_events;   // one event per (stage, role) of a captured call (see stage_event)
 
-  // ---- two-lane driver (iterate_lanes; round 4) ----------------------------------------------------------------------
+  // ---- lanes: the two-lane driver (iterate_lanes); a single rank launches on the deep lane ---------------------------------
   static constexpr int kRing = 4;
   struct Lane {
     hipStream_t        stream = nullptr;
     hipEvent_t         ring[kRing] = {nullptr, nullptr, nullptr, nullptr};   // the record of stage g uses ring[g % kRing]
     std::atomic<long>  recorded{0};     // stages of the current call whose record has been issued
-    std::vector<hipEvent_t> pool;       // timing events of this lane
+    std::vector<hipEvent_t> pool;       // timing events of this lane: start / stop pairs of the stage-kernel launches
     size_t             used = 0;
   };
   Lane            deep_lane, comm_lane;     // C tiles | RCCL, A tiles, B tiles
@@ -128,26 +117,6 @@ struct Stepper {
   long                      host_steps = 0;
 };
 
-// Events that order the three streams. Direct enqueue: one event per role, re-recorded every stage. Inside a capture
-// every (stage, role) gets an event of its own: a captured wait refers to the record node it follows, and the HIP
-// runtime of this stack crashes when an event that captured waits already refer to is recorded again in the same
-// capture (segmentation fault at the end of the capture, with or without RCCL in it: tests/test_gpu_graph.py).
-enum EventRole { kDeep = 0, kGhost = 1, kInterior = 2, kJoin = 3 };
-static int stage_event(Stepper* S, int g, EventRole role, hipEvent_t* out) {
-  if (!S->capturing) {
-    *out = role == kDeep ? S->ev_deep : (role == kGhost ? S->ev_ghost : S->ev_interior);
-    return 0;
-  }
-  const size_t idx = static_cast<size_t>(g) * 4 + static_cast<size_t>(role);
-  while (S->capture_events.size() <= idx) {
-    hipEvent_t e;
-    T8_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    S->capture_events.push_back(e);
-  }
-  *out = S->capture_events[idx];
-  return 0;
-}
-
 template <class T>
 ncclDataType_t nccl_type();
 template <>
@@ -156,95 +125,28 @@ template <>
 ncclDataType_t nccl_type<double>() { return ncclDouble; }
 
 template <class T, class V>
-int exchange(const T8gpuHalo& h, const int32_t* peers, const int32_t* send_off, const int32_t* recv_off, V state,
-             hipStream_t s) {
-  if (h.n_peers <= 0) return 0;
-  T*       sb = static_cast<T*>(h.sendbuf);
-  T*       rb = static_cast<T*>(h.recvbuf);
+int halo_pack(const T8gpuHalo& h, V state, hipStream_t s) {
+  HostTimer ht(0);
   const int cells = h.cells_per_element < 1 ? 1 : h.cells_per_element;
-  HostTimer htp(0);
-  if constexpr (sizeof(T) == 4) {
-    T8_TRY(t8gpu_hip_halo_pack_f32(h.n_send, cells, h.send_idx, state, sb, s));
-  } else {
-    T8_TRY(t8gpu_hip_halo_pack_f64(h.n_send, cells, h.send_idx, state, sb, s));
-  }
-  // T8GPU_EXP_NO_RCCL: experiment builds only (build.py variants, tests/test_gpu_graph.py): the RCCL group is left out, to
-  // tell a capture that fails because of RCCL from one that fails because of the three-stream fork / join. The ghosts are
-  // then stale and the results wrong, so the product library has no run-time switch for it.
-  ncclComm_t comm = static_cast<ncclComm_t>(h.comm);
-#ifndef T8GPU_EXP_NO_RCCL
-  {
-  HostTimer ht(1);
-  T8_TRY(nccl_code(ncclGroupStart()));
-  for (int j = 0; j < h.n_peers; j++) {
-    const size_t w  = 5 * static_cast<size_t>(cells);   // values per element on the wire
-    const size_t rc = w * static_cast<size_t>(recv_off[j + 1] - recv_off[j]);
-    const size_t sc = w * static_cast<size_t>(send_off[j + 1] - send_off[j]);
-    if (rc) T8_TRY(nccl_code(ncclRecv(rb + w * static_cast<size_t>(recv_off[j]), rc, nccl_type<T>(), peers[j], comm, s)));
-    if (sc) T8_TRY(nccl_code(ncclSend(sb + w * static_cast<size_t>(send_off[j]), sc, nccl_type<T>(), peers[j], comm, s)));
-  }
-  T8_TRY(nccl_code(ncclGroupEnd()));
-  }
-#else
-  (void)comm;
-  (void)peers; (void)send_off; (void)recv_off; (void)rb;
-#endif
-  if constexpr (sizeof(T) == 4) {
-    T8_TRY(t8gpu_hip_halo_unpack_f32(h.num_ghosts, h.num_elements, cells, rb, state, s));
-  } else {
-    T8_TRY(t8gpu_hip_halo_unpack_f64(h.num_ghosts, h.num_elements, cells, rb, state, s));
-  }
-  return 0;
+  if constexpr (sizeof(T) == 4)
+    return t8gpu_hip_halo_pack_f32(h.n_send, cells, h.send_idx, state, static_cast<T*>(h.sendbuf), s);
+  else
+    return t8gpu_hip_halo_pack_f64(h.n_send, cells, h.send_idx, state, static_cast<T*>(h.sendbuf), s);
 }
 
-template <class V, class T>
-V step_vars(T* planes, size_t stride, int step) {
-  V v;
-  for (int k = 0; k < 5; k++) v.p[k] = planes + (static_cast<size_t>(step) * 5 + k) * stride;
-  return v;
+template <class T, class V>
+int halo_unpack(const T8gpuHalo& h, V state, hipStream_t s) {
+  HostTimer ht(0);
+  const int cells = h.cells_per_element < 1 ? 1 : h.cells_per_element;
+  if constexpr (sizeof(T) == 4)
+    return t8gpu_hip_halo_unpack_f32(h.num_ghosts, h.num_elements, cells, static_cast<const T*>(h.recvbuf), state, s);
+  else
+    return t8gpu_hip_halo_unpack_f64(h.num_ghosts, h.num_elements, cells, static_cast<const T*>(h.recvbuf), state, s);
 }
 
-int tick(Stepper* S, hipStream_t s) {
-  if (!S->timing || !S->sample) return 0;
-  if (S->used == S->pool.size()) {
-    hipEvent_t e;
-    T8_HIP_TRY(hipEventCreate(&e));
-    S->pool.push_back(e);
-  }
-  T8_HIP_TRY(hipEventRecord(S->pool[S->used++], s));
-  return 0;
-}
-
-
-// ---- the two-lane driver (round 4) ------------------------------------------------------------------------------------
-// What the three-stream pipeline above costs at 8 ranks (profiles/r04_halo_*.md): the exchange chain
-// pack -> RCCL -> unpack -> A tiles is the critical path of a stage (the RCCL kernel alone takes ~50 us beside the tile
-// kernels), and the host needs ~55 us to enqueue a stage (13 HIP calls + the RCCL group) that the GPU finishes in ~50.
-// This driver shortens both:
-//   * GHOST WINDOW (plain 2D / tile plans): the A tiles read their ghosts straight from the receive buffer of the
-//     exchange, in its wire format, and write the elements a peer mirrors into the send buffer in their RK epilogue
-//     (T8gpuPlainPlan::ghost_buf / send_map, fused_common.hpp). No pack kernel (except for the first stage of a call, whose
-//     source state comes from outside) and no unpack kernel: the chain is RCCL -> A tiles.
-//   * TWO LANES, each depending only on the OTHER lane's PREVIOUS stage:
-//       deep lane (caller's stream)  : [A_(g-1)] -> I_g          I = all interior tiles [0, n_interior): one launch
-//       comm lane                    : RCCL_g -> [I_(g-1)] -> A_g
-//     I_g reads what I- and A-tiles of stage g-1 wrote; A_g reads the ghosts of stage g and what A- and I-tiles of stage
-//     g-1 wrote; RCCL_g sends what A_(g-1) put into the send buffer. Both waits refer to work that ended most of a stage
-//     earlier (the chain RCCL + A, ~35 us, is shorter than I, ~45 us, beside it), so neither lane ever stalls on the
-//     other and the long launches run back to back. With the three-stream pipeline the deep tiles of stage g + 1 waited
-//     for B_g, which sat behind the whole exchange chain, across queues: ~10 us of idle GPU per stage.
-//     The RCCL kernel needs 264 VGPRs per lane (rcclGenericKernel<1, false> of RCCL 2.26.6 for gfx950): beside tile kernels
-//     that hold 3 x 160 of a SIMD's 512 it is not dispatched before the tile launch has handed out its last workgroup.
-//     Here it is queued a whole stage ahead of its deadline and slips in at the drain between two interior launches.
-//     (A plan WITH a deep / near-boundary split of its interior tiles -- Subgrid plans, plain plans built without flag 32 -- runs
-//     C_g on the deep lane behind [B_(g-1)] and B_g on the comm lane behind A_g and [C_(g-1)].)
-//   * The comm lane is enqueued by a HOST THREAD of its own while the caller's thread enqueues the deep lane; the threads
-//     meet through two counters (a wait on stage g's event may only be issued once the other thread has recorded it).
-// Plans the ghost window does not cover (Subgrid blocks, 3D patch tiles) run the same two lanes with the pack / unpack
-// kernels around the group.
+// The RCCL group of one exchange: per peer, its ghosts into the receive buffer and what it mirrors out of the send buffer.
 template <class T>
 int exchange_wire(const T8gpuHalo& h, const int32_t* peers, const int32_t* send_off, const int32_t* recv_off, hipStream_t s) {
-#ifndef T8GPU_EXP_NO_RCCL
   HostTimer   ht(1);
   T*          sb    = static_cast<T*>(h.sendbuf);
   T*          rb    = static_cast<T*>(h.recvbuf);
@@ -259,20 +161,49 @@ int exchange_wire(const T8gpuHalo& h, const int32_t* peers, const int32_t* send_
     if (sc) T8_TRY(nccl_code(ncclSend(sb + w * static_cast<size_t>(send_off[j]), sc, nccl_type<T>(), peers[j], comm, s)));
   }
   T8_TRY(nccl_code(ncclGroupEnd()));
-#else
-  (void)h; (void)peers; (void)send_off; (void)recv_off; (void)s;
-#endif
   return 0;
 }
 
-inline void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-  __builtin_ia32_pause();
-#endif
+// t8gpu_hip_halo_exchange_*: pack -> RCCL group -> unpack, all on s
+template <class T, class V>
+int exchange(const T8gpuHalo& h, V state, hipStream_t s) {
+  if (h.n_peers <= 0) return 0;
+  T8_TRY((halo_pack<T, V>(h, state, s)));
+  T8_TRY(exchange_wire<T>(h, h.peers, h.send_off, h.recv_off, s));
+  return halo_unpack<T, V>(h, state, s);
 }
 
-int lane_tick(Stepper* S, Stepper::Lane& L) {
-  if (!S->timing || !S->sample) return 0;
+template <class V, class T>
+V step_vars(T* planes, size_t stride, int step) {
+  V v;
+  for (int k = 0; k < 5; k++) v.p[k] = planes + (static_cast<size_t>(step) * 5 + k) * stride;
+  return v;
+}
+
+// Stage g of an iterate_steps() call: stage k = g % 3 of its step, the planes it reads (previous state, stage source) and writes.
+template <class T, class V>
+struct StageArgs {
+  int k;
+  V   pv, sv, ov;
+  T*  stage_speed;
+};
+template <class T, class V>
+StageArgs<T, V> stage_args(T* planes, size_t stride, int prev, int next, T* speed, int g) {
+  StageArgs<T, V> a;
+  a.k          = g % 3;
+  const int pr = (g / 3) % 2 == 0 ? prev : next, nx = (g / 3) % 2 == 0 ? next : prev;
+  const int src = a.k == 0 ? pr : a.k, dst = a.k == 2 ? nx : a.k + 1;   // Step1 = 1, Step2 = 2 (solver.h:24-31)
+  a.pv = step_vars<V>(planes, stride, pr);
+  a.sv = step_vars<V>(planes, stride, src);
+  a.ov = step_vars<V>(planes, stride, dst);
+  // The per-face speed estimates are rewritten by every stage and read only between steps (compute_timestep uses
+  // those "computed at the last step of the last timestepping", solver.h:88-91): only the third stage writes them
+  // (same contents after every step, a tenth less HBM traffic per step).
+  a.stage_speed = a.k == 2 ? speed : nullptr;
+  return a;
+}
+
+int lane_tick(Stepper::Lane& L) {
   if (L.used == L.pool.size()) {
     hipEvent_t e;
     T8_HIP_TRY(hipEventCreate(&e));
@@ -280,6 +211,60 @@ int lane_tick(Stepper* S, Stepper::Lane& L) {
   }
   T8_HIP_TRY(hipEventRecord(L.pool[L.used++], L.stream));
   return 0;
+}
+
+// units [b, b + n) of stage a on lane L; `sample`: bracketed by the lane's timing events
+template <class T, class V>
+int launch_stage(Stepper* S, Stepper::Lane& L, int kind, const T8gpuPlainPlan* plan, const StageArgs<T, V>& a, int b, int n,
+                 const T* vol, T dt, bool sample) {
+  if (n <= 0) return 0;
+  HostTimer ht(0);
+  if (sample) T8_TRY(lane_tick(L));
+  if constexpr (sizeof(T) == 4) {
+    if (S->subgrid)
+      T8_TRY(t8gpu_hip_subgrid_fused_stage_f32(kind, a.k + 1, &S->splan, b, n, a.pv, a.sv, a.ov, vol, dt, L.stream));
+    else
+      T8_TRY(t8gpu_hip_plain_fused_stage_f32(kind, a.k + 1, plan, b, n, a.pv, a.sv, a.ov, vol, dt, a.stage_speed, L.stream));
+  } else {
+    if (S->subgrid)
+      T8_TRY(t8gpu_hip_subgrid_fused_stage_f64(kind, a.k + 1, &S->splan, b, n, a.pv, a.sv, a.ov, vol, dt, L.stream));
+    else
+      T8_TRY(t8gpu_hip_plain_fused_stage_f64(kind, a.k + 1, plan, b, n, a.pv, a.sv, a.ov, vol, dt, a.stage_speed, L.stream));
+  }
+  if (sample) T8_TRY(lane_tick(L));
+  return 0;
+}
+
+
+// ---- the two-lane driver: a stepper with peers ------------------------------------------------------------------------
+// At 8 ranks the exchange chain of a stage is its critical path (the RCCL kernel alone takes ~50 us beside the tile kernels),
+// and the host needs about as long to enqueue a stage as the GPU to run it (profiles/r04_halo_*.md). This driver shortens both:
+//   * GHOST WINDOW (plain 2D / tile plans): the A tiles (the tiles that read ghost slots) read their ghosts straight from the
+//     receive buffer of the exchange, in its wire format, and write the elements a peer mirrors into the send buffer in their
+//     RK epilogue (T8gpuPlainPlan::ghost_buf / send_map, fused_common.hpp). No pack kernel (except for the first stage of a
+//     call, whose source state comes from outside) and no unpack kernel: the chain is RCCL -> A tiles.
+//   * TWO LANES, each depending only on the OTHER lane's PREVIOUS stage:
+//       deep lane (caller's stream)  : [A_(g-1)] -> I_g          I = all interior tiles [0, n_interior): one launch
+//       comm lane                    : RCCL_g -> [I_(g-1)] -> A_g
+//     I_g reads what I- and A-tiles of stage g-1 wrote; A_g reads the ghosts of stage g and what A- and I-tiles of stage
+//     g-1 wrote; RCCL_g sends what A_(g-1) put into the send buffer. Both waits refer to work that ended most of a stage
+//     earlier (the chain RCCL + A, ~35 us, is shorter than I, ~45 us, beside it), so neither lane ever stalls on the
+//     other and the long launches run back to back.
+//     The RCCL kernel needs 264 VGPRs per lane (rcclGenericKernel<1, false> of RCCL 2.26.6 for gfx950): beside tile kernels
+//     that hold 3 x 160 of a SIMD's 512 it is not dispatched before the tile launch has handed out its last workgroup.
+//     Here it is queued a whole stage ahead of its deadline and slips in at the drain between two interior launches.
+//     (A plan WITH a deep / near-boundary split of its interior tiles -- Subgrid plans, plain plans built without flag 32 -- runs
+//     C_g on the deep lane behind [B_(g-1)] and B_g on the comm lane behind A_g and [C_(g-1)].)
+//   * The comm lane is enqueued by a HOST THREAD of its own while the caller's thread enqueues the deep lane; the threads
+//     meet through two counters (a wait on stage g's event may only be issued once the other thread has recorded it).
+// Plans the ghost window does not cover (Subgrid blocks, 3D patch tiles) run the same two lanes with the pack / unpack
+// kernels around the group.
+// (Rounds 1-3 ran a three-stream pipeline instead -- C, B and pack -> RCCL -> unpack -> A on a stream each; its deep tiles
+//  waited across queues for the exchange chain, ~10 us of idle GPU per stage. Replaced in round 4: DESIGN.md section 6.)
+inline void cpu_relax() {
+#if defined(__x86_64__) || defined(__i386__)
+  __builtin_ia32_pause();
+#endif
 }
 
 // wait until the other lane's host thread has RECORDED stage g (only then may a wait on that event be issued)
@@ -343,65 +328,19 @@ int iterate_lanes(Stepper* S, int kind, T* planes, size_t stride, const T* vol, 
   T8_HIP_TRY(hipStreamWaitEvent(XL.stream, S->ev_state, 0));
   if (DL.stream != s) T8_HIP_TRY(hipStreamWaitEvent(DL.stream, S->ev_state, 0));
 
-  struct StageArgs {
-    int k;
-    V   pv, sv, ov;
-    T*  stage_speed;
+  auto launch = [=](Stepper::Lane& L, const T8gpuPlainPlan* plan, const StageArgs<T, V>& a, int b, int n, bool sample) -> int {
+    return launch_stage<T, V>(S, L, kind, plan, a, b, n, vol, dt, sample);
   };
-  auto stage_args = [=](int g) {
-    StageArgs a;
-    a.k          = g % 3;
-    const int pr = (g / 3) % 2 == 0 ? prev : next, nx = (g / 3) % 2 == 0 ? next : prev;
-    const int src = a.k == 0 ? pr : a.k, dst = a.k == 2 ? nx : a.k + 1;   // Step1 = 1, Step2 = 2 (solver.h:24-31)
-    a.pv = step_vars<V>(planes, stride, pr);
-    a.sv = step_vars<V>(planes, stride, src);
-    a.ov = step_vars<V>(planes, stride, dst);
-    a.stage_speed = a.k == 2 ? speed : nullptr;   // (speed estimates once per step: see iterate())
-    return a;
-  };
-  auto launch = [=](Stepper::Lane& L, const T8gpuPlainPlan* plan, const StageArgs& a, int b, int n, bool sample) -> int {
-    if (n <= 0) return 0;
-    HostTimer ht(0);
-    if (sample) T8_TRY(lane_tick(S, L));
-    if constexpr (sizeof(T) == 4) {
-      if (S->subgrid)
-        T8_TRY(t8gpu_hip_subgrid_fused_stage_f32(kind, a.k + 1, &S->splan, b, n, a.pv, a.sv, a.ov, vol, dt, L.stream));
-      else
-        T8_TRY(t8gpu_hip_plain_fused_stage_f32(kind, a.k + 1, plan, b, n, a.pv, a.sv, a.ov, vol, dt, a.stage_speed, L.stream));
-    } else {
-      if (S->subgrid)
-        T8_TRY(t8gpu_hip_subgrid_fused_stage_f64(kind, a.k + 1, &S->splan, b, n, a.pv, a.sv, a.ov, vol, dt, L.stream));
-      else
-        T8_TRY(t8gpu_hip_plain_fused_stage_f64(kind, a.k + 1, plan, b, n, a.pv, a.sv, a.ov, vol, dt, a.stage_speed, L.stream));
-    }
-    if (sample) T8_TRY(lane_tick(S, L));
-    return 0;
-  };
-  // (S->sample is read by lane_tick: both threads sample the same steps, so it is set once here, "on", and the per-stage
-  //  decision is the `sample` argument)
-  S->sample = true;
 
   // ---- comm lane, stage g: RCCL_g -> A_g -> [C_(g-1)] -> B_g --------------------------------------------------------------
   auto comm_stage = [=, &DL, &XL](int g) -> int {
-    const T8gpuHalo& h      = S->halo;
-    const int        cells  = h.cells_per_element < 1 ? 1 : h.cells_per_element;
-    const StageArgs  a      = stage_args(g);
-    const bool       sample = timing > 0 && (g / 3) % timing == 0;
-    if (!S->zero_copy || g == 0) {   // (ghost window: the A tiles of stage g-1 have filled the send buffer)
-      HostTimer ht(0);
-      if constexpr (sizeof(T) == 4)
-        T8_TRY(t8gpu_hip_halo_pack_f32(h.n_send, cells, h.send_idx, a.sv, static_cast<T*>(h.sendbuf), XL.stream));
-      else
-        T8_TRY(t8gpu_hip_halo_pack_f64(h.n_send, cells, h.send_idx, a.sv, static_cast<T*>(h.sendbuf), XL.stream));
-    }
+    const T8gpuHalo&      h      = S->halo;
+    const StageArgs<T, V> a      = stage_args<T, V>(planes, stride, prev, next, speed, g);
+    const bool            sample = timing > 0 && (g / 3) % timing == 0;
+    if (!S->zero_copy || g == 0)   // (ghost window: the A tiles of stage g-1 have filled the send buffer)
+      T8_TRY((halo_pack<T, V>(h, a.sv, XL.stream)));
     T8_TRY(exchange_wire<T>(h, S->peers.data(), S->send_off.data(), S->recv_off.data(), XL.stream));
-    if (!S->zero_copy) {
-      HostTimer ht(0);
-      if constexpr (sizeof(T) == 4)
-        T8_TRY(t8gpu_hip_halo_unpack_f32(h.num_ghosts, h.num_elements, cells, static_cast<const T*>(h.recvbuf), a.sv, XL.stream));
-      else
-        T8_TRY(t8gpu_hip_halo_unpack_f64(h.num_ghosts, h.num_elements, cells, static_cast<const T*>(h.recvbuf), a.sv, XL.stream));
-    }
+    if (!S->zero_copy) T8_TRY((halo_unpack<T, V>(h, a.sv, XL.stream)));
     auto wait_deep = [&]() -> int {   // the deep lane's stage g-1
       if (g == 0 || nd == 0) return 0;
       if (!lane_wait_recorded(S, DL, g - 1)) return 0;
@@ -424,8 +363,8 @@ int iterate_lanes(Stepper* S, int kind, T* planes, size_t stride, const T* vol, 
   };
   // ---- deep lane, stage g: [B_(g-1)] -> C_g --------------------------------------------------------------------------------
   auto deep_stage = [=, &DL, &XL](int g) -> int {
-    const StageArgs a      = stage_args(g);
-    const bool      sample = timing > 0 && (g / 3) % timing == 0;
+    const StageArgs<T, V> a      = stage_args<T, V>(planes, stride, prev, next, speed, g);
+    const bool            sample = timing > 0 && (g / 3) % timing == 0;
     if (nd > 0) {
       if (g > 0) {
         if (!lane_wait_recorded(S, XL, g - 1)) return 0;
@@ -486,152 +425,42 @@ int iterate_lanes(Stepper* S, int kind, T* planes, size_t stride, const T* vol, 
   return rc_deep != 0 ? rc_deep : rc_comm;
 }
 
-// n_steps SSP-RK3 steps; (prev, next) are the roles of the FIRST step, they swap from step to step
-// (solver.cu:76). Multi-rank pipeline, per stage g (tile classes of tile_plan.cpp: C = deep interior,
-// B = interior tiles that read an element owned by an A tile, A = tiles that read ghost slots):
-//   caller's stream s : [B_(g-1)] -> C_g
-//   near stream       : [C_(g-1), A_(g-1)] -> B_g
-//   comm stream       : pack_g -> RCCL_g -> unpack_g -> [B_(g-1)] -> A_g
-// C_g reads only what B/C tiles of stage g-1 wrote; pack_g reads only elements next to a cut face, which A
-// tiles own (same stream, no wait); A_g reads ghosts, A- and B-owned elements; B_g reads all three classes
-// of stage g-1 but nothing of stage g, so it runs beside C_g instead of behind it. The long launch (C) and
-// the exchange chain therefore never wait for each other, and every bracketed dependency is normally
-// satisfied long before it is reached. Stages two apart are ordered transitively (C_g > B_(g-1) > all of
-// g-2, and so on), which is what the reuse of the four step buffers needs. The streams meet only at the
-// entry and at the exit of the call.
-// Subgrid blocks run through the same pipeline (SubgridCompressibleEulerSolver::iterate, examples/subgrid/solver.inl:
+// n_steps SSP-RK3 steps; (prev, next) are the roles of the FIRST step, they swap from step to step (solver.cu:76).
+// A stepper with peers runs the two-lane driver above. A single rank launches all its units [0, nt) once per stage on the
+// caller's stream (the deep lane's stream for the call, whose events time the sampled steps).
+// Subgrid blocks run through the same drivers (SubgridCompressibleEulerSolver::iterate, examples/subgrid/solver.inl:
 // 152-266): units are blocks in the plan's position order (deep interior, near-boundary, ghost-touching), a ghost
 // block mirrors all 4^rank subcells, `vol` is the separate per-block volume array of SubgridMemoryManager.
 template <class T, class V>
 int iterate(Stepper* S, int kind, T* planes, size_t stride, const T* vol, int prev, int next, T dt, T* speed, int n_steps,
             hipStream_t s) {
-  const int  nt = S->subgrid ? S->splan.num_elements : S->plan.ntiles;
-  const int  ni = S->subgrid ? S->splan.n_interior_blocks : S->plan.n_interior_tiles;
-  const int  ndeep = S->subgrid ? S->splan.n_deep_blocks : S->plan.n_deep_tiles;
-  const int  nd = (ndeep > 0 && ndeep <= ni) ? ndeep : 0;
-  const bool comm = S->has_halo && S->halo.n_peers > 0;
-  // several ranks, direct enqueue: the two-lane driver above. This function keeps the single-rank loop, and the three-stream
-  // pipeline for a hipGraph capture (whose fork / join shape the capture rules of this stack dictate) and for A/B
-  // measurements (T8GPU_STEPPER=legacy).
-  static const bool legacy = std::getenv("T8GPU_STEPPER") && std::strcmp(std::getenv("T8GPU_STEPPER"), "legacy") == 0;
-  if (comm && !S->capturing && !legacy) return iterate_lanes<T, V>(S, kind, planes, stride, vol, prev, next, dt, speed, n_steps, s);
-  t8gpu_hip::Range whole(comm ? "t8gpu.iterate_steps (exchange + 3 tile classes)" : "t8gpu.iterate_steps");
+  if (S->has_halo) return iterate_lanes<T, V>(S, kind, planes, stride, vol, prev, next, dt, speed, n_steps, s);
+  const int nt = S->subgrid ? S->splan.num_elements : S->plan.ntiles;
+  t8gpu_hip::Range whole("t8gpu.iterate_steps");
   static const char* const stage_name[3] = {"t8gpu.rk_stage1", "t8gpu.rk_stage2", "t8gpu.rk_stage3"};
-  hipEvent_t last_ghost = nullptr, last_interior = nullptr;
+  Stepper::Lane& L = S->deep_lane;
+  L.stream = s;
   for (int g = 0; g < 3 * n_steps; g++) {
-    const int k  = g % 3;
-    t8gpu_hip::Range stage_range(stage_name[k]);
-    S->sample    = S->timing > 0 && (g / 3) % S->timing == 0;
-    if (S->sample) S->stages_timed++;
-    const int pr = (g / 3) % 2 == 0 ? prev : next, nx = (g / 3) % 2 == 0 ? next : prev;
-    const int src = k == 0 ? pr : k, dst = k == 2 ? nx : k + 1;   // Step1 = 1, Step2 = 2 (solver.h:24-31)
-    const V   pv = step_vars<V>(planes, stride, pr), sv = step_vars<V>(planes, stride, src), ov = step_vars<V>(planes, stride, dst);
-    // The per-face speed estimates are rewritten by every stage and read only between steps (compute_timestep uses
-    // those "computed at the last step of the last timestepping", solver.h:88-91): only the third stage writes them
-    // (same contents after every step, a tenth less HBM traffic per step).
-    T* const stage_speed = k == 2 ? speed : nullptr;
-    auto launch = [&](int b, int n, hipStream_t on) -> int {
-      if (n <= 0) return 0;
-      HostTimer ht(0);
-      T8_TRY(tick(S, on));
-      if constexpr (sizeof(T) == 4) {
-        if (S->subgrid)
-          T8_TRY(t8gpu_hip_subgrid_fused_stage_f32(kind, k + 1, &S->splan, b, n, pv, sv, ov, vol, dt, on));
-        else
-          T8_TRY(t8gpu_hip_plain_fused_stage_f32(kind, k + 1, &S->plan, b, n, pv, sv, ov, vol, dt, stage_speed, on));
-      } else {
-        if (S->subgrid)
-          T8_TRY(t8gpu_hip_subgrid_fused_stage_f64(kind, k + 1, &S->splan, b, n, pv, sv, ov, vol, dt, on));
-        else
-          T8_TRY(t8gpu_hip_plain_fused_stage_f64(kind, k + 1, &S->plan, b, n, pv, sv, ov, vol, dt, stage_speed, on));
-      }
-      return tick(S, on);
-    };
-    if (!comm) {
-      T8_TRY(launch(0, nt, s));
-      continue;
-    }
-    // Roles of the three streams. Direct enqueue: the caller's stream carries the deep tiles (the long launch), the comm
-    // stream the exchange chain. Inside a capture the ORIGIN stream of the capture must carry the exchange chain: an RCCL
-    // group issued on a FORKED stream of a capture ends in a segmentation fault inside hipStreamEndCapture on this stack
-    // (HIP 7.0.51831 / RCCL 2.26.6; relaxed, global and thread-local capture modes alike -- T8GPU_GRAPH_VARIANT=5 keeps
-    // that layout for the opt-in diagnostic of tests/test_gpu_graph.py), issued on the origin stream it is captured and
-    // replayed correctly. A graph only knows dependencies, so the replayed pipeline has the same shape either way.
-    const bool        swap = S->capturing && S->capture_variant != 5;
-    const hipStream_t sc = swap ? S->comm_stream : s;    // C_g: deep tiles
-    const hipStream_t sx = swap ? s : S->comm_stream;    // pack_g -> RCCL_g -> unpack_g -> A_g
-    const hipStream_t sb = S->near_stream;               // B_g
-    if (g == 0) {  // entry: the other streams must see everything the caller queued on s
-      if (S->capturing && S->scratch) T8_HIP_TRY(hipMemsetAsync(S->scratch, 0, 64, s));   // a first node for the fork event
-      T8_HIP_TRY(hipEventRecord(S->ev_state, s));
-      T8_HIP_TRY(hipStreamWaitEvent(S->comm_stream, S->ev_state, 0));
-      T8_HIP_TRY(hipStreamWaitEvent(S->near_stream, S->ev_state, 0));
-    }
-    // every wait on an event of stage g-1 is issued before that event is re-recorded for stage g
-    hipEvent_t deep_p = nullptr, ghost_p = nullptr, inter_p = nullptr, deep_c, ghost_c, inter_c;
-    if (g > 0) {
-      T8_TRY(stage_event(S, g - 1, kDeep, &deep_p));
-      T8_TRY(stage_event(S, g - 1, kGhost, &ghost_p));
-      T8_TRY(stage_event(S, g - 1, kInterior, &inter_p));
-    }
-    T8_TRY(stage_event(S, g, kDeep, &deep_c));
-    T8_TRY(stage_event(S, g, kGhost, &ghost_c));
-    T8_TRY(stage_event(S, g, kInterior, &inter_c));
-    // (Measured and dropped in round 3: a TWO-class pipeline -- B and A tiles in one launch behind the unpack, 9 host calls
-    //  per stage instead of 13. The host cost fell from 170 to 146 us per step, but C_g then has to wait for the previous
-    //  stage's exchange chain and the step rose from 0.175 to 0.256 ms on rank 3 of the 8-way c4 split with an RCCL
-    //  self-exchange: the third class IS what keeps the long launch from waiting. profiles/r03_halo_overhead.md)
-    if (g > 0 && S->capturing) {
-      // Inside a capture every dependency goes through the origin stream: it joins the other streams' previous stage,
-      // records one event, and they fork from that (forked streams waiting on each other's events -- what the direct
-      // enqueue below does -- crashes the end of the capture as well, with or without RCCL in it). Costs edges the
-      // pipeline does not need: stage g starts when all of stage g-1 is done.
-      hipEvent_t join;
-      T8_TRY(stage_event(S, g, kJoin, &join));
-      T8_HIP_TRY(hipStreamWaitEvent(s, inter_p, 0));
-      T8_HIP_TRY(hipStreamWaitEvent(s, swap ? deep_p : ghost_p, 0));   // (the third class of g-1 ran on s itself)
-      T8_HIP_TRY(hipEventRecord(join, s));
-      T8_HIP_TRY(hipStreamWaitEvent(S->near_stream, join, 0));
-      T8_HIP_TRY(hipStreamWaitEvent(S->comm_stream, join, 0));
-    } else if (g > 0) {
-      HostTimer ht(3);
-      T8_HIP_TRY(hipStreamWaitEvent(sb, deep_p, 0));                       // B_g <- C_(g-1)
-      T8_HIP_TRY(hipStreamWaitEvent(sb, ghost_p, 0));                      // B_g <- A_(g-1)
-      T8_HIP_TRY(hipStreamWaitEvent(sc, inter_p, 0));                      // C_g <- B_(g-1)
-    }
-    T8_TRY(launch(0, nd, sc));                                             // C_g
-    { HostTimer ht(2); T8_HIP_TRY(hipEventRecord(deep_c, sc)); }
-    T8_TRY((exchange<T, V>(S->halo, S->peers.data(), S->send_off.data(), S->recv_off.data(), sv, sx)));
-    if (g > 0 && !S->capturing) { HostTimer ht(3); T8_HIP_TRY(hipStreamWaitEvent(sx, inter_p, 0)); }               // A_g <- B_(g-1)
-    T8_TRY(launch(ni, nt - ni, sx));                                       // A_g
-    { HostTimer ht(2); T8_HIP_TRY(hipEventRecord(ghost_c, sx)); }
-    T8_TRY(launch(nd, ni - nd, sb));                                       // B_g
-    { HostTimer ht(2); T8_HIP_TRY(hipEventRecord(inter_c, sb)); }
-    last_ghost    = swap ? deep_c : ghost_c;   // (what the exit below joins: the two streams that are not s)
-    last_interior = inter_c;
-  }
-  if (comm && n_steps > 0) {  // exit: everything is ordered on s again
-    T8_HIP_TRY(hipStreamWaitEvent(s, last_ghost, 0));
-    T8_HIP_TRY(hipStreamWaitEvent(s, last_interior, 0));
+    const StageArgs<T, V> a = stage_args<T, V>(planes, stride, prev, next, speed, g);
+    t8gpu_hip::Range stage_range(stage_name[a.k]);
+    const bool sample = S->timing > 0 && (g / 3) % S->timing == 0;
+    if (sample) S->stages_timed++;
+    T8_TRY((launch_stage<T, V>(S, L, kind, &S->plan, a, 0, nt, vol, dt, sample)));
   }
   return 0;
 }
 
-// iterate() through a hipGraph: capture the enqueue sequence once per argument set, then replay it. The capture runs
-// on the stepper's own origin stream (the caller's stream may be the legacy default stream, which cannot capture);
-// the comm and near streams join the capture through the events they wait on, and rejoin before it ends. Timing
-// events are off in graph mode. With a halo the RCCL group is captured too (RCCL enqueues its kernels on the capturing
-// stream); if the runtime refuses any part of the capture the error is returned and the caller falls back.
+// iterate() of a single-rank stepper through a hipGraph: capture the enqueue sequence once per argument set, then replay
+// it. The capture runs on the stepper's own origin stream (the caller's stream may be the legacy default stream, which
+// cannot capture). Timing events are off in graph mode, and a stepper with peers always enqueues directly (the two-lane
+// driver). If the runtime refuses the capture the error is returned and the caller falls back.
+// (Round 3 could capture the RCCL groups of a multi-rank stepper too, opt-in; never run across xGMI, more host time than the
+//  lanes, and a crash inside the HIP runtime's hipStreamEndCapture for some layouts: removed)
 template <class T, class V>
 int iterate_graph(Stepper* S, int kind, T* planes, size_t stride, const T* vol, int prev, int next, T dt, T* speed, int n_steps,
                   hipStream_t s) {
-  if (!S->graph_mode || S->timing > 0 || n_steps <= 0) return iterate<T, V>(S, kind, planes, stride, vol, prev, next, dt, speed, n_steps, s);
-  // Multi-rank stages have an RCCL group in the middle. Capturing it is OPT-IN (T8GPU_GRAPH_RCCL=1): a replayed RCCL group
-  // has only ever run on one GPU exchanging with itself (tests/test_gpu_graph.py), never across xGMI, the capture has to
-  // route every dependency through the origin stream (see iterate()), and hipGraphLaunch costs this stack more host time
-  // than the two-lane direct enqueue (profiles/r04_halo_overhead.md). By default a stepper with peers enqueues directly.
-  static const bool rccl_capture = std::getenv("T8GPU_GRAPH_RCCL") && std::getenv("T8GPU_GRAPH_RCCL")[0] == '1';
-  if (S->has_halo && S->halo.n_peers > 0 && !rccl_capture) return iterate<T, V>(S, kind, planes, stride, vol, prev, next, dt, speed, n_steps, s);
+  if (!S->graph_mode || S->timing > 0 || n_steps <= 0 || S->has_halo)
+    return iterate<T, V>(S, kind, planes, stride, vol, prev, next, dt, speed, n_steps, s);
   struct Key {
     int kind, prev, next, n_steps, tsize, subgrid;
     const void *planes, *vol, *speed;
@@ -658,36 +487,14 @@ int iterate_graph(Stepper* S, int kind, T* planes, size_t stride, const T* vol, 
       lru->exec = nullptr;
     }
     hipGraph_t g = nullptr;
-    static const bool trace = std::getenv("T8GPU_DEBUG_GRAPH") != nullptr;   // progress marks on stderr (diagnostics)
-#define T8_MARK(what) do { if (trace) { std::fprintf(stderr, "[t8gpu graph] %s\n", what); std::fflush(stderr); } } while (0)
-    T8_MARK("begin capture");
-    S->capture_variant = std::getenv("T8GPU_GRAPH_VARIANT") ? std::atoi(std::getenv("T8GPU_GRAPH_VARIANT")) : 0;
-    if (!S->scratch) T8_HIP_TRY(hipMalloc(&S->scratch, 64));
-    {   // every event a capture of this length needs exists before the capture starts
-      struct Capturing {   // (reset on every way out of this block, early error returns included)
-        Stepper* s;
-        explicit Capturing(Stepper* p) : s(p) { s->capturing = true; }
-        ~Capturing() { s->capturing = false; }
-      } guard(S);
-      hipEvent_t e;
-      for (int g2 = 0; g2 < 3 * n_steps; g2++)
-        for (int r = 0; r < 4; r++) T8_TRY(stage_event(S, g2, static_cast<EventRole>(r), &e));
-    }
-    const hipStreamCaptureMode cmode = S->capture_variant == 2 ? hipStreamCaptureModeGlobal
-                                                                : (S->capture_variant == 3 ? hipStreamCaptureModeThreadLocal : hipStreamCaptureModeRelaxed);
-    T8_HIP_TRY(hipStreamBeginCapture(S->graph_stream, cmode));
-    S->capturing  = true;
+    T8_HIP_TRY(hipStreamBeginCapture(S->graph_stream, hipStreamCaptureModeRelaxed));
     const int  rc = iterate<T, V>(S, kind, planes, stride, vol, prev, next, dt, speed, n_steps, S->graph_stream);
-    S->capturing  = false;
-    T8_MARK("enqueue recorded");
     hipError_t e  = hipStreamEndCapture(S->graph_stream, &g);
-    T8_MARK("capture ended");
     if (rc != 0 || e != hipSuccess || !g) {
       if (g) (void)hipGraphDestroy(g);
       return rc != 0 ? rc : static_cast<int>(e != hipSuccess ? e : hipErrorStreamCaptureInvalidated);
     }
     e = hipGraphInstantiate(&lru->exec, g, nullptr, nullptr, 0);
-    T8_MARK("instantiated");
     (void)hipGraphDestroy(g);
     if (e != hipSuccess) {
       lru->exec = nullptr;
@@ -702,7 +509,6 @@ int iterate_graph(Stepper* S, int kind, T* planes, size_t stride, const T* vol, 
   T8_HIP_TRY(hipEventRecord(S->ev_graph_in, s));                         // the graph starts behind the caller's work ...
   T8_HIP_TRY(hipStreamWaitEvent(S->graph_stream, S->ev_graph_in, 0));
   T8_HIP_TRY(hipGraphLaunch(hit->exec, S->graph_stream));
-  if (std::getenv("T8GPU_DEBUG_GRAPH")) { std::fprintf(stderr, "[t8gpu graph] launched\n"); std::fflush(stderr); }
   T8_HIP_TRY(hipEventRecord(S->ev_graph_out, S->graph_stream));
   T8_HIP_TRY(hipStreamWaitEvent(s, S->ev_graph_out, 0));                 // ... and the caller's stream continues behind it
   S->graph_replays++;
@@ -740,7 +546,6 @@ int repartition(void* comm, int my_rank, int n_send, const int32_t* send_peer, c
   for (int j = 0; j < n_recv; j++) remote = remote || recv_peer[j] != my_rank;
   if (!remote) return 0;
   if (!comm) return static_cast<int>(hipErrorInvalidValue);
-#ifndef T8GPU_EXP_NO_RCCL
   ncclComm_t c = static_cast<ncclComm_t>(comm);
   T8_TRY(nccl_code(ncclGroupStart()));
   for (int j = 0; j < n_recv; j++) {
@@ -756,7 +561,6 @@ int repartition(void* comm, int my_rank, int n_send, const int32_t* send_peer, c
     T8_TRY(nccl_code(ncclSend(src_vol + send_first[j], n, nccl_type<T>(), send_peer[j], c, s)));
   }
   T8_TRY(nccl_code(ncclGroupEnd()));
-#endif
   return 0;
 }
 }  // namespace
@@ -808,11 +612,11 @@ int t8gpu_hip_comm_abort(void* comm) { return comm ? nccl_code(ncclCommAbort(sta
 
 int t8gpu_hip_halo_exchange_f32(const T8gpuHalo* h, T8gpuVars_f32 state, void* stream) {
   if (!h) return static_cast<int>(hipErrorInvalidValue);
-  return exchange<float, T8gpuVars_f32>(*h, h->peers, h->send_off, h->recv_off, state, static_cast<hipStream_t>(stream));
+  return exchange<float, T8gpuVars_f32>(*h, state, static_cast<hipStream_t>(stream));
 }
 int t8gpu_hip_halo_exchange_f64(const T8gpuHalo* h, T8gpuVars_f64 state, void* stream) {
   if (!h) return static_cast<int>(hipErrorInvalidValue);
-  return exchange<double, T8gpuVars_f64>(*h, h->peers, h->send_off, h->recv_off, state, static_cast<hipStream_t>(stream));
+  return exchange<double, T8gpuVars_f64>(*h, state, static_cast<hipStream_t>(stream));
 }
 
 int t8gpu_hip_repartition_f32(void* comm, int my_rank, int n_send, const int32_t* send_peer, const int32_t* send_first,
@@ -840,7 +644,6 @@ int t8gpu_hip_comm_allgatherv_f64(void* comm, int rank, int nranks, const double
   if (n) T8_HIP_TRY(hipMemcpyAsync(all + offsets[rank], mine, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
   if (nranks == 1) return 0;
   if (!comm) return static_cast<int>(hipErrorInvalidValue);
-#ifndef T8GPU_EXP_NO_RCCL
   ncclComm_t c = static_cast<ncclComm_t>(comm);
   T8_TRY(nccl_code(ncclGroupStart()));
   for (int q = 0; q < nranks; q++) {
@@ -850,7 +653,6 @@ int t8gpu_hip_comm_allgatherv_f64(void* comm, int rank, int nranks, const double
     if (n) T8_TRY(nccl_code(ncclSend(mine, n, ncclDouble, q, c, s)));
   }
   T8_TRY(nccl_code(ncclGroupEnd()));
-#endif
   return 0;
 }
 
@@ -881,14 +683,9 @@ static int stepper_halo_setup(Stepper* S, const T8gpuHalo* halo) {
     //  rank 3 of the 8-way c4 split)
     hipError_t e = hipStreamCreateWithFlags(&S->comm_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&S->ev_state, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&S->ev_ghost, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&S->ev_interior, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&S->ev_deep, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&S->near_stream, hipStreamNonBlocking);
     // the lanes' events order two queues of ONE device: a device-scope release is all they need (the default is a
-    // system-scope fence per record). T8GPU_EVENT_SCOPE=system keeps the default (measurements).
-    const char*    scope = std::getenv("T8GPU_EVENT_SCOPE");
-    const unsigned flags = hipEventDisableTiming | ((scope && scope[0] == 's') ? 0u : static_cast<unsigned>(hipEventReleaseToDevice));
+    // system-scope fence per record)
+    const unsigned flags = hipEventDisableTiming | hipEventReleaseToDevice;
     for (int i = 0; i < Stepper::kRing && e == hipSuccess; i++) {
       e = hipEventCreateWithFlags(&S->deep_lane.ring[i], flags);
       if (e == hipSuccess) e = hipEventCreateWithFlags(&S->comm_lane.ring[i], flags);
@@ -996,17 +793,10 @@ int t8gpu_hip_plain_stepper_destroy(void* h) {
   }
   if (S->d_send_map) (void)hipFree(S->d_send_map);
   if (S->d_send_list) (void)hipFree(S->d_send_list);
-  for (hipEvent_t e : S->pool) (void)hipEventDestroy(e);
   if (S->ev_state) (void)hipEventDestroy(S->ev_state);
-  if (S->ev_ghost) (void)hipEventDestroy(S->ev_ghost);
-  if (S->ev_interior) (void)hipEventDestroy(S->ev_interior);
-  if (S->ev_deep) (void)hipEventDestroy(S->ev_deep);
   if (S->comm_stream) (void)hipStreamDestroy(S->comm_stream);
-  if (S->near_stream) (void)hipStreamDestroy(S->near_stream);
   for (auto& ge : S->graph_cache)
     if (ge.exec) (void)hipGraphExecDestroy(ge.exec);
-  for (hipEvent_t e : S->capture_events) (void)hipEventDestroy(e);
-  if (S->scratch) (void)hipFree(S->scratch);
   if (S->ev_graph_in) (void)hipEventDestroy(S->ev_graph_in);
   if (S->ev_graph_out) (void)hipEventDestroy(S->ev_graph_out);
   if (S->graph_stream) (void)hipStreamDestroy(S->graph_stream);
@@ -1052,8 +842,9 @@ int t8gpu_hip_subgrid_stepper_iterate_steps_f64(void* h, int flux_kind, double* 
                                               n_steps, static_cast<hipStream_t>(stream));
 }
 
-// hipGraph replay of iterate_steps() (both step drivers): enable = 1 captures the whole call once per argument set and
-// replays it with one hipGraphLaunch; 0 enqueues directly. counts (may be NULL) = {captures, replays} so far.
+// hipGraph replay of a single-rank stepper's iterate_steps(): enable = 1 captures the whole call once per argument set and
+// replays it with one hipGraphLaunch; 0 enqueues directly. A stepper with peers always enqueues directly. counts (may be
+// NULL) = {captures, replays} so far.
 int t8gpu_hip_plain_stepper_graph(void* h, int enable, int* counts) {
   Stepper* S = static_cast<Stepper*>(h);
   if (!S) return static_cast<int>(hipErrorInvalidValue);
@@ -1115,7 +906,6 @@ int t8gpu_hip_plain_stepper_timing(void* h, int enable) {
   if (!S) return static_cast<int>(hipErrorInvalidValue);
   S->timing = enable < 0 ? 0 : enable;
   S->stages_timed = 0;
-  S->used   = 0;
   S->deep_lane.used = S->comm_lane.used = 0;
   return 0;
 }
@@ -1135,8 +925,7 @@ int t8gpu_hip_plain_stepper_elapsed(void* h, double* total_ms, int* launches) {
     }
     return 0;
   };
-  T8_TRY(add(S->pool, S->used));
-  T8_TRY(add(S->deep_lane.pool, S->deep_lane.used));   // (the two-lane driver's launches)
+  T8_TRY(add(S->deep_lane.pool, S->deep_lane.used));   // (a single rank's launches are all on the deep lane)
   T8_TRY(add(S->comm_lane.pool, S->comm_lane.used));
   *total_ms = sum;
   *launches = n;

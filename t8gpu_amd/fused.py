@@ -77,10 +77,10 @@ class PlainPlan:
         # (amr._inherited_plan_options); None: the default
         self.auto_fcap = given_fcap
         # Partitioned meshes: interior tiles in ONE class (tile_order = interior | ghost-reading) -- the two-lane step driver
-        # (stepper.hip) launches [0, n_interior) as one kernel per stage. two_classes=False / T8GPU_PLAN_CLASSES=3 keeps the
-        # deep / near-boundary split (what the three-stream pipeline of rounds 1-3 wants: T8GPU_STEPPER=legacy).
+        # (stepper.hip) launches [0, n_interior) as one kernel per stage. two_classes=False keeps the deep / near-boundary
+        # split (the lanes then run the near-boundary tiles on the comm lane behind the ghost-reading ones).
         if two_classes is None:
-            two_classes = getattr(part, "nranks", 1) > 1 and os.environ.get("T8GPU_PLAN_CLASSES", "2") != "3"
+            two_classes = getattr(part, "nranks", 1) > 1
         self.two_classes = bool(two_classes)
         retry_768 = given_fcap in (384, 480) and dtype == torch.float64      # an inherited cap still has to fit the persistent kernel
         if (fcap is None and "T8GPU_FCAP" not in os.environ and not small and dtype == torch.float64 and

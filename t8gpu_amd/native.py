@@ -148,7 +148,7 @@ class NativeStepper:
 
 class NativeSubgridStepper(NativeStepper):
     """t8gpu_hip_subgrid_stepper_*: SubgridCompressibleEulerSolver::iterate enqueued by one C call (block classes on
-    three streams, one RCCL exchange of whole ghost blocks per stage)."""
+    the two lanes, one RCCL exchange of whole ghost blocks per stage)."""
 
     def __init__(self, plan, halo=None):
         self.plan, self.halo = plan, halo

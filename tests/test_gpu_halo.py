@@ -247,7 +247,7 @@ def k_way_subgrid(mesh, world, mode, dim, both_classes):
                                                 (torch.float64, (8, 30), 2), (torch.float32, (8, 30), 3), (torch.float64, (256, 512), 2),
                                                 (torch.float64, (256, 512), 3), (torch.float64, (4000, 512), 3)])
 def test_native_stepper_with_rccl_self_exchange_on_a_symmetric_problem(dtype, caps, classes):
-    """The C++ step driver with its RCCL exchange and two-stream pipeline, with REAL data dependencies, on one
+    """The C++ step driver with its RCCL exchange and two lanes, with REAL data dependencies, on one
     GPU: the mesh and the state are invariant under y -> y + 1/2, which maps the lower half of the Morton
     curve (rank 0 of 2) onto the upper half (rank 1) in order. What rank 1 would send to rank 0 is then
     exactly what rank 0 sends to rank 1, so rank 0 can exchange with ITSELF through a one-rank RCCL
@@ -316,7 +316,7 @@ def test_native_stepper_with_rccl_self_exchange_on_a_symmetric_problem(dtype, ca
 @pytest.mark.parametrize("dtype,dim", [(torch.float32, 2), (torch.float64, 2), (torch.float64, 3), (torch.float32, 3)])
 def test_native_subgrid_stepper_with_rccl_self_exchange_on_a_symmetric_problem(dtype, dim):
     """The C++ step driver for Subgrid blocks (t8gpu_hip_subgrid_stepper_*: deep / near-boundary / ghost-touching
-    blocks on three streams, whole ghost blocks over RCCL), with real data dependencies on one GPU: mesh and state
+    blocks on the two lanes, whole ghost blocks over RCCL), with real data dependencies on one GPU: mesh and state
     are invariant under a shift by 1/2 along the last axis, which maps rank 0's half of the Morton curve onto rank
     1's, so rank 0 exchanges with itself through a one-rank RCCL communicator and must reproduce the single-rank
     run on its half (to rounding: a block and its image list their remaining coarse faces in different orders; a ghost
