@@ -1,0 +1,94 @@
+#!/usr/bin/env python3
+"""Adaptive 2D four-quadrant Riemann problem on [0, 1]^2 with outflow on all four sides (one MI355X): the structure of
+kelvin_helmholtz_amr.py -- adapt every N steps by the reference's gradient indicator, iterate with the fused kernels and
+the native step driver -- on a mesh with open boundaries (SynthMesh(..., sides=...)).
+
+Initial state (Lax & Liu 1998, configuration 3): four constant states meeting at (0.5, 0.5); four shocks run out of the
+corners and leave through the sides, which a reflective wall would send back.
+
+    python examples/riemann2d_amr.py --t-end 0.3 --min-level 5 --max-level 9 --out out/riemann2d
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from t8gpu_amd import amr, vtk  # noqa: E402
+from t8gpu_amd.solver import PlainSolver  # noqa: E402
+from t8gpu_amd.synth import SynthMesh  # noqa: E402
+
+GAMMA = 1.4
+# (rho, u, v, p) of the quadrants NE, NW, SW, SE
+QUADRANTS = ((1.5, 0.0, 0.0, 1.5), (0.5323, 1.206, 0.0, 0.3), (0.138, 1.206, 1.206, 0.029), (0.5323, 0.0, 1.206, 0.3))
+
+
+def initial_state(part):
+    x, y = part.centres[:, 0], part.centres[:, 1]
+    q = np.where(x >= 0.5, np.where(y >= 0.5, 0, 3), np.where(y >= 0.5, 1, 2))
+    rho, u, v, p = (np.array([s[k] for s in QUADRANTS])[q] for k in range(4))
+    return np.stack([rho, rho * u, rho * v, 0 * rho, p / (GAMMA - 1) + 0.5 * rho * (u * u + v * v)])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--t-end", type=float, default=0.3)
+    ap.add_argument("--adapt-every", type=int, default=20)
+    ap.add_argument("--min-level", type=int, default=5)
+    ap.add_argument("--max-level", type=int, default=9)
+    ap.add_argument("--threshold", type=float, default=10.0)     # mesh_manager.inl:141
+    ap.add_argument("--cfl", type=float, default=0.35)
+    ap.add_argument("--out", default=None, help="directory of the .vtu written at the end (density, energy, momentum)")
+    ap.add_argument("--toy", action="store_true", help="levels 3-5, t_end 0.05 (a quick check)")
+    args = ap.parse_args()
+    if args.toy:
+        args.min_level, args.max_level, args.t_end, args.adapt_every = 3, 5, 0.05, 5
+
+    sides = ("outflow",) * 4
+    mesh = SynthMesh(2, args.min_level, args.min_level, sides=sides)
+    solver = PlainSolver(mesh.partition(), torch.float64, mode="fused", state=initial_state(mesh.partition()))
+
+    def adapt(s):
+        return amr.adapt(s, args.threshold, args.min_level, args.max_level)[0]
+
+    for _ in range(args.max_level - args.min_level):      # refine around the discontinuities, then re-evaluate the state
+        solver = adapt(solver)
+        ic = torch.from_numpy(initial_state(solver.part)).to(solver.dtype).cuda()
+        solver.planes[5 * solver.next:5 * solver.next + 5] = ic
+    solver.use_native_stepper()
+    t, it, cells, t_iter = 0.0, 0, 0, 0.0
+    while t < args.t_end - 1e-12:
+        if it % args.adapt_every == 0 and it > 0:
+            solver = adapt(solver)
+            solver.use_native_stepper()
+        if it == 0:
+            dt = 0.1 * 2.0 ** -solver.part.mesh.finest_level
+        else:
+            dt = solver.compute_timestep(cfl=args.cfl)             # CFL step from the speeds of the last step (open faces too)
+        dt = min(dt, args.t_end - t)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        solver.iterate(dt)
+        torch.cuda.synchronize()
+        t_iter += time.perf_counter() - t0
+        t += dt
+        it += 1
+        cells += solver.N
+        if it % 50 == 0:
+            print(f"it {it:5d}  t {t:.4f}  elements {solver.N:8d}  finest level {solver.part.mesh.finest_level}  dt {dt:.3e}",
+                  flush=True)
+    assert bool(torch.isfinite(solver.state()).all())
+    print(f"t = {t:.4f} after {it} steps, {solver.N} elements; {cells / t_iter / 1e6:.1f} M cell-updates/s (host-synchronised)")
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        fields = [vtk.get_host_scalar_variable(solver, solver.next, 0, "density"),
+                  vtk.get_host_scalar_variable(solver, solver.next, 4, "energy"),
+                  vtk.get_host_vector_variable(solver, solver.next, (1, 2, 3), "momentum")]
+        print("wrote", vtk.save_variables_to_vtk(solver, fields, os.path.join(args.out, "riemann2d")))
+
+
+if __name__ == "__main__":
+    main()

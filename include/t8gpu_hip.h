@@ -75,6 +75,18 @@ int t8gpu_hip_flux_boundary_f64(int flux_kind, int num_faces, int num_boundary_f
                                 const int32_t* face_neighbors, const double* face_normals,
                                 const double* face_surfaces, T8gpuVars_f64 state, T8gpuVars_f64 fluxes,
                                 double* speed_estimates, void* stream);
+/* The boundary faces with their kinds (t8gpu_host.h: boundary_kinds[B], device copy): walls as above; outflow faces evaluate
+ * the interior face flux with the outside state = the inside one; inflow faces with the outside state = the conservative
+ * state k of `inflow_table` (t8gpu_hip_plain_inflow_table_*; may be NULL when no face is an inflow face).
+ * boundary_kinds = NULL is t8gpu_hip_flux_boundary_*. */
+int t8gpu_hip_flux_boundary_bc_f32(int flux_kind, int num_faces, int num_boundary_faces, int normal_dim,
+                                   const int32_t* face_neighbors, const uint8_t* boundary_kinds, const float* inflow_table,
+                                   const float* face_normals, const float* face_surfaces, T8gpuVars_f32 state,
+                                   T8gpuVars_f32 fluxes, float* speed_estimates, void* stream);
+int t8gpu_hip_flux_boundary_bc_f64(int flux_kind, int num_faces, int num_boundary_faces, int normal_dim,
+                                   const int32_t* face_neighbors, const uint8_t* boundary_kinds, const double* inflow_table,
+                                   const double* face_normals, const double* face_surfaces, T8gpuVars_f64 state,
+                                   T8gpuVars_f64 fluxes, double* speed_estimates, void* stream);
 
 /* timestepping::SSP_3RK_step{1,2,3}<V><<<ceil(N/256),256>>>, t8gpu/timestepping/ssp_runge_kutta.inl:30-99.
  * stage 1: out = prev + dt/vol*f;  stage 2: out = .75 prev + .25 mid + .25 dt/vol*f;
@@ -135,7 +147,7 @@ typedef struct T8gpuPlainPlan {
   const int32_t*  halo_off;   /* [ntiles+1] into halo_ids                                         */
   const int32_t*  face_off;   /* [ntiles+1] into face_*                                           */
   const int32_t*  halo_ids;   /* slots of outside elements (other tiles / ghost mirrors)          */
-  const uint32_t* face_lr;    /* tile-local l | r << 16 (r = 0xFFFF: reflective wall)             */
+  const uint32_t* face_lr;    /* tile-local l | r << 16 (r = 0xFFFF: reflective wall; 0xFFFE, 0xFFF0 + k: open, ABI 9) */
   const void*     face_geo;   /* float_type [n_faces][4] = nx, ny, nz, area                       */
   const int32_t*  face_orig;  /* original face index if this tile reports the speed, else -1      */
   const int32_t*  csr_off;    /* [N+1] into csr_ent. The two CSR arrays are read by the generic kernel only: may be NULL where `ell`
@@ -196,7 +208,25 @@ typedef struct T8gpuPlainPlan {
   void*          send_buf;    /* DEVICE float_type [5 * n_send], element-major                              */
   int32_t        n_owned;     /* N: first ghost slot                                                        */
   int32_t        reserved7;
+  /* OPEN BOUNDARIES (ABI 9). A plan built with boundary_kinds (t8gpu_host.h: t8gpu_plan_plain_create_bc) encodes the r half of
+   * a boundary face's face_lr as 0xFFFF (reflective wall), 0xFFFE (outflow: the outside state is the inside one) or
+   * 0xFFF0 + k (inflow with prescribed state k). has_open_faces = 1 selects the kernels that decode the two open codes; 0 (a
+   * zeroed tail) is the behaviour of earlier ABIs: every boundary face a wall. `inflow` is the table of the prescribed
+   * states, filled once by t8gpu_hip_plain_inflow_table_*; it must be given (at least one entry, hipErrorInvalidValue
+   * otherwise) whenever has_open_faces is set, and holds an entry for every inflow code of the plan. No launch writes it. The persistent tile kernel does not take plans with open faces (t8gpu_hip_plain_persistent_accepts says 0):
+   * their launches run the one-tile kernels, which give the same bits. */
+  const void*    inflow;      /* DEVICE float_type [K][T8GPU_INFLOW_WORDS]                                  */
+  int32_t        has_open_faces;
+  int32_t        reserved9;
 } T8gpuPlainPlan;
+
+/* One inflow-table entry: the conservative state (5 values), the 9 per-element KEPES quantities the tile kernels derive from a
+ * state (rho, v, p, beta, log rho, log beta, entropy term: the same device routine the tiles run for their cells, so an inflow
+ * state equal to a cell's state gives that cell's bits), 2 words of padding. */
+#define T8GPU_INFLOW_WORDS 16
+/* table[K][T8GPU_INFLOW_WORDS] (DEVICE, float_type) from states[K][5] (DEVICE, float_type, conservative), K <= 8. */
+int t8gpu_hip_plain_inflow_table_f32(const float* states, int num_states, float* table, void* stream);
+int t8gpu_hip_plain_inflow_table_f64(const double* states, int num_states, double* table, void* stream);
 
 /* tile_begin/tile_count select a range of tile_order (0, ntiles = everything; [0, n_interior) can run
  * while the halo exchange of `src` is still in flight, [n_interior, ntiles) after it). mid = state

@@ -18,8 +18,25 @@
 extern "C" {
 #endif
 
+/* ---- boundary kinds --------------------------------------------------------------------------
+ * boundary_kinds[B] (uint8, one entry per boundary face, in the order of the boundary entries of face_neighbors):
+ * 0 reflective wall, 1 outflow (zero gradient: the outside state is the inside one), 2 + k inflow with prescribed
+ * conservative state k (k < T8GPU_MAX_INFLOW_STATES). An absent array (NULL) means every boundary face is a wall. */
+#define T8GPU_BOUNDARY_WALL 0
+#define T8GPU_BOUNDARY_OUTFLOW 1
+#define T8GPU_BOUNDARY_INFLOW 2
+#define T8GPU_MAX_INFLOW_STATES 8
+
 /* ---- synthetic mesh -------------------------------------------------------------------------- */
+/* periodic != 0: every side periodic, else every side a wall */
 void*   t8gpu_synth_mesh_create(int dim, int base_level, int max_level, double band, double shrink, int periodic);
+/* sides[2 * dim] in the order -x, +x, -y, +y, -z, +z: -1 periodic, 0 wall, 1 outflow, 2 + k inflow state k. A periodic
+ * side must be paired with the opposite side of its axis. NULL on invalid parameters (t8gpu_synth_check_sides: 0 valid,
+ * 1 a code out of range, 2 an unpaired periodic side). adapt / adapt_by_rounds / partitions keep the sides. */
+void*   t8gpu_synth_mesh_create_sides(int dim, int base_level, int max_level, double band, double shrink, const int* sides);
+int     t8gpu_synth_check_sides(int dim, const int* sides);
+/* sides[6] of the mesh (entries past 2 * dim are -1); returns 2 * dim */
+int     t8gpu_synth_mesh_sides(const void* mesh, int* sides);
 void    t8gpu_synth_mesh_destroy(void* mesh);
 int64_t t8gpu_synth_mesh_num_elements(const void* mesh);
 int     t8gpu_synth_mesh_finest_level(const void* mesh);
@@ -35,6 +52,8 @@ void t8gpu_synth_part_connectivity(const void* part, int32_t* face_neighbors, do
 /* the same arrays in place (no copy): ptrs[5] = {face_neighbors, normals, areas, face_level_difference, face_neighbor_offset},
  * null where empty; valid until t8gpu_synth_part_release_arrays / _destroy */
 void t8gpu_synth_part_connectivity_ptrs(const void* part, const void** ptrs);
+/* boundary_kinds[B] of the partition in place (NULL when B = 0); valid as the arrays above */
+const uint8_t* t8gpu_synth_part_boundary_kinds(const void* part);
 /* per owned + ghost element: level[N+G], volume[N+G], centre[(N+G)*3] */
 void t8gpu_synth_part_elements(const void* part, int32_t* level, double* volume, double* centre);
 void t8gpu_synth_part_halo(const void* part, int64_t* ghost_global, int32_t* ghost_owner, int32_t* peers,
@@ -75,6 +94,14 @@ void* t8gpu_plan_plain_create(int32_t N, int32_t G, int32_t F, int32_t B, int32_
  * is then ONE kernel launch, which is what the two-lane step driver of the multi-rank path wants (csrc/hip/stepper.hip). */
 void* t8gpu_plan_plain_create_ex(int32_t N, int32_t G, int32_t F, int32_t B, int32_t ndim, const int32_t* face_neighbors,
                                  const double* normals, const double* areas, int32_t tmax, int32_t fcap, int32_t flags);
+/* The same with boundary_kinds[B] (NULL: every boundary face a wall -- what _ex does). An open boundary face (outflow /
+ * inflow) is encoded in face_lr as r = 0xFFFE (outflow) or 0xFFF0 + k (inflow k); walls keep 0xFFFF, so tile-local
+ * indices stay below 0xFFF0. A cell with an open face never goes into a patch (2D or 3D): it runs through the generic
+ * tiles. t8gpu_plan_plain_open_faces tells whether the plan has open faces at all (T8gpuPlainPlan::has_open_faces). */
+void* t8gpu_plan_plain_create_bc(int32_t N, int32_t G, int32_t F, int32_t B, int32_t ndim, const int32_t* face_neighbors,
+                                 const double* normals, const double* areas, const uint8_t* boundary_kinds, int32_t tmax,
+                                 int32_t fcap, int32_t flags);
+int32_t t8gpu_plan_plain_open_faces(const void* plan);
 void  t8gpu_plan_plain_destroy(void* plan);
 /* counts[4] = leading patch tiles of the deep / near-boundary / ghost-reading class of tile_order, total */
 void  t8gpu_plan_plain_patch_counts(const void* plan, int32_t* counts);

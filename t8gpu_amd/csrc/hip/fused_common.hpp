@@ -98,6 +98,35 @@ T8_DEV void ghost_window_send(const T8gpuPlainPlan& P, int e, const T v[5]) {
   }
 }
 
+// ---- boundary faces of the tile plan (ABI 9) ------------------------------------------------------------------------
+// The r half of a face_lr entry (tile_plan.cpp: boundary_code): a tile-local slot below 0xFFF0, else 0xFFFF reflective wall,
+// 0xFFFE outflow, 0xFFF0 + k inflow state k. The one place that spells the codes; only the OPEN instantiations of the tile
+// kernels decode the open ones (the others see walls only, as before ABI 9).
+struct FaceSide {
+  int  r;        // slot of the right state in LDS: the neighbour, or l itself at a boundary face
+  bool wall;     // reflective wall: the right state is the mirror image of the left one
+  bool open;     // outflow or inflow: no right element to update
+  int  inflow;   // inflow state index, -1 otherwise
+};
+T8_DEV FaceSide decode_face_side(int l, unsigned r16) {
+  FaceSide f;
+  f.wall   = r16 == 0xFFFFu;
+  f.open   = r16 >= 0xFFF0u && r16 < 0xFFFFu;
+  f.inflow = r16 >= 0xFFF0u && r16 < 0xFFFEu ? static_cast<int>(r16 - 0xFFF0u) : -1;
+  f.r      = r16 >= 0xFFF0u ? l : static_cast<int>(r16);
+  return f;
+}
+// the conservative state (words 0-4) and the KEPES per-element record (words 5-13) of inflow state k
+template <class T>
+T8_DEV const T* inflow_entry(const T8gpuPlainPlan& P, int k) {
+  return static_cast<const T*>(P.inflow) + T8GPU_INFLOW_WORDS * k;
+}
+template <class T>
+T8_DEV void inflow_prim(const T8gpuPlainPlan& P, int k, Prim<T>& q) {
+  const T* w = inflow_entry<T>(P, k) + 5;
+  q.rho = w[0]; q.vx = w[1]; q.vy = w[2]; q.vz = w[3]; q.p = w[4]; q.beta = w[5]; q.lrho = w[6]; q.lbeta = w[7]; q.v0 = w[8];
+}
+
 // ---- LDS records of the persistent kernels (kernels_fused_persistent.hip, kernels_fused_patch.hip) ---------------
 template <class T>
 struct vec16;

@@ -74,7 +74,9 @@ T8_DEV void load_prim(const T* pe, int LE, int i, Prim<T>& q) {
 // meshes: 35 KB; 3D tiles are 37 KB and lose 7 % with it even though the fourth workgroup then fits -- their wavefronts mix
 // face directions and run both arms of the axis path under the tighter budget). The DENSE kernel reads the logarithm
 // table from global memory instead of an LDS copy (c2: +1 %).
-template <class T, int KIND, int STAGE, bool DICT, int MAXP, bool SCATTER = false, bool DENSE = false>
+// OPEN: the plan has outflow / inflow faces (T8gpuPlainPlan::has_open_faces): their codes are decoded (decode_face_side);
+// OPEN = false is the wall-only body, unchanged.
+template <class T, int KIND, int STAGE, bool DICT, int MAXP, bool SCATTER = false, bool DENSE = false, bool OPEN = false>
 T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& prev, const FVars<T>& src, const FVars<T>& out,
                             const T* __restrict__ vol, T dt, T* __restrict__ speed) {
   extern __shared__ __attribute__((aligned(16))) double lds_raw[];
@@ -184,8 +186,19 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
     const bool    last = it == MAXP - 1 || nf <= 256 * (it + 1);
     if (fi.valid) {
       const int  l = fi.lr & 0xFFFFu, r16 = fi.lr >> 16;
-      const bool wall = r16 == 0xFFFFu;
-      const int  r = wall ? l : r16;
+      bool       wall, other;   // other: the right side is an element of the tile window
+      int        r, inflow = -1;
+      if constexpr (OPEN) {
+        const FaceSide fs = decode_face_side(l, r16);
+        wall   = fs.wall;
+        other  = !fs.wall && !fs.open;
+        r      = fs.r;
+        inflow = fs.inflow;
+      } else {
+        wall  = r16 == 0xFFFFu;
+        other = !wall;
+        r     = wall ? l : r16;
+      }
       T          g[5], spd = T(0);
       // The tile's faces are ordered by direction inside each block of 256 (tile_plan.cpp), so a wavefront's active lanes
       // usually share one axis-aligned normal s * e_axis: selecting components then gives the same values as the general
@@ -197,7 +210,10 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
         const T area = reinterpret_cast<const T*>(reinterpret_cast<const V4*>(P.geo_table) + fi.gi)[3];
         Prim<T> L, R;
         load_prim<T>(pe, LE, l, L);
-        load_prim<T>(pe, LE, r, R);
+        if (OPEN && inflow >= 0)
+          inflow_prim<T>(P, inflow, R);
+        else
+          load_prim<T>(pe, LE, r, R);
         T uL, vL, wL, uR, vR, wR;
         if ((wcode >> 1) == 0) {
           asm volatile("");
@@ -246,7 +262,10 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
       if (KIND == 0) {
         Prim<T> L, R;
         load_prim<T>(pe, LE, l, L);
-        load_prim<T>(pe, LE, r, R);
+        if (OPEN && inflow >= 0)
+          inflow_prim<T>(P, inflow, R);
+        else
+          load_prim<T>(pe, LE, r, R);
 #ifdef T8GPU_EXP_NOMATH
         g[0] = L.rho + R.rho + n[0] + t1[0]; g[1] = L.vx + R.vx + t2[0]; g[2] = L.vy + R.vy + L.beta + R.beta; g[3] = L.vz + R.vz + L.lrho + R.lrho;
         g[4] = L.p + R.p + L.lbeta + R.lbeta + L.v0 + R.v0 + gm.w;
@@ -261,6 +280,11 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
           sl[k] = pe[k * LE + l];
           sr[k] = pe[k * LE + r];
         }
+        if (OPEN && inflow >= 0) {
+          const T* q = inflow_entry<T>(P, inflow);
+#pragma unroll
+          for (int k = 0; k < 5; k++) sr[k] = q[k];
+        }
         hll_face<T>(sl, sr, wall, n, t1, t2, gm.w, g, spd, KIND == 2);
       }
       }
@@ -270,7 +294,7 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
 #pragma unroll
           for (int k = 0; k < 5; k++) atomicAdd(&ff[k * 256 + l], -g[k]);
         }
-        if (!wall && r < ne) {
+        if (other && r < ne) {
 #pragma unroll
           for (int k = 0; k < 5; k++) atomicAdd(&ff[k * 256 + r], g[k]);
         }
@@ -322,7 +346,7 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
 }
 
 // one tile per workgroup: workgroup b takes position tile_begin + xcd_position(b) of tile_order
-template <class T, int KIND, int STAGE, bool DICT, int MAXP, bool SCATTER = false, bool DENSE = false>
+template <class T, int KIND, int STAGE, bool DICT, int MAXP, bool SCATTER = false, bool DENSE = false, bool OPEN = false>
 __global__ __launch_bounds__(256, DENSE ? (sizeof(T) == 8 ? 4 : 5) : 1) void k_plain_fused_p(T8gpuPlainPlan P, int tile_begin, FVars<T> prev, FVars<T> src,
                                                        FVars<T> out, const T* __restrict__ vol, T dt,
                                                        T* __restrict__ speed) {
@@ -332,7 +356,7 @@ __global__ __launch_bounds__(256, DENSE ? (sizeof(T) == 8 ? 4 : 5) : 1) void k_p
 #else
   const int pos = tile_begin + xcd_position(blockIdx.x, gridDim.x);
 #endif
-  plain_tile_body<T, KIND, STAGE, DICT, MAXP, SCATTER, DENSE>(P, pos, prev, src, out, vol, dt, speed);
+  plain_tile_body<T, KIND, STAGE, DICT, MAXP, SCATTER, DENSE, OPEN>(P, pos, prev, src, out, vol, dt, speed);
 }
 
 }  // namespace t8gpu_hip

@@ -91,6 +91,41 @@ __global__ __launch_bounds__(256) void k_flux_boundary(int F, int B, int ndim, c
   for (int k = 0; k < 5; k++) gadd(&fl.p[k][e], -g[k]);
 }
 
+// ---- boundary faces with their kinds (open boundaries; not in the reference) ----------------------
+// The wall flux above with a different outside state: outflow = the inside state unmirrored, inflow k = the conservative
+// state of inflow table entry k (t8gpu_hip.h: T8GPU_INFLOW_WORDS).
+template <class T, int KIND>
+__global__ __launch_bounds__(256) void k_flux_boundary_bc(int F, int B, int ndim, const int32_t* __restrict__ fn,
+                                                          const uint8_t* __restrict__ kinds, const T* __restrict__ inflow,
+                                                          const T* __restrict__ normals, const T* __restrict__ areas,
+                                                          Vars<T> st, Vars<T> fl, T* __restrict__ speed) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  const T   area = areas[F + i];
+  const int e    = fn[2 * (size_t)F + i];
+  const int kind = kinds[i];
+  T         n[3] = {T(0), T(0), T(0)};
+  for (int k = 0; k < ndim; k++) n[k] = normals[(size_t)ndim * (F + i) + k];
+  T s[5], o[5];
+  load5(st, e, s);
+  if (kind >= 2) {
+#pragma unroll
+    for (int k = 0; k < 5; k++) o[k] = inflow[T8GPU_INFLOW_WORDS * (kind - 2) + k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 5; k++) o[k] = s[k];
+  }
+  T t1[3], t2[3], Ff[5], g[5], spd;
+  face_basis<T>(n, t1, t2);
+  face_frame_flux_ref<T, KIND>(n, t1, t2, s, o, kind == 0, Ff, spd);
+  if (speed) speed[F + i] = spd;
+#pragma unroll
+  for (int k = 0; k < 5; k++) Ff[k] = area * Ff[k];
+  from_face_frame<T>(n, t1, t2, Ff, g);
+#pragma unroll
+  for (int k = 0; k < 5; k++) gadd(&fl.p[k][e], -g[k]);
+}
+
 // ---- a6: SSP-RK3 stages, ssp_runge_kutta.inl:30-99 (S = 1) and :101-221 (S = Subgrid::size) -------
 // One lane per cell; `volume[i / S] / S` for subgrids. Grid-stride, coalesced, fluxes zeroed.
 template <class T, int STAGE, int S>
@@ -292,6 +327,23 @@ int flux_boundary(int kind, int F, int B, int ndim, const int32_t* fn, const T* 
   return launch_status();
 }
 
+template <class T, class V>
+int flux_boundary_bc(int kind, int F, int B, int ndim, const int32_t* fn, const uint8_t* kinds, const T* inflow, const T* normals,
+                     const T* areas, V st, V fl, T* speed, void* stream) {
+  if (!kinds) return flux_boundary<T, V>(kind, F, B, ndim, fn, normals, areas, st, fl, speed, stream);
+  if (B <= 0) return 0;
+  if (ndim < 2 || ndim > 3 || (kind < 0 || kind > 2)) return static_cast<int>(hipErrorInvalidValue);
+  const dim3  grid((B + 255) / 256), block(256);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (kind == 0)
+    hipLaunchKernelGGL((k_flux_boundary_bc<T, 0>), grid, block, 0, s, F, B, ndim, fn, kinds, inflow, normals, areas, mk<T>(st), mk<T>(fl), speed);
+  else if (kind == 1)
+    hipLaunchKernelGGL((k_flux_boundary_bc<T, 1>), grid, block, 0, s, F, B, ndim, fn, kinds, inflow, normals, areas, mk<T>(st), mk<T>(fl), speed);
+  else
+    hipLaunchKernelGGL((k_flux_boundary_bc<T, 2>), grid, block, 0, s, F, B, ndim, fn, kinds, inflow, normals, areas, mk<T>(st), mk<T>(fl), speed);
+  return launch_status();
+}
+
 template <class T, int S, class V>
 int rk_stage(int stage, size_t ncells, V prev, V mid, V out, V fl, const T* volume, T dt, void* stream) {
   if (ncells == 0) return 0;
@@ -363,7 +415,7 @@ using namespace t8gpu_hip;
 extern "C" {
 
 const char* t8gpu_hip_last_stage_kernel(void) { return stage_kernel_note().name; }
-int t8gpu_hip_abi_version(void) { return 8; }   // 2: T8gpuPlainPlan.tile_desc; 3: T8gpuSubgridPlan row format (far-cell recipes), n_blocks_addressed, family records; 4: T8gpuPlainPlan.n_patch_tiles; 5: T8gpuPlainPlan.ell holds rows for generic tiles only (tile_desc word 6), patch_dim; 6: T8gpuPlainPlan.n_irregular_tiles; 7: T8gpuPlainPlan ghost window (ghost_buf, send_map, send_list, send_buf, n_owned); 8: t8gpu_hip_plain_geo_frames_* (plan builders must call it)
+int t8gpu_hip_abi_version(void) { return 9; }   // 2: T8gpuPlainPlan.tile_desc; 3: T8gpuSubgridPlan row format (far-cell recipes), n_blocks_addressed, family records; 4: T8gpuPlainPlan.n_patch_tiles; 5: T8gpuPlainPlan.ell holds rows for generic tiles only (tile_desc word 6), patch_dim; 6: T8gpuPlainPlan.n_irregular_tiles; 7: T8gpuPlainPlan ghost window (ghost_buf, send_map, send_list, send_buf, n_owned); 8: t8gpu_hip_plain_geo_frames_* (plan builders must call it); 9: T8gpuPlainPlan open boundaries (inflow, has_open_faces), t8gpu_hip_flux_boundary_bc_*, t8gpu_hip_plain_inflow_table_*
 int t8gpu_hip_device_count(int* count) { return static_cast<int>(hipGetDeviceCount(count)); }
 int t8gpu_hip_set_device(int device) { return static_cast<int>(hipSetDevice(device)); }
 const char* t8gpu_hip_error_string(int code) {
@@ -379,6 +431,11 @@ const char* t8gpu_hip_error_string(int code) {
   int t8gpu_hip_flux_boundary_##SUF(int kind, int F, int B, int ndim, const int32_t* fn, const T* normals,           \
                                     const T* areas, V st, V fl, T* speed, void* stream) {                            \
     return flux_boundary<T, V>(kind, F, B, ndim, fn, normals, areas, st, fl, speed, stream);                         \
+  }                                                                                                                  \
+  int t8gpu_hip_flux_boundary_bc_##SUF(int kind, int F, int B, int ndim, const int32_t* fn, const uint8_t* kinds,       \
+                                       const T* inflow, const T* normals, const T* areas, V st, V fl, T* speed,        \
+                                       void* stream) {                                                                 \
+    return flux_boundary_bc<T, V>(kind, F, B, ndim, fn, kinds, inflow, normals, areas, st, fl, speed, stream);         \
   }                                                                                                                  \
   int t8gpu_hip_rk3_stage_##SUF(int stage, int N, V prev, V mid, V out, V fl, const T* volume, T dt, void* stream) { \
     return rk_stage<T, 1, V>(stage, N < 0 ? 0 : (size_t)N, prev, mid, out, fl, volume, dt, stream);                  \

@@ -19,7 +19,8 @@
 
 namespace t8gpu_hip {
 
-template <class T, int KIND, int STAGE>
+// OPEN: the plan has outflow / inflow faces (fused_common.hpp: decode_face_side); OPEN = false is the wall-only kernel
+template <class T, int KIND, int STAGE, bool OPEN = false>
 __global__ __launch_bounds__(256) void k_plain_fused(T8gpuPlainPlan P, int tile_begin, FVars<T> prev, FVars<T> src,
                                                      FVars<T> out, const T* __restrict__ vol, T dt,
                                                      T* __restrict__ speed) {
@@ -79,8 +80,17 @@ __global__ __launch_bounds__(256) void k_plain_fused(T8gpuPlainPlan P, int tile_
     const uint32_t lr = P.face_lr[f0 + f];
     const V4       gm = geo[f];
     const int      l = lr & 0xFFFFu, r16 = lr >> 16;
-    const bool     wall = r16 == 0xFFFFu;
-    const int      r = wall ? l : r16;
+    bool           wall;
+    int            r, inflow = -1;
+    if constexpr (OPEN) {
+      const FaceSide fs = decode_face_side(l, r16);
+      wall   = fs.wall;
+      r      = fs.r;
+      inflow = fs.inflow;
+    } else {
+      wall = r16 == 0xFFFFu;
+      r    = wall ? l : r16;
+    }
     const T        n[3] = {gm.x, gm.y, gm.z};
     T              t1[3], t2[3], g[5], spd = T(0);
     face_basis_fast<T>(n, t1, t2);
@@ -90,6 +100,7 @@ __global__ __launch_bounds__(256) void k_plain_fused(T8gpuPlainPlan P, int tile_
       L.beta = pe[5 * LE + l]; L.lrho = pe[6 * LE + l]; L.lbeta = pe[7 * LE + l]; L.v0 = pe[8 * LE + l];
       R.rho = pe[0 * LE + r]; R.vx = pe[1 * LE + r]; R.vy = pe[2 * LE + r]; R.vz = pe[3 * LE + r]; R.p = pe[4 * LE + r];
       R.beta = pe[5 * LE + r]; R.lrho = pe[6 * LE + r]; R.lbeta = pe[7 * LE + r]; R.v0 = pe[8 * LE + r];
+      if (OPEN && inflow >= 0) inflow_prim<T>(P, inflow, R);
       kepes_prim<T>(L, R, wall, n, t1, t2, gm.w, g, spd);
     } else {
       T sl[5], sr[5];
@@ -97,6 +108,11 @@ __global__ __launch_bounds__(256) void k_plain_fused(T8gpuPlainPlan P, int tile_
       for (int k = 0; k < 5; k++) {
         sl[k] = pe[k * LE + l];
         sr[k] = pe[k * LE + r];
+      }
+      if (OPEN && inflow >= 0) {
+        const T* q = inflow_entry<T>(P, inflow);
+#pragma unroll
+        for (int k = 0; k < 5; k++) sr[k] = q[k];
       }
       hll_face<T>(sl, sr, wall, n, t1, t2, gm.w, g, spd, KIND == 2);
     }
@@ -168,7 +184,10 @@ int plain_generic_stage(int kind, int stage, const T8gpuPlainPlan* plan, int til
   // (the generic kernel walks the CSR lists; callers that know their plan stays inside the pipelined kernels' limits need not
   //  upload them -- t8gpu_amd/fused.py does not)
   if (!pipelined && (!plan->csr_off || !plan->csr_ent)) return static_cast<int>(hipErrorInvalidValue);
-  static const bool scatter = std::getenv("T8GPU_LDS_SCATTER") && std::getenv("T8GPU_LDS_SCATTER")[0] == '1';   // measured alternative
+  static const bool scatter_env = std::getenv("T8GPU_LDS_SCATTER") && std::getenv("T8GPU_LDS_SCATTER")[0] == '1';   // measured alternative
+  const bool        open = plan->has_open_faces != 0;   // outflow / inflow faces: the OPEN instantiations
+  const bool        scatter = scatter_env && !open;     // (the scatter form is kept for walls only)
+  if (open && !plan->inflow) return static_cast<int>(hipErrorInvalidValue);
   // The persistent, software-pipelined kernel (kernels_fused_persistent.hip) for launches that cover the whole plan.
   // A multi-rank stage is split into tile classes on three streams beside the pack / RCCL / unpack kernels
   // (stepper.hip): persistent workgroups would hold every register file and LDS slot of the chip until their class is
@@ -203,9 +222,26 @@ int plain_generic_stage(int kind, int stage, const T8gpuPlainPlan* plan, int til
     hipLaunchKernelGGL(KERNEL, grid, block, lds, s, *plan, tile_begin, fmk<T>(prev), fmk<T>(mid),            \
                        fmk<T>(out), volume, dt, speed);                                                      \
   } while (0)
+#define T8_FUSED_OPEN(K, S)                                         \
+  do {                                                              \
+    if (dict && !four && dense)                                     \
+      T8_LAUNCH((k_plain_fused_p<T, K, S, true, 2, false, true, true>), "k_plain_fused_p<T, K, S, true, 2, false, true, true>");    \
+    else if (dict && !four)                                         \
+      T8_LAUNCH((k_plain_fused_p<T, K, S, true, 2, false, false, true>), "k_plain_fused_p<T, K, S, true, 2, false, false, true>"); \
+    else if (dict)                                                  \
+      T8_LAUNCH((k_plain_fused_p<T, K, S, true, 4, false, false, true>), "k_plain_fused_p<T, K, S, true, 4, false, false, true>"); \
+    else if (pipelined && !four)                                    \
+      T8_LAUNCH((k_plain_fused_p<T, K, S, false, 2, false, false, true>), "k_plain_fused_p<T, K, S, false, 2, false, false, true>"); \
+    else if (pipelined)                                             \
+      T8_LAUNCH((k_plain_fused_p<T, K, S, false, 4, false, false, true>), "k_plain_fused_p<T, K, S, false, 4, false, false, true>"); \
+    else                                                            \
+      T8_LAUNCH((k_plain_fused<T, K, S, true>), "k_plain_fused<T, K, S, true>");                                      \
+  } while (0)
 #define T8_FUSED(K, S)                                              \
   do {                                                              \
-    if (scatter && dict && !four)                                   \
+    if (open)                                                       \
+      T8_FUSED_OPEN(K, S);                                          \
+    else if (scatter && dict && !four)                              \
       T8_LAUNCH((k_plain_fused_p<T, K, S, true, 2, true>), "k_plain_fused_p<T, K, S, true, 2, true, false>");         \
     else if (scatter && pipelined && !four)                         \
       T8_LAUNCH((k_plain_fused_p<T, K, S, false, 2, true>), "k_plain_fused_p<T, K, S, false, 2, true, false>");        \
@@ -230,6 +266,7 @@ int plain_generic_stage(int kind, int stage, const T8gpuPlainPlan* plan, int til
     if (stage == 1) T8_FUSED(2, 1); else if (stage == 2) T8_FUSED(2, 2); else T8_FUSED(2, 3);
   }
 #undef T8_FUSED
+#undef T8_FUSED_OPEN
 #undef T8_LAUNCH
   return static_cast<int>(hipGetLastError());
 }
@@ -250,6 +287,7 @@ int plain_fused_stage(int kind, int stage, const T8gpuPlainPlan* plan, int tile_
       if (prev.p[k] != mid.p[k]) return static_cast<int>(hipErrorInvalidValue);
   if (tile_count == 0) return 0;
   if ((plan->ghost_buf || plan->send_map) && (plan->n_owned <= 0 || (plan->send_map && !plan->send_buf))) return static_cast<int>(hipErrorInvalidValue);
+  if (plan->has_open_faces && !plan->inflow) return static_cast<int>(hipErrorInvalidValue);
   stage_kernel_note_reset();
   // The interior launch of a multi-rank stage -- exactly [0, n_interior) -- is a persistent grid like a whole-plan launch. In
   // the three-stream pipeline of rounds 1-3 resident workgroups that never leave kept the exchange kernels from starting
@@ -363,7 +401,34 @@ int geo_frames(void* table, int n_geo, void* stream) {
 }
 }  // namespace t8gpu_hip
 
+namespace t8gpu_hip {
+// inflow table entries (t8gpu_hip.h: T8GPU_INFLOW_WORDS): the state and its KEPES record by the routine the tile kernels run
+// for their cells (fp64: table-driven logarithms, the table read from global memory -- the same values as the LDS copy)
+template <class T>
+__global__ __launch_bounds__(64) void k_inflow_table(const T* __restrict__ states, int n, T* __restrict__ table) {
+  const int i = threadIdx.x;
+  if (i >= n) return;
+  T s[5];
+  for (int k = 0; k < 5; k++) s[k] = states[5 * i + k];
+  const Prim<T> q = prim_from_state<T, sizeof(T) == 8>(s, kLogTab);
+  T* const      w = table + T8GPU_INFLOW_WORDS * i;
+  for (int k = 0; k < 5; k++) w[k] = s[k];
+  w[5] = q.rho; w[6] = q.vx; w[7] = q.vy; w[8] = q.vz; w[9] = q.p; w[10] = q.beta; w[11] = q.lrho; w[12] = q.lbeta; w[13] = q.v0;
+  w[14] = T(0);
+  w[15] = T(0);
+}
+template <class T>
+int inflow_table(const T* states, int n, T* table, void* stream) {
+  if (n < 0 || n > 8 || (n > 0 && (!states || !table))) return static_cast<int>(hipErrorInvalidValue);
+  if (n == 0) return 0;
+  hipLaunchKernelGGL((k_inflow_table<T>), dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), states, n, table);
+  return static_cast<int>(hipGetLastError());
+}
+}  // namespace t8gpu_hip
+
 extern "C" {
+int t8gpu_hip_plain_inflow_table_f32(const float* states, int n, float* table, void* stream) { return t8gpu_hip::inflow_table<float>(states, n, table, stream); }
+int t8gpu_hip_plain_inflow_table_f64(const double* states, int n, double* table, void* stream) { return t8gpu_hip::inflow_table<double>(states, n, table, stream); }
 int t8gpu_hip_plain_geo_frames_f32(void* geo_table, int n_geo, void* stream) { return t8gpu_hip::geo_frames<float>(geo_table, n_geo, stream); }
 int t8gpu_hip_plain_geo_frames_f64(void* geo_table, int n_geo, void* stream) { return t8gpu_hip::geo_frames<double>(geo_table, n_geo, stream); }
 int t8gpu_hip_plain_needs_csr(const T8gpuPlainPlan* plan) { return plan && t8gpu_hip::plain_tiles_pipelined(plan) ? 0 : 1; }

@@ -265,7 +265,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_patch(T8g
 // workgroups walk the patch tiles, every further workgroup takes one generic tile (fused_tile_body.hpp). As two launches
 // the generic tiles of the benchmark mesh -- 3 % of its elements -- cost 9 % of the stage: a launch of their own, started
 // when the patch launch has drained. Here they start as the persistent patch workgroups finish and fill the ragged end.
-template <class T, int KIND, int STAGE, bool NT>
+// OPEN: the plan has outflow / inflow faces -- only its generic tiles can see them (a cell with an open face is in no patch)
+template <class T, int KIND, int STAGE, bool NT, bool OPEN = false>
 __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_stage(T8gpuPlainPlan P, int patch_begin, int patch_count, int patch_wgs, int chunk,
                                                                                 int tile_begin, int tile_count, FVars<T> prev, FVars<T> src,
                                                                                 FVars<T> out, const T* __restrict__ vol, T dt,
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_stage(T8g
 #else
     const int pos = tile_begin + xcd_position(b - patch_wgs, tile_count);
 #endif
-    plain_tile_body<T, KIND, STAGE, true, 2>(P, pos, prev, src, out, vol, dt, speed);
+    plain_tile_body<T, KIND, STAGE, true, 2, false, false, OPEN>(P, pos, prev, src, out, vol, dt, speed);
   }
 }
 
@@ -350,11 +351,15 @@ int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch
   // non-temporal stage results / previous-state loads where the stage's planes are a stream for the caches (flux_math.hpp)
   const bool nt = stream_hint(plan->n_slots_addressed, sizeof(T));
   note_stage_kernel(patch_count + (tile_count > 0 ? tile_count : 0),
-                    tile_count > 0 ? (nt ? "k_plain_stage<T, K, S, true>" : "k_plain_stage<T, K, S, false>") : (nt ? "k_plain_patch<T, K, S, true>" : "k_plain_patch<T, K, S, false>"),
+                    tile_count > 0 ? (plan->has_open_faces ? (nt ? "k_plain_stage<T, K, S, true, true>" : "k_plain_stage<T, K, S, false, true>")
+                                                           : (nt ? "k_plain_stage<T, K, S, true>" : "k_plain_stage<T, K, S, false>")) : (nt ? "k_plain_patch<T, K, S, true>" : "k_plain_patch<T, K, S, false>"),
                     static_cast<int>(sizeof(T)), kind, stage);
 #define T8_PAN(K, S, N)                                                                                                           \
   do {                                                                                                                            \
-    if (tile_count > 0)                                                                                                           \
+    if (tile_count > 0 && plan->has_open_faces)                                                                                   \
+      hipLaunchKernelGGL((k_plain_stage<T, K, S, N, true>), grid, block, lds, stream, *plan, patch_begin, patch_count, patch_wgs, chunk, tile_begin, \
+                         tile_count, prev, mid, out, volume, dt, speed);                                                          \
+    else if (tile_count > 0)                                                                                                      \
       hipLaunchKernelGGL((k_plain_stage<T, K, S, N>), grid, block, lds, stream, *plan, patch_begin, patch_count, patch_wgs, chunk, tile_begin, \
                          tile_count, prev, mid, out, volume, dt, speed);                                                          \
     else                                                                                                                          \

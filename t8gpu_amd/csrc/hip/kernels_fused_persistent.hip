@@ -348,7 +348,8 @@ bool plain_persistent_accepts(int kind, const T8gpuPlainPlan* plan, int tile_cou
   // what this kernel takes: the compressed plan with a geometry dictionary small enough for LDS, ELL rows of 8, 16 or 24
   // entries (the second chunk travels with the previous state, a third is fetched where an element has more than 15
   // faces), tiles of <= 256 elements, <= 512 own + halo slots and <= 512 faces
-  if (off || !plan->tile_desc || !plan->ell || (plan->ell_width != 8 && plan->ell_width != 16 && plan->ell_width != 24) || !plan->geo_idx || !plan->geo_table || plan->n_geo <= 0 || plan->n_geo > 128 ||
+  // (open boundaries: the one-tile kernels decode them, this kernel knows walls only -- its plans' launches run those, same bits)
+  if (off || plan->has_open_faces || !plan->tile_desc || !plan->ell || (plan->ell_width != 8 && plan->ell_width != 16 && plan->ell_width != 24) || !plan->geo_idx || !plan->geo_table || plan->n_geo <= 0 || plan->n_geo > 128 ||
       plan->max_elems > 256 || slots <= 0 || slots > 512 || plan->max_faces > 512)
     return false;
   const int    nw  = kind == 0 ? kPrimWords : 5;

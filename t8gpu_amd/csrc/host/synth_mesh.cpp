@@ -35,6 +35,9 @@ struct Leaf {
 
 struct Mesh {
   int    dim = 2, base = 1, lmax = 1, periodic = 1;
+  // per side (-x, +x, -y, +y, -z, +z): -1 periodic, 0 wall, 1 outflow, 2 + k inflow state k. A periodic side is always
+  // paired with the opposite side of its axis (t8gpu_synth_mesh_create_sides checks it); `periodic` = every side periodic.
+  int    side[6] = {-1, -1, -1, -1, -1, -1};
   double band = 0, shrink = 1;
   std::vector<Leaf>    leaves;
   std::vector<int32_t> owner;  // finest-level grid -> leaf index
@@ -108,14 +111,14 @@ struct Mesh {
     uint32_t       p[3] = {l.c[0] * s, l.c[1] * s, dim == 3 ? l.c[2] * s : 0};
     if (f & 1) {
       if (p[d] + s >= ext) {
-        if (!periodic) return -1;
+        if (side[f] >= 0) return -1;
         p[d] = 0;
       } else {
         p[d] += s;
       }
     } else {
       if (p[d] == 0) {
-        if (!periodic) return -1;
+        if (side[f] >= 0) return -1;
         p[d] = ext - 1;
       } else {
         p[d] -= 1;
@@ -166,6 +169,7 @@ struct Part {
   uvector<int32_t> fn;       // 2F + B      (uvector: sized, then written completely by parallel loops)
   uvector<double>  normals;  // ndim * (F + B)
   uvector<double>  areas;    // F + B
+  std::vector<uint8_t> kinds;  // B: boundary kind of every boundary face (0 wall, 1 outflow, 2 + k inflow k)
   std::vector<int32_t> level_diff, nb_offset;
   std::vector<int64_t> ghost_global;
   std::vector<int32_t> ghost_owner;
@@ -297,10 +301,12 @@ void build_part(Part& P) {
       }
     }
   }
+  P.kinds.resize(static_cast<size_t>(P.B));
 #pragma omp parallel for num_threads(host_threads()) schedule(static)
   for (int32_t i = 0; i < P.B; i++) {
     P.fn[2 * static_cast<size_t>(P.F) + i] = local(walls[i].l);
     geom(static_cast<size_t>(P.F) + i, walls[i].l, walls[i].f);
+    P.kinds[i] = static_cast<uint8_t>(M.side[walls[i].f]);   // (a boundary face lies on a non-periodic side: code >= 0)
   }
 
   timer.lap("face arrays");
@@ -359,16 +365,40 @@ void kh_state(int dim, const double x[3], double out[5]) {
 extern "C" {
 
 void* t8gpu_synth_mesh_create(int dim, int base_level, int max_level, double band, double shrink, int periodic) {
+  const int sides[6] = {periodic ? -1 : 0, periodic ? -1 : 0, periodic ? -1 : 0, periodic ? -1 : 0, periodic ? -1 : 0, periodic ? -1 : 0};
+  return t8gpu_synth_mesh_create_sides(dim, base_level, max_level, band, shrink, sides);
+}
+
+int t8gpu_synth_check_sides(int dim, const int* sides) {
+  if (dim < 2 || dim > 3 || !sides) return 1;
+  for (int f = 0; f < 2 * dim; f++) {
+    if (sides[f] < -1 || sides[f] >= 2 + T8GPU_MAX_INFLOW_STATES) return 1;
+    if ((sides[f] == -1) != (sides[f ^ 1] == -1)) return 2;   // a periodic side without its opposite side
+  }
+  return 0;
+}
+
+void* t8gpu_synth_mesh_create_sides(int dim, int base_level, int max_level, double band, double shrink, const int* sides) {
   if (dim < 2 || dim > 3 || base_level < 1 || max_level < base_level || dim * max_level > 28) return nullptr;
+  if (t8gpu_synth_check_sides(dim, sides) != 0) return nullptr;
   Mesh* m     = new Mesh;
   m->dim      = dim;
   m->base     = base_level;
   m->lmax     = max_level;
   m->band     = band;
   m->shrink   = shrink;
-  m->periodic = periodic;
+  m->periodic = 1;
+  for (int f = 0; f < 2 * dim; f++) {
+    m->side[f] = sides[f];
+    m->periodic = m->periodic && sides[f] == -1;
+  }
   m->build();
   return m;
+}
+int t8gpu_synth_mesh_sides(const void* h, int* sides) {
+  const Mesh* m = static_cast<const Mesh*>(h);
+  for (int f = 0; f < 6; f++) sides[f] = f < 2 * m->dim ? m->side[f] : -1;
+  return 2 * m->dim;
 }
 void    t8gpu_synth_mesh_destroy(void* h) { delete static_cast<Mesh*>(h); }
 int t8gpu_synth_mesh_dim(const void* h) { return static_cast<const Mesh*>(h)->dim; }
@@ -399,6 +429,7 @@ void t8gpu_synth_part_release_arrays(void* h) {
   uvector<int32_t>().swap(p->fn);
   uvector<double>().swap(p->normals);
   uvector<double>().swap(p->areas);
+  std::vector<uint8_t>().swap(p->kinds);
   std::vector<int32_t>().swap(p->level_diff);
   std::vector<int32_t>().swap(p->nb_offset);
 }
@@ -438,6 +469,12 @@ void t8gpu_synth_part_connectivity_ptrs(const void* h, const void** ptrs) {
   ptrs[2] = p->areas.empty() ? nullptr : p->areas.data();
   ptrs[3] = p->level_diff.empty() ? nullptr : p->level_diff.data();
   ptrs[4] = p->nb_offset.empty() ? nullptr : p->nb_offset.data();
+}
+
+// boundary_kinds[B] of the partition in place (null when B = 0), valid as the arrays above
+const uint8_t* t8gpu_synth_part_boundary_kinds(const void* h) {
+  const Part* p = static_cast<const Part*>(h);
+  return p->kinds.empty() ? nullptr : p->kinds.data();
 }
 
 // per owned+ghost element: level, volume, centre (N + G entries; centre is [N+G][3])
@@ -575,6 +612,7 @@ static void* adapt_by_rounds(const void* mesh, const int8_t* marks) {
   const int   nsub = 1 << O.dim;
   Mesh*       M    = new Mesh;
   M->dim = O.dim; M->base = O.base; M->band = O.band; M->shrink = O.shrink; M->periodic = O.periodic;
+  std::copy(O.side, O.side + 6, M->side);
   // the finest-level lookup grid is sized for lmax: refining a finest leaf needs one more level
   int newmax = O.lmax;
   for (size_t e = 0; e < O.leaves.size(); e++)
@@ -724,6 +762,7 @@ void* t8gpu_synth_mesh_adapt(const void* mesh, const int8_t* marks) {
   for (int64_t e = 0; e < n; e++) at[e + 1] += at[e];
   Mesh* M = new Mesh;
   M->dim = O.dim; M->base = O.base; M->band = O.band; M->shrink = O.shrink; M->periodic = O.periodic;
+  std::copy(O.side, O.side + 6, M->side);
   M->lmax = newmax;
   M->leaves.resize(static_cast<size_t>(at[n]));
   M->adapted_from = mesh;   // (t8gpu_synth_mesh_adapt_data copies the correspondence instead of walking the two forests)

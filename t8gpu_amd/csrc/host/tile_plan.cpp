@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "host_threads.hpp"
+#include "t8gpu_host.h"
 
 namespace {
 
@@ -76,7 +77,7 @@ struct TilePlan {
   std::vector<int32_t>  elem_off, halo_off, face_off;  // [ntiles + 1]
   // (uvector: sized once, then written completely by the parallel per-tile loops -- no value-initialising pass)
   uvector<int32_t>      halo_ids;                      // slots
-  uvector<uint32_t>     face_lr;                       // l | r << 16 (tile-local; r = 0xFFFF: wall mirror)
+  uvector<uint32_t>     face_lr;                       // l | r << 16 (tile-local; r >= 0xFFF0: boundary face, boundary_code)
   uvector<double>       face_geo;                      // [nfaces][4] = nx, ny, nz, area
   uvector<int32_t>      face_orig;                     // original face id if this tile reports its speed, else -1
   std::vector<int32_t>  csr_off;                       // [N + 1]
@@ -94,6 +95,8 @@ struct TilePlan {
   int32_t want_patches = 0;
   bool    skip_face_geo = false;                       // leave face_geo empty when the plan has a geometry dictionary
   bool    two_classes = false;                         // no deep / near-boundary split of the interior tiles (flag 32)
+  const uint8_t* kinds = nullptr;                      // boundary_kinds[B] (null: all walls), read during build() only
+  bool    open_faces = false;                          // some boundary face is not a wall
   std::vector<Patch>   patches;                        // in element order
   std::vector<int32_t> tile_patch;                     // [ntiles] index into patches, or -1 (generic tile)
   int32_t n_patch_class[3] = {0, 0, 0};                // leading patch tiles of the deep / near / ghost-reading class
@@ -111,6 +114,31 @@ inline int direction_code(const double* n, int ndim) {
     axis = k;
   }
   return axis < 0 ? 6 : 2 * axis + (n[axis] > 0.0 ? 1 : 0);
+}
+
+// face_lr code of boundary face b (the r half): 0xFFFF wall, 0xFFFE outflow, 0xFFF0 + k inflow state k. The kernels decode it
+// in one place (fused_common.hpp: boundary_side).
+inline uint32_t boundary_code(const TilePlan& P, int32_t b) {
+  const int k = P.kinds ? P.kinds[b] : 0;
+  return k == 0 ? 0xFFFFu : (k == 1 ? 0xFFFEu : 0xFFF0u + static_cast<uint32_t>(k - 2));
+}
+
+// Drops the patches that hold a cell with an open boundary face: the patch kernels know walls only, such cells run through
+// the generic tiles (patches are disjoint aligned blocks, so this leaves exactly the blocks a finder that rejected open faces
+// would have found).
+void drop_open_patches(TilePlan& P, const int32_t* fn) {
+  if (!P.open_faces || P.patches.empty()) return;
+  std::vector<uint8_t> open(static_cast<size_t>(P.N), 0);
+  for (int32_t b = 0; b < P.B; b++)
+    if (P.kinds[b] != 0) open[fn[2 * static_cast<size_t>(P.F) + b]] = 1;
+  std::vector<Patch> kept;
+  kept.reserve(P.patches.size());
+  for (Patch& pt : P.patches) {
+    bool any = false;
+    for (int t = 0; t < kPatchElems && !any; t++) any = open[pt.e0 + t] != 0;
+    if (!any) kept.push_back(std::move(pt));
+  }
+  P.patches.swap(kept);
 }
 
 // The patches of the mesh, found from the reference-format arrays alone. deg / ef: the faces of every owned element in
@@ -461,8 +489,14 @@ void build(TilePlan& P, const int32_t* fn, const double* normals, const double* 
   };
 
   lap("element -> faces");
-  if (P.want_patches & 1) find_patches(P, fn, normals, areas, deg, ef);
-  if ((P.want_patches & 2) && P.patches.empty()) find_patches3(P, fn, normals, areas, deg, ef);
+  if (P.want_patches & 1) {
+    find_patches(P, fn, normals, areas, deg, ef);
+    drop_open_patches(P, fn);
+  }
+  if ((P.want_patches & 2) && P.patches.empty()) {
+    find_patches3(P, fn, normals, areas, deg, ef);
+    drop_open_patches(P, fn);
+  }
   std::vector<int32_t> patch_at(static_cast<size_t>(N) + 1, -1);   // patch that starts at an element
   for (size_t k = 0; k < P.patches.size(); k++) patch_at[P.patches[k].e0] = static_cast<int32_t>(k);
   lap("patches");
@@ -820,7 +854,7 @@ void build(TilePlan& P, const int32_t* fn, const double* normals, const double* 
       for (size_t jj = 0; jj < nft; jj++) {
         const int32_t f = tf[order[jj]];
         const int32_t l = side(f, 0), r = side(f, 1);
-        const uint32_t ll = loc(l), rr = r < 0 ? 0xFFFFu : loc(r);
+        const uint32_t ll = loc(l), rr = r < 0 ? boundary_code(P, f - F) : loc(r);
         P.face_lr[q] = ll | (rr << 16);
         if (fill_geo) {
           for (int k = 0; k < 3; k++) P.face_geo[4 * q + k] = k < P.ndim ? normals[static_cast<size_t>(P.ndim) * f + k] : 0.0;
@@ -911,26 +945,42 @@ void build(TilePlan& P, const int32_t* fn, const double* normals, const double* 
 
 extern "C" {
 
-// fn = [2F + B] reference face_neighbors (local slots), normals = [ndim * (F + B)], areas = [F + B].
+// Returns null if a limit of the packed format is exceeded (tile-local index >= 0xFFF0, > 32767 faces).
 // Returns null if a limit of the packed format is exceeded (tile-local index >= 0xFFFF, > 32767 faces).
 // flags bit 0 / 1: cut structured 2D / 3D patches (find_patches, find_patches3) out of the tiling; bit 2: the caller does not
 // read `face_geo` when the plan has a geometry dictionary (sizes[11] > 0): it is left empty then
-void* t8gpu_plan_plain_create_ex(int32_t N, int32_t G, int32_t F, int32_t B, int32_t ndim, const int32_t* fn,
-                                 const double* normals, const double* areas, int32_t tmax, int32_t fcap, int32_t flags) {
+// boundary_kinds[B] (null: all walls): t8gpu_host.h
+void* t8gpu_plan_plain_create_bc(int32_t N, int32_t G, int32_t F, int32_t B, int32_t ndim, const int32_t* fn,
+                                 const double* normals, const double* areas, const uint8_t* kinds, int32_t tmax, int32_t fcap,
+                                 int32_t flags) {
   if (N < 0 || F < 0 || B < 0 || ndim < 2 || ndim > 3 || tmax < 1 || tmax > 1024 || fcap < 1) return nullptr;
+  bool open_faces = false;
+  for (int32_t b = 0; kinds && b < B; b++) {
+    if (kinds[b] >= 2 + T8GPU_MAX_INFLOW_STATES) return nullptr;
+    open_faces = open_faces || kinds[b] != 0;
+  }
   TilePlan* P = new TilePlan;
+  P->kinds      = open_faces ? kinds : nullptr;
+  P->open_faces = open_faces;
   P->N = N; P->G = G; P->F = F; P->B = B; P->ndim = ndim; P->tmax = tmax; P->fcap = fcap;
   P->want_patches  = flags & 27;   // bit 0: 2D patches (16 x 16), bit 1: 3D patches (8 x 8 x 4), bit 3: irregular 3D patches too, bit 4: no regular 3D ones
   P->skip_face_geo = (flags & 4) != 0;   // bit 2: no face_geo rows if the plan has a geometry dictionary
   P->two_classes   = (flags & 32) != 0;  // bit 5: interior tiles in ONE class (n_deep_tiles = n_interior_tiles): a launch over
                                          // [0, n_interior) is then one kernel launch (the two-lane step driver, stepper.hip)
   build(*P, fn, normals, areas);
-  if (P->max_elems + P->max_halo >= 0xFFFF || P->max_faces > 0x7FFE) {
+  P->kinds = nullptr;   // (the caller's array: not kept)
+  // tile-local indices stay below the boundary codes (0xFFF0 .. 0xFFFF)
+  if (P->max_elems + P->max_halo >= 0xFFF0 || P->max_faces > 0x7FFE) {
     delete P;
     return nullptr;
   }
   return P;
 }
+void* t8gpu_plan_plain_create_ex(int32_t N, int32_t G, int32_t F, int32_t B, int32_t ndim, const int32_t* fn,
+                                 const double* normals, const double* areas, int32_t tmax, int32_t fcap, int32_t flags) {
+  return t8gpu_plan_plain_create_bc(N, G, F, B, ndim, fn, normals, areas, nullptr, tmax, fcap, flags);
+}
+int32_t t8gpu_plan_plain_open_faces(const void* h) { return static_cast<const TilePlan*>(h)->open_faces ? 1 : 0; }
 void* t8gpu_plan_plain_create(int32_t N, int32_t G, int32_t F, int32_t B, int32_t ndim, const int32_t* fn,
                               const double* normals, const double* areas, int32_t tmax, int32_t fcap) {
   return t8gpu_plan_plain_create_ex(N, G, F, B, ndim, fn, normals, areas, tmax, fcap, 0);

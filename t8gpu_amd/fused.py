@@ -17,7 +17,9 @@ class T8gpuPlainPlan(C.Structure):
                 ("n_irregular_tiles", C.c_int32 * 3),
         # ABI 7: the ghost window, attached by the multi-rank step driver only (stepper.hip); NULL / 0 here
         ("ghost_buf", C.c_void_p), ("send_map", C.c_void_p), ("send_list", C.c_void_p), ("send_buf", C.c_void_p),
-        ("n_owned", C.c_int32), ("reserved7", C.c_int32)]
+        ("n_owned", C.c_int32), ("reserved7", C.c_int32),
+        # ABI 9: open boundaries -- the inflow table (device, [K][16]) and "the plan has outflow / inflow faces"
+        ("inflow", C.c_void_p), ("has_open_faces", C.c_int32), ("reserved9", C.c_int32)]
 
 
 class PlainPlan:
@@ -195,7 +197,13 @@ class PlainPlan:
             c.n_irregular_tiles[k] = self.host.n_irregular_class[k]
         c.patch_dim = self.host.patch_dim
         c.n_slots_addressed = part.N + part.G
+        c.has_open_faces = int(self.host.open_faces)
         self.c = c
+
+    def attach_inflow(self, table):
+        """the device inflow table (t8gpu_hip_plain_inflow_table_*) the OPEN kernels read: set once, before any launch"""
+        self._keep["inflow"] = table
+        self.c.inflow = table.data_ptr()
 
     @staticmethod
     def _needs_csr(h):
@@ -221,6 +229,7 @@ class PlainPlan:
             c.geo_idx, c.geo_table = one, one
         c.n_geo, c.ell_width = h.geo_table.shape[0], h.ell_width
         c.ntiles, c.max_elems, c.max_halo, c.max_faces, c.max_slots = h.ntiles, h.max_elems, h.max_halo, h.max_faces, h.max_slots
+        c.has_open_faces = int(getattr(h, "open_faces", False))
         fn = hip.lib().t8gpu_hip_plain_persistent_accepts
         fn.restype = C.c_int
         n_generic = h.ntiles - h.n_patches if n_generic is None else n_generic

@@ -16,6 +16,10 @@ def _lib():
         lib.t8gpu_plan_plain_create.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 3 + [C.c_int32] * 2
         lib.t8gpu_plan_plain_create_ex.restype = C.c_void_p
         lib.t8gpu_plan_plain_create_ex.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 3 + [C.c_int32] * 3
+        lib.t8gpu_plan_plain_create_bc.restype = C.c_void_p
+        lib.t8gpu_plan_plain_create_bc.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 4 + [C.c_int32] * 3
+        lib.t8gpu_plan_plain_open_faces.restype = C.c_int32
+        lib.t8gpu_plan_plain_open_faces.argtypes = [C.c_void_p]
         lib.t8gpu_plan_plain_patch_counts.argtypes = [C.c_void_p] * 2
         lib.t8gpu_plan_plain_irregular_counts.argtypes = [C.c_void_p] * 2
         lib.t8gpu_plan_plain_patch_dim.argtypes = [C.c_void_p]
@@ -39,11 +43,13 @@ class HostPlainPlan:
               "csr_ent", "tile_order")
 
     def __init__(self, N, G, F, B, ndim, face_neighbors, normals, areas, tmax=256, fcap=512, want_face_geo=True,
-                 patches=False, volumes=None, irregular=True, two_classes=False):
+                 patches=False, volumes=None, irregular=True, two_classes=False, boundary_kinds=None):
         """patches=True: structured 16 x 16 patches are cut out of the tiling (tile_plan.cpp: find_patches); they are
         tiles without face records (`tile_patch[t]` = 1), first inside every class of `tile_order` (`n_patch_class`).
         want_face_geo=False: leave `face_geo` (32 bytes per tile face, only read by the kernels that have no geometry
-        dictionary) empty when the plan has a dictionary -- at c4 size that is 700 MB of host copying per plan."""
+        dictionary) empty when the plan has a dictionary -- at c4 size that is 700 MB of host copying per plan.
+        boundary_kinds[B] (0 wall, 1 outflow, 2 + k inflow k; None: all walls): open faces get their codes in face_lr and keep
+        their cells out of patches (t8gpu_host.h: t8gpu_plan_plain_create_bc)."""
         lib = _lib()
         fn = np.ascontiguousarray(face_neighbors, np.int32)
         nr = np.ascontiguousarray(normals, np.float64)
@@ -58,7 +64,12 @@ class HostPlainPlan:
                 pflags |= 16  # ... and the regular blocks take the irregular form as well (one kernel, one launch per stage)
         if two_classes:
             pflags |= 32      # interior tiles in one class (no deep / near-boundary split): one launch per stage for [0, n_interior)
-        h = lib.t8gpu_plan_plain_create_ex(N, G, F, B, ndim, p(fn), p(nr), p(ar), tmax, fcap, pflags)
+        if boundary_kinds is None:
+            h = lib.t8gpu_plan_plain_create_ex(N, G, F, B, ndim, p(fn), p(nr), p(ar), tmax, fcap, pflags)
+        else:
+            kinds = np.ascontiguousarray(boundary_kinds, np.uint8)
+            assert kinds.size == B
+            h = lib.t8gpu_plan_plain_create_bc(N, G, F, B, ndim, p(fn), p(nr), p(ar), p(kinds), tmax, fcap, pflags)
         if not h:
             raise ValueError("tile plan exceeds the packed index format (use smaller tmax / fcap)")
         # The plan's arrays are VIEWS of the planner's own arrays (no copy: a few hundred MB per plan at 3 M elements); a view
@@ -69,6 +80,7 @@ class HostPlainPlan:
         (self.ntiles, n_halo, n_faces, n_csr, self.max_elems, self.max_halo, self.max_faces,
          self.n_interior) = (int(x) for x in sz[:8])
         self.N, self.F, self.B, self.tmax, self.fcap = N, F, B, tmax, fcap
+        self.open_faces = bool(lib.t8gpu_plan_plain_open_faces(h))     # some boundary face is an outflow / inflow face
         self.ell_width, n_geo, self.max_slots, self.n_deep = int(sz[10]), int(sz[11]), int(sz[12]), int(sz[13])
         self.n_ell_rows = int(sz[15])                  # rows exist for the elements of generic tiles only (tile_desc word 6)
         ptrs = (C.c_void_p * 13)()
@@ -113,6 +125,7 @@ class HostPlainPlan:
     @classmethod
     def from_partition(cls, part, **kw):
         kw.setdefault("volumes", getattr(part, "volumes", None))
+        kw.setdefault("boundary_kinds", getattr(part, "boundary_kinds", None))
         return cls(part.N, part.G, part.F, part.B, part.normal_dim, part.face_neighbors, part.normals, part.areas, **kw)
 
 

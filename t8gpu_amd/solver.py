@@ -39,12 +39,45 @@ def _dev(a, dtype=None):
     return hostmem.to_device(a, dtype)          # (tensor.cuda(), or the application's pinned staging buffer: hostmem.py)
 
 
+def boundary_kinds_of(part):
+    """part.boundary_kinds as uint8 (None: the provider sets none -- every boundary face a wall)"""
+    kinds = getattr(part, "boundary_kinds", None)
+    return None if kinds is None else np.asarray(kinds, np.uint8)
+
+
+def check_inflow_states(part, inflow_states):
+    """The (K, 5) conservative inflow states as float64, or None. Required iff part.boundary_kinds holds an inflow code
+    (2 + k); then K <= 8, every code has its state, and every state is a physical one (rho > 0, p > 0, finite). A partition
+    without inflow faces takes them too (a rank of a partitioned mesh, an adapted mesh: the states travel with the run)."""
+    from .synth import INFLOW, MAX_INFLOW_STATES
+    kinds = boundary_kinds_of(part)
+    need = 0 if kinds is None or kinds.size == 0 else max(0, int(kinds.max()) - INFLOW + 1)
+    if inflow_states is None:
+        if need:
+            raise ValueError(f"the partition has inflow faces (states 0..{need - 1}): inflow_states is required")
+        return None
+    s = np.array(inflow_states, np.float64, copy=True)
+    if s.ndim != 2 or s.shape[1] != 5 or not 1 <= s.shape[0] <= MAX_INFLOW_STATES:
+        raise ValueError(f"inflow_states must be a (K, 5) array of conservative states, 1 <= K <= {MAX_INFLOW_STATES}")
+    if s.shape[0] < need:
+        raise ValueError(f"the partition uses inflow state {need - 1}, inflow_states has {s.shape[0]}")
+    if not np.all(np.isfinite(s)):
+        raise ValueError("inflow_states must be finite")
+    p = 0.4 * (s[:, 4] - 0.5 * (s[:, 1] ** 2 + s[:, 2] ** 2 + s[:, 3] ** 2) / np.where(s[:, 0] > 0, s[:, 0], 1.0))
+    if np.any(s[:, 0] <= 0) or np.any(p <= 0):
+        raise ValueError("inflow_states must have positive density and pressure (gamma = 1.4)")
+    return s
+
+
 class PlainSolver:
     """Plain elements. mode = "compat": reference data flow (face kernel + atomics, RK kernel);
-    mode = "fused": tile kernels (flux + RK in one pass, no flux planes in HBM)."""
+    mode = "fused": tile kernels (flux + RK in one pass, no flux planes in HBM).
+    Boundary faces follow part.boundary_kinds (0 wall, 1 outflow, 2 + k inflow with state k; absent: walls);
+    inflow_states = (K, 5) conservative states, required iff some face is an inflow face."""
 
     def __init__(self, part, dtype=torch.float64, flux_kind=hip.KEPES, mode="compat", capacity=None, state=None,
-                 device=None, plan_options=None):
+                 device=None, plan_options=None, inflow_states=None):
+        inflow_states = check_inflow_states(part, inflow_states)
         if not torch.cuda.is_available():
             raise hip.T8gpuHipError("PlainSolver needs a GPU: the hot path has no CPU implementation")
         hip.lib()
@@ -62,12 +95,27 @@ class PlainSolver:
         self._normals = self._areas = None     # per-face geometry of the compat kernels: uploaded when first asked for
         self.speed = torch.zeros(max(1, part.F + part.B), dtype=dtype, device="cuda")
         self.next, self.prev = STEP0, STEP3  # solver.h:100-101
+        # open boundaries: the kinds (compat kernels) and the inflow table, uploaded once here (launches never allocate or copy)
+        kinds = boundary_kinds_of(part)
+        self.open_boundaries = kinds is not None and bool(np.any(kinds != 0))
+        self.inflow_states = inflow_states
+        self.kinds = self.inflow_table = None
+        if self.open_boundaries:
+            self.kinds = _dev(kinds)
+            states = inflow_states if inflow_states is not None else np.zeros((1, 5))   # (an outflow-only plan: never read)
+            st = torch.from_numpy(np.ascontiguousarray(states)).to(dtype).cuda()
+            self.inflow_table = torch.zeros((states.shape[0], 16), dtype=dtype, device="cuda")
+            hip.call("t8gpu_hip_plain_inflow_table", dtype, hip.ptr(st), int(states.shape[0]), hip.ptr(self.inflow_table),
+                     hip.stream_ptr())
+            torch.cuda.current_stream().synchronize()     # (`st` is released on return)
         self.plan = None
         if mode == "fused":
             from . import fused
             import time
             t0 = time.perf_counter()
             self.plan = fused.PlainPlan(part, dtype, **dict(dict(flux_kind=flux_kind), **(plan_options or {})))
+            if self.plan.c.has_open_faces:
+                self.plan.attach_inflow(self.inflow_table)
             self.plan_build_s = time.perf_counter() - t0          # host tile plan + its upload (amr.adapt reports it)
         elif mode != "compat":
             raise ValueError(mode)
@@ -104,7 +152,11 @@ class PlainSolver:
         hip.call("t8gpu_hip_flux_faces", self.dtype, self.kind, self.F, self.ndim, hip.ptr(self.fn), None,
                  hip.ptr(self.normals), hip.ptr(self.areas), st, fl, hip.ptr(self.speed), stream)
         _timer_end(self, ev)
-        if self.B > 0:
+        if self.B > 0 and self.open_boundaries:
+            hip.call("t8gpu_hip_flux_boundary_bc", self.dtype, self.kind, self.F, self.B, self.ndim, hip.ptr(self.fn),
+                     hip.ptr(self.kinds), hip.ptr(self.inflow_table), hip.ptr(self.normals), hip.ptr(self.areas), st, fl,
+                     hip.ptr(self.speed), stream)
+        elif self.B > 0:
             hip.call("t8gpu_hip_flux_boundary", self.dtype, self.kind, self.F, self.B, self.ndim, hip.ptr(self.fn),
                      hip.ptr(self.normals), hip.ptr(self.areas), st, fl, hip.ptr(self.speed), stream)
         hip.call("t8gpu_hip_rk3_stage", self.dtype, stage, self.N, self.get_own_variables(self.prev), st,
@@ -219,6 +271,10 @@ class SubgridSolver:
     """Subgrid<4,4> / Subgrid<4,4,4>: planes[25, (N+G)*S] in subcells + per-block volumes."""
 
     def __init__(self, part, dtype=torch.float32, flux_kind=hip.KEPES, mode="compat", state=None):
+        kinds = boundary_kinds_of(part)
+        if kinds is not None and np.any(kinds != 0):
+            raise ValueError("SubgridSolver supports reflective walls only: the partition has outflow / inflow boundary faces "
+                             "(open boundaries are implemented for plain elements, PlainSolver)")
         if not torch.cuda.is_available():
             raise hip.T8gpuHipError("SubgridSolver needs a GPU: the hot path has no CPU implementation")
         hip.lib()

@@ -14,6 +14,14 @@ def lib():
         _lib = C.CDLL(os.environ.get("T8GPU_HOST_LIB") or _build.build_host())   # override: sanitizer builds
         _lib.t8gpu_synth_mesh_create.restype = C.c_void_p
         _lib.t8gpu_synth_mesh_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]
+        _lib.t8gpu_synth_mesh_create_sides.restype = C.c_void_p
+        _lib.t8gpu_synth_mesh_create_sides.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
+        _lib.t8gpu_synth_check_sides.restype = C.c_int
+        _lib.t8gpu_synth_check_sides.argtypes = [C.c_int, C.c_void_p]
+        _lib.t8gpu_synth_mesh_sides.restype = C.c_int
+        _lib.t8gpu_synth_mesh_sides.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.t8gpu_synth_part_boundary_kinds.restype = C.c_void_p
+        _lib.t8gpu_synth_part_boundary_kinds.argtypes = [C.c_void_p]
         _lib.t8gpu_synth_mesh_destroy.argtypes = [C.c_void_p]
         _lib.t8gpu_synth_mesh_num_elements.restype = C.c_int64
         _lib.t8gpu_synth_mesh_num_elements.argtypes = [C.c_void_p]
@@ -68,12 +76,46 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-class SynthMesh:
-    """Global 2:1-balanced periodic (or walled) quad/hex mesh in Morton order."""
+WALL, OUTFLOW, INFLOW = 0, 1, 2          # boundary_kinds codes (t8gpu_host.h); inflow state k has code INFLOW + k
+MAX_INFLOW_STATES = 8
+_SIDE_CODES = {"periodic": -1, "wall": WALL, "outflow": OUTFLOW}
 
-    def __init__(self, dim, base_level, max_level, band=0.0, shrink=1.0, periodic=True):
+
+def side_codes(dim, sides):
+    """sides[2 * dim] (order -x, +x, -y, +y, -z, +z) as provider codes: "periodic" -1, "wall" 0, "outflow" 1, int k -> inflow
+    state k (2 + k). Raises ValueError on anything else and on a periodic side whose opposite side is not periodic."""
+    sides = tuple(sides)
+    if len(sides) != 2 * dim:
+        raise ValueError(f"sides needs {2 * dim} entries (-x, +x, -y, +y{', -z, +z' if dim == 3 else ''}), got {len(sides)}")
+    codes = []
+    for s in sides:
+        if isinstance(s, str) and s in _SIDE_CODES:
+            codes.append(_SIDE_CODES[s])
+        elif isinstance(s, (int, np.integer)) and not isinstance(s, bool) and 0 <= int(s) < MAX_INFLOW_STATES:
+            codes.append(INFLOW + int(s))
+        else:
+            raise ValueError(f"invalid side {s!r}: 'periodic', 'wall', 'outflow' or an inflow state index 0..{MAX_INFLOW_STATES - 1}")
+    for a in range(dim):
+        if (codes[2 * a] == -1) != (codes[2 * a + 1] == -1):
+            raise ValueError(f"side {'xyz'[a]}: a periodic side must be paired with the opposite side of its axis")
+    arr = np.array(codes, np.int32)
+    assert lib().t8gpu_synth_check_sides(dim, _p(arr)) == 0
+    return arr
+
+
+class SynthMesh:
+    """Global 2:1-balanced quad/hex mesh of the unit square / cube in Morton order. periodic=True: every side periodic,
+    False: every side a reflective wall; sides=(...): one entry per side (see side_codes), overrides `periodic`."""
+
+    def __init__(self, dim, base_level, max_level, band=0.0, shrink=1.0, periodic=True, sides=None):
         self.dim, self.base_level, self.max_level = dim, base_level, max_level
-        self._h = lib().t8gpu_synth_mesh_create(dim, base_level, max_level, float(band), float(shrink), int(periodic))
+        if sides is None:
+            self._h = lib().t8gpu_synth_mesh_create(dim, base_level, max_level, float(band), float(shrink), int(periodic))
+        else:
+            if dim not in (2, 3):
+                raise ValueError("invalid synthetic mesh parameters")
+            codes = side_codes(dim, sides)
+            self._h = lib().t8gpu_synth_mesh_create_sides(dim, base_level, max_level, float(band), float(shrink), _p(codes))
         if not self._h:
             raise ValueError("invalid synthetic mesh parameters")
         self.num_elements = lib().t8gpu_synth_mesh_num_elements(self._h)
@@ -83,6 +125,13 @@ class SynthMesh:
         if getattr(self, "_h", None):
             lib().t8gpu_synth_mesh_destroy(self._h)
             self._h = None
+
+    @property
+    def sides(self):
+        """provider codes of the 2 * dim sides (-1 periodic, 0 wall, 1 outflow, 2 + k inflow k)"""
+        out = np.zeros(6, np.int32)
+        n = lib().t8gpu_synth_mesh_sides(self._h, _p(out))
+        return out[:n]
 
     def partition(self, rank=0, nranks=1, subgrid=False, normal_dim=None):
         return Partition(self, rank, nranks, subgrid, normal_dim)
@@ -157,6 +206,8 @@ class Partition:
         self.areas = _view(ptrs[2], self.F + self.B, np.float64, owner)
         self.level_diff = _view(ptrs[3], self.F, np.int32, owner) if subgrid else None
         self.nb_offset = _view(ptrs[4], dim * self.F, np.int32, owner) if subgrid else None
+        # boundary_kinds[B]: 0 wall, 1 outflow, 2 + k inflow state k (t8gpu_host.h), in the order of the boundary faces
+        self.boundary_kinds = _view(lib().t8gpu_synth_part_boundary_kinds(h), self.B, np.uint8, owner)
         tot = self.N + self.G
         self.levels = np.empty(tot, np.int32)                # (np.empty: the provider overwrites every entry)
         self.volumes = np.empty(tot, np.float64)

@@ -225,6 +225,7 @@ class UnstructuredPartition:
         fn[0: 2 * self.F: 2], fn[1: 2 * self.F: 2] = local(li), local(ri)
         fn[2 * self.F:] = local(L[F:][keep_b])
         self.face_neighbors = fn
+        self.boundary_kinds = None             # (no boundary kinds from this provider: every boundary face is a wall)
         A = np.concatenate([mesh.area_vec[:F][keep_i], mesh.area_vec[F:][keep_b]])
         area = np.linalg.norm(A, axis=1)
         self.areas = area
