@@ -54,44 +54,32 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-std=c++17", "-O3", "-fPIC", "-munsafe-fp
              "-Wno-unused-function"]
 
 
-def build_hip(force=False, variant=None, defines=(), only=None):
-    """One object per .hip file (compiled in parallel, rebuilt only when the file or a header changed), then one link.
-    variant / defines: an experiment build with extra -D flags into lib/variants/libt8gpu_hip_<variant>.so
-    (load it with T8GPU_HIP_LIB=...; used for A/B measurements and diagnostics, never by the product path).
-    only: basenames of the sources the defines matter for -- the other objects are taken from the default build."""
+def build_hip(force=False):
+    """One object per .hip file (compiled in parallel, rebuilt only when the file or a header changed), then one link."""
     from concurrent.futures import ThreadPoolExecutor
     srcs = _glob(os.path.join(CSRC, "hip"), (".hip", ".cpp"))
     hdrs = _glob(os.path.join(CSRC, "hip"), (".h", ".hpp")) + _glob(os.path.join(ROOT, "include"), (".h",))
-    objdir = os.path.join(LIB, "obj", variant or "default")
-    target = HIP_LIB if variant is None else os.path.join(LIB, "variants", f"libt8gpu_hip_{variant}.so")
+    objdir = os.path.join(LIB, "obj")
     os.makedirs(objdir, exist_ok=True)
-    os.makedirs(os.path.dirname(target), exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     stamp = os.path.join(objdir, "flags.txt")
-    flags = HIP_FLAGS + list(defines)
-    if not os.path.exists(stamp) or open(stamp).read() != " ".join(flags):
+    if not os.path.exists(stamp) or open(stamp).read() != " ".join(HIP_FLAGS):
         force = True
-    jobs = []
-    default_objdir = os.path.join(LIB, "obj", "default")
-    if variant is not None and only is not None:
-        build_hip()                                            # the shared objects must be current
     def objpath(src):
-        shared = variant is not None and only is not None and os.path.basename(src) not in only
-        return os.path.join(default_objdir if shared else objdir, os.path.basename(src) + ".o")
+        return os.path.join(objdir, os.path.basename(src) + ".o")
+    jobs = []
     for src in srcs:
         obj = objpath(src)
-        if obj.startswith(default_objdir + os.sep) and variant is not None:
-            continue
         if force or _newer(obj, [src] + hdrs):
-            jobs.append([hipcc] + flags + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(CSRC, "hip"), "-c", src, "-o", obj])
+            jobs.append([hipcc] + HIP_FLAGS + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(CSRC, "hip"), "-c", src, "-o", obj])
     if jobs:
         with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as pool:
             list(pool.map(_run, jobs))
-        open(stamp, "w").write(" ".join(flags))
+        open(stamp, "w").write(" ".join(HIP_FLAGS))
     objs = [objpath(src) for src in srcs]
-    if jobs or _newer(target, objs):
-        _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs + ["-L/opt/rocm/lib", "-lrccl"])
-    return target
+    if jobs or _newer(HIP_LIB, objs):
+        _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", HIP_LIB] + objs + ["-L/opt/rocm/lib", "-lrccl"])
+    return HIP_LIB
 
 
 def kernel_source_hash():

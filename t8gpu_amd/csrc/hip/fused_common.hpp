@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
+#include <utility>
 
 #include "flux_math.hpp"
 #include "t8gpu_hip.h"
@@ -27,6 +29,65 @@ inline int env_per_cu(const char* name) {
   const char* env = std::getenv(name);
   const int   v   = env ? std::atoi(env) : 0;
   return (v < 0 || v > 8) ? 0 : v;
+}
+
+// ---- host side of the fused-stage launchers ---------------------------------------------------------------------
+// Runtime launch choices -> compile-time constants: dispatch(f, kind, stage, b...) calls f(int_c<kind>, int_c<stage>,
+// bool_c<b>...) for kind 0..2 (KEPES, HLL, HLLC) and stage 1..3. The generic lambda f names its kernel with these constants
+// as template arguments (and `if constexpr` keeps combinations it never launches from instantiating a kernel).
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <bool V>
+using bool_c = std::integral_constant<bool, V>;
+
+template <class F>
+int dispatch_flags(F&& f) {
+  return f();
+}
+template <class F, class... B>
+int dispatch_flags(F&& f, bool b, B... rest) {
+  if (b) return dispatch_flags([&](auto... c) { return f(bool_c<true>{}, c...); }, rest...);
+  return dispatch_flags([&](auto... c) { return f(bool_c<false>{}, c...); }, rest...);
+}
+template <class F, class... B>
+int dispatch(F&& f, int kind, int stage, B... flags) {
+  auto with_kind = [&](auto K) {
+    auto with_stage = [&](auto S) { return dispatch_flags([&](auto... c) { return f(K, S, c...); }, flags...); };
+    return stage == 1 ? with_stage(int_c<1>{}) : stage == 2 ? with_stage(int_c<2>{}) : with_stage(int_c<3>{});
+  };
+  return kind == 0 ? with_kind(int_c<0>{}) : kind == 1 ? with_kind(int_c<1>{}) : with_kind(int_c<2>{});
+}
+
+// Launches `kernel` with `lds` bytes of dynamic LDS; a kernel is granted more than the default 64 KiB first. Returns 0 or a
+// hipError_t.
+template <class... P, class... A>
+int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, A&&... args) {
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             static_cast<int>(lds));
+    if (e != hipSuccess) return static_cast<int>(e);
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, std::forward<A>(args)...);
+  return static_cast<int>(hipGetLastError());
+}
+
+// element slots per LDS plane of a generic tile: the plan's max_slots, or (0) the element and halo caps together
+__host__ __device__ __forceinline__ int plan_slots(const T8gpuPlainPlan& P) {
+  return P.max_slots > 0 ? P.max_slots : P.max_elems + P.max_halo;
+}
+
+// Do the generic tiles of this plan run the pipelined one-tile kernels (ELL rows + tile descriptors: no CSR lists read), or the
+// generic kernel, which walks csr_off / csr_ent? One definition for the launchers (kernels_fused.hip, kernels_fused_patch.hip)
+// and for t8gpu_hip_plain_needs_csr, which the host asks before it decides what to upload.
+inline bool plain_tiles_pipelined(const T8gpuPlainPlan* plan) {
+  return plan->ell && plan->tile_desc && plan->ell_width >= 8 && plan->ell_width % 8 == 0 && plan->max_elems <= 256 &&
+         plan_slots(*plan) <= 512 && plan->max_faces <= 1024;
+}
+
+// LDS bytes of the fp64 KEPES logarithm table (flux_math.hpp: kLogTab), 0 where the kernel has none
+template <class T>
+size_t lds_log_table(int kind) {
+  return (sizeof(T) == 8 && kind == 0) ? 2 * kLogTabEntries * sizeof(double) : 0;
 }
 
 template <class T>
@@ -148,6 +209,13 @@ constexpr int rec_words() {
   return sizeof(T) == 8 ? (NW > 5 ? 10 : 6) : 12;
 }
 
+// dynamic LDS of a patch or persistent launch: `words` words of flux buffers and tables, `records` LDS records, the logarithm table
+template <class T>
+size_t record_lds(int kind, size_t words, size_t records) {
+  const size_t rec = kind == 0 ? rec_words<T, kPrimWords>() : rec_words<T, 5>();
+  return sizeof(T) * (words + rec * records) + lds_log_table<T>(kind);
+}
+
 template <class T, int NW>
 T8_DEV void rec_store(T* rec, const T* w) {
   using V         = typename vec16<T>::type;
@@ -181,12 +249,7 @@ T8_DEV void rec_load(const T* rec, T* w) {
 
 template <class T>
 T8_DEV void prim_words(const T s[5], T w[kPrimWords], const double* logtab) {
-#ifdef T8GPU_EXP_NOMATH    // experiment builds only: same loads, LDS traffic, barriers and stores, (almost) no arithmetic
-  Prim<T> q;
-  q.rho = s[0]; q.vx = s[1]; q.vy = s[2]; q.vz = s[3]; q.p = s[4]; q.beta = s[0]; q.lrho = s[1]; q.lbeta = s[2]; q.v0 = s[3];
-#else
   const Prim<T> q = prim_from_state<T, sizeof(T) == 8>(s, logtab);   // fp64: table-driven logarithms (flux_math.hpp)
-#endif
   w[0] = q.rho; w[1] = q.vx; w[2] = q.vy; w[3] = q.vz; w[4] = q.p; w[5] = q.beta; w[6] = q.lrho; w[7] = q.lbeta; w[8] = q.v0;
 }
 template <class T>

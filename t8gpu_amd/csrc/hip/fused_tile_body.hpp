@@ -37,12 +37,7 @@ T8_DEV bool ell_accumulate(uint4 w, int pass, const T* __restrict__ ff, T acc[5]
 
 template <class T>
 T8_DEV void store_prim(T* pe, int LE, int i, const T s[5], const double* logtab) {
-#ifdef T8GPU_EXP_NOMATH    // experiment builds only: same loads, LDS traffic, barriers and stores, (almost) no arithmetic
-  Prim<T> q;
-  q.rho = s[0]; q.vx = s[1]; q.vy = s[2]; q.vz = s[3]; q.p = s[4]; q.beta = s[0]; q.lrho = s[1]; q.lbeta = s[2]; q.v0 = s[3];
-#else
   const Prim<T> q = prim_from_state<T, sizeof(T) == 8>(s, logtab);
-#endif
   pe[0 * LE + i] = q.rho;
   pe[1 * LE + i] = q.vx;
   pe[2 * LE + i] = q.vy;
@@ -63,10 +58,6 @@ T8_DEV void load_prim(const T* pe, int LE, int i, Prim<T>& q) {
 // MAXP = 2: at most 512 faces per tile, both passes' face records loaded in the prologue (2D meshes).
 // MAXP = 4: up to 1024 faces per tile (3D meshes: a 256-element tile has ~3 faces per element plus its
 // surface); the record of pass p + 1 is fetched at the top of pass p, so two are live at any time.
-// SCATTER = true is the accumulation the project brief sketches: every face lane adds -F / +F to per-element
-// accumulators in LDS with ds_add_f32 / ds_add_f64 (no ELL rows, no gather, one barrier after the last pass).
-// Kept as a measured alternative (T8GPU_LDS_SCATTER=1): the order of the additions is not fixed, so the
-// result is no longer bitwise reproducible, and the default gather is faster.
 // DENSE: register budget for 4 (fp64) / 5 (fp32) workgroups per CU. The fp64 KEPES kernel then spills ~20 registers and
 // still gains 7 % where the tiles leave the LDS room for the fourth workgroup (2D meshes: c2 7 640 -> 8 150 M/s, the
 // one-tile kernel on c4 7 520 -> 8 090); where they do not (3D tiles: ~39 KB) the spills cost 9 % (c5, c5u); HLL / HLLC
@@ -76,14 +67,14 @@ T8_DEV void load_prim(const T* pe, int LE, int i, Prim<T>& q) {
 // table from global memory instead of an LDS copy (c2: +1 %).
 // OPEN: the plan has outflow / inflow faces (T8gpuPlainPlan::has_open_faces): their codes are decoded (decode_face_side);
 // OPEN = false is the wall-only body, unchanged.
-template <class T, int KIND, int STAGE, bool DICT, int MAXP, bool SCATTER = false, bool DENSE = false, bool OPEN = false>
+template <class T, int KIND, int STAGE, bool DICT, int MAXP, bool DENSE = false, bool OPEN = false>
 T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& prev, const FVars<T>& src, const FVars<T>& out,
                             const T* __restrict__ vol, T dt, T* __restrict__ speed) {
   extern __shared__ __attribute__((aligned(16))) double lds_raw[];
   using V4 = typename vec4<T>::type;
   T* const      lds = reinterpret_cast<T*>(lds_raw);
   constexpr int NW  = KIND == 0 ? kPrimWords : 5;
-  const int     LE  = P.max_slots > 0 ? P.max_slots : P.max_elems + P.max_halo;
+  const int     LE  = plan_slots(P);
   T* const      pe  = lds;
   T* const      ff  = lds + (size_t)NW * LE;  // [5][256]: one pass of 256 faces at a time
   constexpr bool kTab = sizeof(T) == 8 && KIND == 0;   // fp64 KEPES: table-driven logarithms, table behind the flux buffer
@@ -154,10 +145,6 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
     lt_lds[tid] = kLogTab[tid];
     __syncthreads();
   }
-  if (SCATTER) {
-#pragma unroll
-    for (int k = 0; k < 5; k++) ff[k * 256 + tid] = T(0);
-  }
   if (a0) {
     if (KIND == 0) {
       store_prim<T>(pe, LE, tid, s0, lt);
@@ -186,18 +173,16 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
     const bool    last = it == MAXP - 1 || nf <= 256 * (it + 1);
     if (fi.valid) {
       const int  l = fi.lr & 0xFFFFu, r16 = fi.lr >> 16;
-      bool       wall, other;   // other: the right side is an element of the tile window
+      bool       wall;
       int        r, inflow = -1;
       if constexpr (OPEN) {
         const FaceSide fs = decode_face_side(l, r16);
         wall   = fs.wall;
-        other  = !fs.wall && !fs.open;
         r      = fs.r;
         inflow = fs.inflow;
       } else {
-        wall  = r16 == 0xFFFFu;
-        other = !wall;
-        r     = wall ? l : r16;
+        wall = r16 == 0xFFFFu;
+        r    = wall ? l : r16;
       }
       T          g[5], spd = T(0);
       // The tile's faces are ordered by direction inside each block of 256 (tile_plan.cpp), so a wavefront's active lanes
@@ -266,13 +251,7 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
           inflow_prim<T>(P, inflow, R);
         else
           load_prim<T>(pe, LE, r, R);
-#ifdef T8GPU_EXP_NOMATH
-        g[0] = L.rho + R.rho + n[0] + t1[0]; g[1] = L.vx + R.vx + t2[0]; g[2] = L.vy + R.vy + L.beta + R.beta; g[3] = L.vz + R.vz + L.lrho + R.lrho;
-        g[4] = L.p + R.p + L.lbeta + R.lbeta + L.v0 + R.v0 + gm.w;
-        spd = g[0];
-#else
         kepes_prim<T>(L, R, wall, n, t1, t2, gm.w, g, spd);
-#endif
       } else {
         T sl[5], sr[5];
 #pragma unroll
@@ -289,19 +268,8 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
       }
       }
       if (fi.orig >= 0) speed[fi.orig] = spd;
-      if (SCATTER) {
-        if (l < ne) {
 #pragma unroll
-          for (int k = 0; k < 5; k++) atomicAdd(&ff[k * 256 + l], -g[k]);
-        }
-        if (other && r < ne) {
-#pragma unroll
-          for (int k = 0; k < 5; k++) atomicAdd(&ff[k * 256 + r], g[k]);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 5; k++) ff[k * 256 + tid] = g[k];
-      }
+      for (int k = 0; k < 5; k++) ff[k * 256 + tid] = g[k];
     }
     if (MAXP == 2 && last) {  // last pass: start the RK stage's loads; they fly during the barrier + gather
       if (STAGE > 1) {
@@ -310,7 +278,6 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
       }
       volume = vol[e];
     }
-    if (SCATTER) continue;   // the accumulators take every pass; one barrier after the loop
     __syncthreads();
     if (own) {
       bool done = ell_accumulate<T>(ell0, it, ff, acc);
@@ -318,14 +285,6 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
     }
     if (!last) __syncthreads();   // the buffer is rewritten by the next pass
   }
-  if (SCATTER) {
-    __syncthreads();
-    if (own) {
-#pragma unroll
-      for (int k = 0; k < 5; k++) acc[k] = ff[k * 256 + tid];
-    }
-  }
-
   if (MAXP > 2) {  // (the last pass is not known at compile time here: fetched after the loop, other workgroups cover it)
     if (STAGE > 1) {
 #pragma unroll
@@ -346,17 +305,12 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
 }
 
 // one tile per workgroup: workgroup b takes position tile_begin + xcd_position(b) of tile_order
-template <class T, int KIND, int STAGE, bool DICT, int MAXP, bool SCATTER = false, bool DENSE = false, bool OPEN = false>
+template <class T, int KIND, int STAGE, bool DICT, int MAXP, bool DENSE = false, bool OPEN = false>
 __global__ __launch_bounds__(256, DENSE ? (sizeof(T) == 8 ? 4 : 5) : 1) void k_plain_fused_p(T8gpuPlainPlan P, int tile_begin, FVars<T> prev, FVars<T> src,
                                                        FVars<T> out, const T* __restrict__ vol, T dt,
                                                        T* __restrict__ speed) {
-#ifdef T8GPU_EXP_TILEMOD   // experiment builds only (build.py variants): every workgroup works on one of the first few tiles,
-                           // so all traffic stays in the caches -- what remains is the kernel's instruction time
-  const int pos = tile_begin + xcd_position(blockIdx.x, gridDim.x) % T8GPU_EXP_TILEMOD;
-#else
   const int pos = tile_begin + xcd_position(blockIdx.x, gridDim.x);
-#endif
-  plain_tile_body<T, KIND, STAGE, DICT, MAXP, SCATTER, DENSE, OPEN>(P, pos, prev, src, out, vol, dt, speed);
+  plain_tile_body<T, KIND, STAGE, DICT, MAXP, DENSE, OPEN>(P, pos, prev, src, out, vol, dt, speed);
 }
 
 }  // namespace t8gpu_hip

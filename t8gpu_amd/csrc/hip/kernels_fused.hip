@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void k_plain_fused(T8gpuPlainPlan P, int tile_
   extern __shared__ double lds_raw[];
   T* const      lds = reinterpret_cast<T*>(lds_raw);
   constexpr int NW  = KIND == 0 ? kPrimWords : 5;  // words per element kept in LDS
-  const int     LE  = P.max_slots > 0 ? P.max_slots : P.max_elems + P.max_halo;    // element slots per LDS plane
+  const int     LE  = plan_slots(P);                 // element slots per LDS plane
   const int     LF  = P.max_faces;
   T* const      pe  = lds;                         // [NW][LE]
   T* const      ff  = lds + (size_t)NW * LE;       // [5][LF]
@@ -160,15 +160,6 @@ __global__ __launch_bounds__(256) void k_plain_fused(T8gpuPlainPlan P, int tile_
 namespace t8gpu_hip {
 
 
-// Do the generic tiles of this plan run the pipelined one-tile kernels (ELL rows + tile descriptors: no CSR lists read), or the
-// generic kernel, which walks csr_off / csr_ent? One definition for the launcher below and for t8gpu_hip_plain_needs_csr,
-// which the host asks before it decides what to upload (t8gpu_amd/fused.py used to repeat a part of this test).
-inline bool plain_tiles_pipelined(const T8gpuPlainPlan* plan) {
-  const int slots = plan->max_slots > 0 ? plan->max_slots : plan->max_elems + plan->max_halo;
-  return plan->ell && plan->tile_desc && plan->ell_width >= 8 && plan->ell_width % 8 == 0 && plan->max_elems <= 256 && slots <= 512 &&
-         plan->max_faces <= 1024;
-}
-
 // tiles [tile_begin, tile_begin + tile_count) of tile_order, none of them a patch tile. whole_plan: the caller's launch
 // covers the whole plan (what the persistent kernel is for).
 template <class T, class V>
@@ -178,15 +169,13 @@ int plain_generic_stage(int kind, int stage, const T8gpuPlainPlan* plan, int til
   const int   nw = kind == 0 ? kPrimWords : 5;
   hipStream_t s  = static_cast<hipStream_t>(stream);
   const dim3  grid(tile_count), block(256);
-  const int   slots = plan->max_slots > 0 ? plan->max_slots : plan->max_elems + plan->max_halo;
+  const int   slots = plan_slots(*plan);
   const bool  pipelined = plain_tiles_pipelined(plan);
   const bool  four = plan->max_faces > 512;
   // (the generic kernel walks the CSR lists; callers that know their plan stays inside the pipelined kernels' limits need not
   //  upload them -- t8gpu_amd/fused.py does not)
   if (!pipelined && (!plan->csr_off || !plan->csr_ent)) return static_cast<int>(hipErrorInvalidValue);
-  static const bool scatter_env = std::getenv("T8GPU_LDS_SCATTER") && std::getenv("T8GPU_LDS_SCATTER")[0] == '1';   // measured alternative
-  const bool        open = plan->has_open_faces != 0;   // outflow / inflow faces: the OPEN instantiations
-  const bool        scatter = scatter_env && !open;     // (the scatter form is kept for walls only)
+  const bool  open = plan->has_open_faces != 0;   // outflow / inflow faces: the OPEN instantiations
   if (open && !plan->inflow) return static_cast<int>(hipErrorInvalidValue);
   // The persistent, software-pipelined kernel (kernels_fused_persistent.hip) for launches that cover the whole plan.
   // A multi-rank stage is split into tile classes on three streams beside the pack / RCCL / unpack kernels
@@ -195,80 +184,34 @@ int plain_generic_stage(int kind, int stage, const T8gpuPlainPlan* plan, int til
   // ranges use the one-tile-per-workgroup kernels, whose slots free up continuously. Both give the same bits.
   static const bool persistent_always = std::getenv("T8GPU_PERSISTENT") && std::getenv("T8GPU_PERSISTENT")[0] == '2';
   // (the persistent kernel knows no ghost window -- t8gpu_hip.h: such launches run one tile per workgroup)
-  if (!scatter && (persistent_always || whole_plan) && !plan->ghost_buf && !plan->send_map) {
+  if ((persistent_always || whole_plan) && !plan->ghost_buf && !plan->send_map) {
     const int rc = plain_persistent_stage<T>(kind, stage, plan, tile_begin, tile_count, fmk<T>(prev), fmk<T>(mid), fmk<T>(out), volume,
                                              dt, speed, s);
     if (rc >= 0) return rc;
   }
-  const size_t lds_table = (sizeof(T) == 8 && kind == 0) ? 2 * kLogTabEntries * sizeof(double) + 16 : 0;
+  const size_t tab       = lds_log_table<T>(kind);
+  const size_t lds_table = tab ? tab + 16 : 0;
   size_t       lds       = sizeof(T) * ((size_t)nw * slots + (size_t)5 * (pipelined ? 256 : plan->max_faces)) + lds_table;
-#ifdef T8GPU_EXP_LDS_PAD   // experiment builds only: fewer workgroups per CU, to measure how much the kernel leans on occupancy
-  if (const char* pad = std::getenv("T8GPU_EXP_LDS_PAD")) lds += static_cast<size_t>(std::atoi(pad));
-#endif
   if (lds > 160 * 1024) return static_cast<int>(hipErrorInvalidValue);
-  const bool  dict = pipelined && plan->geo_idx && plan->geo_table && plan->n_geo > 0;
-  static const int dense_env = std::getenv("T8GPU_DENSE") ? std::atoi(std::getenv("T8GPU_DENSE")) : -1;   // (measurements)
-  const bool  dense = pipelined && !scatter && kind == 0 && sizeof(T) == 8 && plan->geo_idx && plan->geo_table && plan->n_geo > 0 &&
-                     plan->max_faces <= 512 && (dense_env >= 0 ? dense_env != 0 : lds - lds_table <= static_cast<size_t>(36) * 1024);
+  const bool  dict  = pipelined && plan->geo_idx && plan->geo_table && plan->n_geo > 0;
+  // the DENSE register budget (fused_tile_body.hpp) for fp64 KEPES tiles of <= 36 KB with a dictionary and <= 512 faces
+  const bool  dense = dict && !four && kind == 0 && sizeof(T) == 8 && lds - lds_table <= static_cast<size_t>(36) * 1024;
   if (dense) lds -= lds_table;   // (the DENSE kernel reads the logarithm table from global memory)
-#define T8_LAUNCH(KERNEL, NAME)                                                                              \
-  do {                                                                                                       \
-    note_stage_kernel(tile_count, NAME, static_cast<int>(sizeof(T)), kind, stage);                           \
-    if (lds > 64 * 1024) {                                                                                   \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL),                             \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)); \
-      if (e != hipSuccess) return static_cast<int>(e);                                                       \
-    }                                                                                                        \
-    hipLaunchKernelGGL(KERNEL, grid, block, lds, s, *plan, tile_begin, fmk<T>(prev), fmk<T>(mid),            \
-                       fmk<T>(out), volume, dt, speed);                                                      \
-  } while (0)
-#define T8_FUSED_OPEN(K, S)                                         \
-  do {                                                              \
-    if (dict && !four && dense)                                     \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, true, 2, false, true, true>), "k_plain_fused_p<T, K, S, true, 2, false, true, true>");    \
-    else if (dict && !four)                                         \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, true, 2, false, false, true>), "k_plain_fused_p<T, K, S, true, 2, false, false, true>"); \
-    else if (dict)                                                  \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, true, 4, false, false, true>), "k_plain_fused_p<T, K, S, true, 4, false, false, true>"); \
-    else if (pipelined && !four)                                    \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, false, 2, false, false, true>), "k_plain_fused_p<T, K, S, false, 2, false, false, true>"); \
-    else if (pipelined)                                             \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, false, 4, false, false, true>), "k_plain_fused_p<T, K, S, false, 4, false, false, true>"); \
-    else                                                            \
-      T8_LAUNCH((k_plain_fused<T, K, S, true>), "k_plain_fused<T, K, S, true>");                                      \
-  } while (0)
-#define T8_FUSED(K, S)                                              \
-  do {                                                              \
-    if (open)                                                       \
-      T8_FUSED_OPEN(K, S);                                          \
-    else if (scatter && dict && !four)                              \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, true, 2, true>), "k_plain_fused_p<T, K, S, true, 2, true, false>");         \
-    else if (scatter && pipelined && !four)                         \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, false, 2, true>), "k_plain_fused_p<T, K, S, false, 2, true, false>");        \
-    else if (dict && !four && dense)                                \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, true, 2, false, true>), "k_plain_fused_p<T, K, S, true, 2, false, true>");  \
-    else if (dict && !four)                                         \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, true, 2>), "k_plain_fused_p<T, K, S, true, 2, false, false>");               \
-    else if (dict)                                                  \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, true, 4>), "k_plain_fused_p<T, K, S, true, 4, false, false>");               \
-    else if (pipelined && !four)                                    \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, false, 2>), "k_plain_fused_p<T, K, S, false, 2, false, false>");              \
-    else if (pipelined)                                             \
-      T8_LAUNCH((k_plain_fused_p<T, K, S, false, 4>), "k_plain_fused_p<T, K, S, false, 4, false, false>");              \
-    else                                                            \
-      T8_LAUNCH((k_plain_fused<T, K, S>), "k_plain_fused<T, K, S>");                          \
-  } while (0)
-  if (kind == 0) {
-    if (stage == 1) T8_FUSED(0, 1); else if (stage == 2) T8_FUSED(0, 2); else T8_FUSED(0, 3);
-  } else if (kind == 1) {
-    if (stage == 1) T8_FUSED(1, 1); else if (stage == 2) T8_FUSED(1, 2); else T8_FUSED(1, 3);
-  } else {
-    if (stage == 1) T8_FUSED(2, 1); else if (stage == 2) T8_FUSED(2, 2); else T8_FUSED(2, 3);
-  }
-#undef T8_FUSED
-#undef T8_FUSED_OPEN
-#undef T8_LAUNCH
-  return static_cast<int>(hipGetLastError());
+  return dispatch(
+      [&](auto K, auto S, auto OPEN, auto PIPELINED, auto DICT, auto FOUR, auto DENSE) {
+        if constexpr (!PIPELINED) {
+          note_stage_kernel<T>(tile_count, "k_plain_fused", K, S, OPEN);
+          return launch(&k_plain_fused<T, K, S, OPEN>, grid, block, lds, s, *plan, tile_begin, fmk<T>(prev), fmk<T>(mid), fmk<T>(out),
+                        volume, dt, speed);
+        } else {
+          constexpr int  MAXP = FOUR ? 4 : 2;
+          constexpr bool D    = DENSE && DICT && !FOUR && K == 0 && sizeof(T) == 8;   // (`dense` is never set otherwise)
+          note_stage_kernel<T>(tile_count, "k_plain_fused_p", K, S, DICT, MAXP, D, OPEN);
+          return launch(&k_plain_fused_p<T, K, S, DICT, MAXP, D, OPEN>, grid, block, lds, s, *plan, tile_begin, fmk<T>(prev), fmk<T>(mid),
+                        fmk<T>(out), volume, dt, speed);
+        }
+      },
+      kind, stage, open, pipelined, dict, four, dense);
 }
 
 // The C-ABI entry: splits the range of tile_order into its patch tiles (kernels_fused_patch.hip) and its generic tiles
@@ -293,10 +236,8 @@ int plain_fused_stage(int kind, int stage, const T8gpuPlainPlan* plan, int tile_
   // the three-stream pipeline of rounds 1-3 resident workgroups that never leave kept the exchange kernels from starting
   // (profiles/r03_halo_overhead.md); the two-lane driver queues the RCCL kernel and the ghost-reading tiles a stage ahead of
   // their deadline and they slip in at the drain between two interior launches: rank 3 of the 8-way c4 split 0.168 -> 0.153
-  // ms/step (profiles/r04_halo_overhead.md). T8GPU_INTERIOR_PERSISTENT=0: one tile per workgroup (measurements).
-  static const bool interior_persistent = !(std::getenv("T8GPU_INTERIOR_PERSISTENT") && std::getenv("T8GPU_INTERIOR_PERSISTENT")[0] == '0');
-  const bool whole = (tile_begin == 0 && tile_count == plan->ntiles) ||
-                     (interior_persistent && tile_begin == 0 && tile_count == plan->n_interior_tiles && tile_count < plan->ntiles);
+  // ms/step (profiles/r04_halo_overhead.md).
+  const bool whole = tile_begin == 0 && (tile_count == plan->ntiles || tile_count == plan->n_interior_tiles);
   const int  np_total = plan->n_patch_tiles[0] + plan->n_patch_tiles[1] + plan->n_patch_tiles[2];
   if (np_total == 0) return plain_generic_stage<T, V>(kind, stage, plan, tile_begin, tile_count, prev, mid, out, volume, dt, speed, whole, stream);
   if (!plan->tile_desc) return static_cast<int>(hipErrorInvalidValue);
@@ -306,6 +247,8 @@ int plain_fused_stage(int kind, int stage, const T8gpuPlainPlan* plan, int tile_
   const int seg[4] = {0, nd, plan->n_interior_tiles, plan->ntiles};
   const int b = tile_begin, e = tile_begin + tile_count;
   static const bool persistent_always = std::getenv("T8GPU_PERSISTENT") && std::getenv("T8GPU_PERSISTENT")[0] == '2';
+  const bool        persistent        = whole || persistent_always;   // (patch launches: persistent grids)
+  const hipStream_t s                 = static_cast<hipStream_t>(stream);
   // generic sub-ranges that touch are launched together (single rank: one patch launch + one generic launch)
   int gb = -1, ge = -1;
   auto flush = [&]() -> int {
@@ -314,7 +257,6 @@ int plain_fused_stage(int kind, int stage, const T8gpuPlainPlan* plan, int tile_
     gb = ge = -1;
     return rc;
   };
-  static const bool scatter = std::getenv("T8GPU_LDS_SCATTER") && std::getenv("T8GPU_LDS_SCATTER")[0] == '1';
   for (int c = 0; c < 3; c++) {
     const int s0 = seg[c], s1 = seg[c + 1], p1 = s0 + plan->n_patch_tiles[c];
     if (p1 > s1) return static_cast<int>(hipErrorInvalidValue);
@@ -331,34 +273,32 @@ int plain_fused_stage(int kind, int stage, const T8gpuPlainPlan* plan, int tile_
       if (ni < 0 || ni > plan->n_patch_tiles[c]) return static_cast<int>(hipErrorInvalidValue);
       const int i0 = p1 - ni;   // first irregular patch of the class
       const int rb = pb, re = pe < i0 ? pe : i0, ib = pb > i0 ? pb : i0, ie = pe;
-      int both = -1;
-      if (re > rb && ie > ib && (whole || persistent_always))   // both kinds in one launch (kernels_fused_patch3.hip)
-        both = plain_patch3_both_stage<T>(kind, stage, plan, rb, re - rb, ib, ie - ib, fmk<T>(prev), fmk<T>(mid), fmk<T>(out), volume, dt, speed,
-                                          static_cast<hipStream_t>(stream));
+      const int both = re > rb && ie > ib && persistent   // both kinds in one launch (kernels_fused_patch3.hip; -1: not taken)
+                           ? plain_patch3_both_stage<T>(kind, stage, plan, rb, re - rb, ib, ie - ib, fmk<T>(prev), fmk<T>(mid), fmk<T>(out),
+                                                        volume, dt, speed, s)
+                           : -1;
       if (both > 0) return both;
-      if (both == 0) {
-        // done
-      } else {
-      if (re > rb)
-        if (int rc = plain_patch3_stage<T>(kind, stage, plan, rb, re - rb, fmk<T>(prev), fmk<T>(mid), fmk<T>(out), volume, dt, speed,
-                                           whole || persistent_always, false, static_cast<hipStream_t>(stream)))
-          return rc;
-      if (ie > ib)
-        if (int rc = plain_patch3_stage<T>(kind, stage, plan, ib, ie - ib, fmk<T>(prev), fmk<T>(mid), fmk<T>(out), volume, dt, speed,
-                                           whole || persistent_always, true, static_cast<hipStream_t>(stream)))
-          return rc;
+      if (both < 0) {
+        if (re > rb)
+          if (int rc = plain_patch3_stage<T>(kind, stage, plan, rb, re - rb, fmk<T>(prev), fmk<T>(mid), fmk<T>(out), volume, dt, speed,
+                                             persistent, false, s))
+            return rc;
+        if (ie > ib)
+          if (int rc = plain_patch3_stage<T>(kind, stage, plan, ib, ie - ib, fmk<T>(prev), fmk<T>(mid), fmk<T>(out), volume, dt, speed,
+                                             persistent, true, s))
+            return rc;
       }
     } else if (pe > pb) {
       if (int rc = flush()) return rc;
       // patches and generic tiles of the class in ONE launch where the patches carry most of it (the generic tiles then
       // run the one-tile body behind the persistent patch workgroups); otherwise the generic tiles keep their own launch
       // (the persistent tile kernel where the range covers the plan)
-      const bool mixed = !scatter && qe > qb && static_cast<long long>(pe - pb) * 256 >= static_cast<long long>(qe - qb) * 128;
+      const bool mixed = qe > qb && static_cast<long long>(pe - pb) * 256 >= static_cast<long long>(qe - qb) * 128;
       int rc = plain_patch_stage<T>(kind, stage, plan, pb, pe - pb, qb, mixed ? qe - qb : 0, fmk<T>(prev), fmk<T>(mid), fmk<T>(out), volume,
-                                    dt, speed, whole || persistent_always, static_cast<hipStream_t>(stream));
+                                    dt, speed, persistent, s);
       if (rc == -1)   // (the mixed kernel does not take this plan's generic tiles)
         rc = plain_patch_stage<T>(kind, stage, plan, pb, pe - pb, qb, 0, fmk<T>(prev), fmk<T>(mid), fmk<T>(out), volume, dt, speed,
-                                  whole || persistent_always, static_cast<hipStream_t>(stream));
+                                  persistent, s);
       else if (rc == 0 && mixed)
         qe = qb;   // done
       if (rc != 0) return rc;

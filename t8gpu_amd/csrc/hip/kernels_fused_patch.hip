@@ -26,8 +26,6 @@
 //
 // Persistent and software-pipelined like k_plain_persistent: a workgroup walks patches j, j + n, ... of its XCD's
 // contiguous share with the next patch's loads in flight; two barriers per patch.
-#include <cstdlib>
-
 #include "fused_common.hpp"
 #include "fused_tile_body.hpp"
 #include "patch_common.hpp"
@@ -84,14 +82,10 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
   // the workgroup's it-th patch, role 3 takes the side cells, role 0 the - faces. Fixed to wavefronts 3 and 0 (round 3) the
   // wavefronts of a workgroup carry 730 / 520 / 520 / 620 VALU instructions per patch, and a workgroup's wavefront i runs on
   // SIMD i of its CU: one SIMD of four does 22 % more than the average while the others wait at the barriers.
-  // Measured (same box, scripts/ab_variants.sh): c4 fp64 11 640 -> 11 727 M/s, fp32 and c2 unchanged -- the dispatcher does not pin
-  // wavefront i to SIMD i as strictly as feared. T8GPU_EXP_FIXED_ROLES: experiment builds keep the fixed assignment.
+  // Measured (same box, against an experiment build with the fixed assignment, since removed): c4 fp64 11 640 -> 11 727 M/s,
+  // fp32 and c2 unchanged -- the dispatcher does not pin wavefront i to SIMD i as strictly as feared.
   const int  wv = __builtin_amdgcn_readfirstlane(tid >> 6), ln = tid & 63;
-#ifdef T8GPU_EXP_FIXED_ROLES
-  auto role = [&](int) { return wv == 3 ? 3 : (wv == 0 ? 0 : 1); };
-#else
   auto role = [&](int it) { return (wv + it) & 3; };
-#endif
   const int  hl      = ln;                                     // side-cell lane: cell hl of [-x | +x | -y | +y] x 16
   const bool minus_y = ln >= 16;                               // - face lanes 0-31 of the role-0 wavefront: -x side, then -y side
   const int  m_l = 256 + (minus_y ? 32 : 0) + (ln & 15);       // left operand: the cell across; right: the patch's cell
@@ -103,11 +97,7 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
     double area, vol;   // vol: the patch's uniform element volume where flags has 0x400 (tile_plan.cpp), else unused
   };
   auto load_desc = [&](int tt) {   // scalar load through the constant address space (see k_plain_persistent)
-#ifdef T8GPU_EXP_TILEMOD   // experiment builds only: every patch is one of the first few, all traffic stays in the caches
-    const size_t k = static_cast<size_t>(tile_begin + (tt < tend ? tt : tend - 1) % T8GPU_EXP_TILEMOD);
-#else
     const size_t k = static_cast<size_t>(tt < tend ? tt : tend - 1);
-#endif
     const int8v  r = *reinterpret_cast<const __attribute__((address_space(4))) int8v*>(
         reinterpret_cast<const __attribute__((address_space(4))) char*>(reinterpret_cast<uintptr_t>(P.tile_desc)) + 32 * k);
     Desc d;
@@ -275,12 +265,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_stage(T8g
   if (b < patch_wgs) {
     plain_patch_body<T, KIND, STAGE, NT>(P, patch_begin, patch_count, b, patch_wgs, chunk, prev, src, out, vol, dt, speed);
   } else {
-#ifdef T8GPU_EXP_TILEMOD
-    const int pos = tile_begin + xcd_position(b - patch_wgs, tile_count) % T8GPU_EXP_TILEMOD;
-#else
     const int pos = tile_begin + xcd_position(b - patch_wgs, tile_count);
-#endif
-    plain_tile_body<T, KIND, STAGE, true, 2, false, false, OPEN>(P, pos, prev, src, out, vol, dt, speed);
+    plain_tile_body<T, KIND, STAGE, true, 2, false, OPEN>(P, pos, prev, src, out, vol, dt, speed);
   }
 }
 
@@ -295,40 +281,30 @@ int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch
   // (does this launch run beside another lane's kernels? a plan with ghost-reading tiles, launched in part)
   const bool shared_gpu = plan->n_interior_tiles < plan->ntiles && patch_count + (tile_count > 0 ? tile_count : 0) < plan->ntiles;
   if (!plan->tile_desc) return static_cast<int>(hipErrorInvalidValue);
-  // (the kernel addresses a plane by a 32-bit byte offset, patch_common.hpp: at32)
-  if (plan->n_slots_addressed <= 0 || static_cast<unsigned long long>(plan->n_slots_addressed) * sizeof(T) >= (1ull << 32))
-    return static_cast<int>(hipErrorInvalidValue);
-  const int    nw  = kind == 0 ? kPrimWords : 5;
-  const int    rec = sizeof(T) == 8 ? (nw > 5 ? 10 : 6) : 12;
-  const size_t tab = (sizeof(T) == 8 && kind == 0) ? 2 * kLogTabEntries * sizeof(double) : 0;
-  size_t       lds = sizeof(T) * (static_cast<size_t>(5) * kPatchFF + static_cast<size_t>(rec) * 320) + tab;
+  if (!plan_planes_fit_32bit<T>(plan)) return static_cast<int>(hipErrorInvalidValue);
+  size_t lds = record_lds<T>(kind, static_cast<size_t>(5) * kPatchFF, 320);
   if (tile_count > 0) {
     // what plain_tile_body<T, K, S, true, 2> takes (kernels_fused.hip: the pipelined kernel with a geometry dictionary, two
     // passes of 256 faces), and its LDS window
-    const int  slots = plan->max_slots > 0 ? plan->max_slots : plan->max_elems + plan->max_halo;
-    const bool ok = plan->ell && plan->tile_desc && plan->ell_width >= 8 && plan->ell_width % 8 == 0 && plan->max_elems <= 256 && slots <= 512 &&
-                    plan->max_faces <= 512 && plan->geo_idx && plan->geo_table && plan->n_geo > 0;
-    static const bool off = std::getenv("T8GPU_PATCH_MIXED") && std::getenv("T8GPU_PATCH_MIXED")[0] == '0';   // (measurements)
-    if (!ok || off) return -1;
-    const size_t lds_tile = sizeof(T) * (static_cast<size_t>(nw) * slots + static_cast<size_t>(5) * 256) + (tab ? tab + 16 : 0);
+    if (!plain_tiles_pipelined(plan) || plan->max_faces > 512 || !plan->geo_idx || !plan->geo_table || plan->n_geo <= 0) return -1;
+    const int    nw       = kind == 0 ? kPrimWords : 5;
+    const size_t tab      = lds_log_table<T>(kind);
+    const size_t lds_tile = sizeof(T) * (static_cast<size_t>(nw) * plan_slots(*plan) + static_cast<size_t>(5) * 256) + (tab ? tab + 16 : 0);
     if (lds_tile > lds) lds = lds_tile;
     if (sizeof(T) == 8 && 3 * lds > static_cast<size_t>(156) * 1024) return -1;   // (the kernel lives on three workgroups per CU)
   }
-  const int        cus        = device_cu_count();
-  static const int per_cu_env = env_per_cu("T8GPU_PATCH_WGS");
+  const int cus = device_cu_count();
   if (cus == 0) return static_cast<int>(hipErrorInvalidDevice);
   // persistent = true: the launch covers the whole plan -- as many patch workgroups as stay resident (3 per CU in fp64).
   // persistent = false: a class of a multi-rank stage, launched beside the pack / RCCL / unpack kernels of the exchange: one
   // patch per workgroup, so that slots free up continuously. That costs the patch kernel its software pipeline (13 % at c2
-  // size, 19 % at c4 size: T8GPU_PATCH_PERSISTENT=0 on one rank), but a "polite" persistent grid of two workgroups per CU
-  // for the class launches -- measured in round 3 -- is worse where it matters: rank 3 of the 8-way c4 split with an RCCL
+  // size, 19 % at c4 size, measured on one rank), but a "polite" persistent grid of two workgroups per CU for the class
+  // launches -- measured in round 3 -- is worse where it matters: rank 3 of the 8-way c4 split with an RCCL
   // self-exchange 0.173 -> 0.205 ms/step (profiles/r03_halo_overhead.md); the exchange kernels wait behind resident
   // workgroups that never leave.
-  static const bool never_persistent = std::getenv("T8GPU_PATCH_PERSISTENT") && std::getenv("T8GPU_PATCH_PERSISTENT")[0] == '0';   // (measurements)
-  if (never_persistent) persistent = false;
   // a ghost window (t8gpu_hip.h) is honoured by a workgroup's FIRST patch only (plain_patch_body): one patch per workgroup
   if (plan->ghost_buf || plan->send_map) persistent = false;
-  const int  per_cu    = per_cu_env > 0 ? per_cu_env : (sizeof(T) == 8 ? 3 : 5);
+  const int  per_cu    = sizeof(T) == 8 ? 3 : 5;
   const int  resident  = cus * per_cu;
   // A persistent launch that shares the GPU with the other lane's kernels (the interior launch of a multi-rank stage: the plan
   // has ghost-reading tiles and the range is not the whole plan) must not count on all its workgroups being resident from
@@ -337,11 +313,10 @@ int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch
   // as long (rank 0 of the 2-way c4 split: interior kernel 180 instead of 150 us, profiles/r04_halo_overhead.md). Such
   // launches hand out CHUNKS instead: workgroup j takes `chunk` consecutive patches, with the software pipeline inside the
   // chunk, and the hardware dispatches the chunks as slots free up.
-  static const int chunk_env = std::getenv("T8GPU_PATCH_CHUNK") ? std::atoi(std::getenv("T8GPU_PATCH_CHUNK")) : -1;
   int chunk = 0;
   // (measured, rank of the c4 mesh split 2 / 4 / 8 ways with a self-exchange, ms per step: persistent walk 0.549 / 0.313 / 0.151,
   //  chunks of 2: 0.497 / 0.280 / 0.153, of 3: 0.483 / 0.268 / 0.151, of 4: 0.481 / 0.264 / 0.156, of 6: 0.469 / 0.288 / 0.157)
-  if (persistent && shared_gpu && patch_count >= resident) chunk = chunk_env >= 0 ? chunk_env : 3;
+  if (persistent && shared_gpu && patch_count >= resident) chunk = 3;
   int patch_wgs = (!persistent || patch_count < resident) ? patch_count : resident;
   if (chunk > 0) {   // 8 XCD shares of ceil(count / 8) patches, ceil(share / chunk) workgroups each
     const int share = (patch_count + 7) / 8;
@@ -350,48 +325,19 @@ int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch
   const dim3 grid(patch_wgs + (tile_count > 0 ? tile_count : 0)), block(256);
   // non-temporal stage results / previous-state loads where the stage's planes are a stream for the caches (flux_math.hpp)
   const bool nt = stream_hint(plan->n_slots_addressed, sizeof(T));
-  note_stage_kernel(patch_count + (tile_count > 0 ? tile_count : 0),
-                    tile_count > 0 ? (plan->has_open_faces ? (nt ? "k_plain_stage<T, K, S, true, true>" : "k_plain_stage<T, K, S, false, true>")
-                                                           : (nt ? "k_plain_stage<T, K, S, true>" : "k_plain_stage<T, K, S, false>")) : (nt ? "k_plain_patch<T, K, S, true>" : "k_plain_patch<T, K, S, false>"),
-                    static_cast<int>(sizeof(T)), kind, stage);
-#define T8_PAN(K, S, N)                                                                                                           \
-  do {                                                                                                                            \
-    if (tile_count > 0 && plan->has_open_faces)                                                                                   \
-      hipLaunchKernelGGL((k_plain_stage<T, K, S, N, true>), grid, block, lds, stream, *plan, patch_begin, patch_count, patch_wgs, chunk, tile_begin, \
-                         tile_count, prev, mid, out, volume, dt, speed);                                                          \
-    else if (tile_count > 0)                                                                                                      \
-      hipLaunchKernelGGL((k_plain_stage<T, K, S, N>), grid, block, lds, stream, *plan, patch_begin, patch_count, patch_wgs, chunk, tile_begin, \
-                         tile_count, prev, mid, out, volume, dt, speed);                                                          \
-    else                                                                                                                          \
-      hipLaunchKernelGGL((k_plain_patch<T, K, S, N>), grid, block, lds, stream, *plan, patch_begin, patch_count, chunk, prev, mid, out, volume, dt, \
-                         speed);                                                                                                  \
-  } while (0)
-#define T8_PA(K, S)        \
-  do {                     \
-    if (nt)                \
-      T8_PAN(K, S, true);  \
-    else                   \
-      T8_PAN(K, S, false); \
-  } while (0)
-#define T8_PAS(K)          \
-  do {                     \
-    if (stage == 1)        \
-      T8_PA(K, 1);         \
-    else if (stage == 2)   \
-      T8_PA(K, 2);         \
-    else                   \
-      T8_PA(K, 3);         \
-  } while (0)
-  if (kind == 0)
-    T8_PAS(0);
-  else if (kind == 1)
-    T8_PAS(1);
-  else
-    T8_PAS(2);
-#undef T8_PAS
-#undef T8_PA
-#undef T8_PAN
-  return static_cast<int>(hipGetLastError());
+  return dispatch(
+      [&](auto K, auto S, auto NT, auto MIXED, auto OPEN) {
+        if constexpr (MIXED) {
+          note_stage_kernel<T>(patch_count + tile_count, "k_plain_stage", K, S, NT, OPEN);
+          return launch(&k_plain_stage<T, K, S, NT, OPEN>, grid, block, lds, stream, *plan, patch_begin, patch_count, patch_wgs, chunk,
+                        tile_begin, tile_count, prev, mid, out, volume, dt, speed);
+        } else {
+          note_stage_kernel<T>(patch_count, "k_plain_patch", K, S, NT);
+          return launch(&k_plain_patch<T, K, S, NT>, grid, block, lds, stream, *plan, patch_begin, patch_count, chunk, prev, mid, out, volume,
+                        dt, speed);
+        }
+      },
+      kind, stage, nt, tile_count > 0, tile_count > 0 && plan->has_open_faces);
 }
 
 template int plain_patch_stage<float>(int, int, const T8gpuPlainPlan*, int, int, int, int, FVars<float>, FVars<float>, FVars<float>,

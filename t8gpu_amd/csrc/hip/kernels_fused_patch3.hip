@@ -20,8 +20,6 @@
 // Per 256 cells: 8 + 14 wave-rounds of primitives / fluxes and no face lists (generic 3D tiles: 8 + 8 rounds and a
 // 16-entry list walk per 134 cells). Same flux functions, operand order and summation order as the tile kernels: bitwise
 // their results (tests/test_gpu_patch.py). Persistent and software-pipelined; two barriers per patch.
-#include <cstdlib>
-
 #include "patch_common.hpp"
 #include "stage_kernel_note.hpp"
 
@@ -130,11 +128,7 @@ T8_DEV void plain_patch3_body(const T8gpuPlainPlan& P, int tile_begin, int tile_
     double area, vol;   // vol: the patch's uniform element volume where flags has 0x400 (tile_plan.cpp), else unused
   };
   auto load_desc = [&](int tt) {   // scalar load through the constant address space (see k_plain_persistent)
-#ifdef T8GPU_EXP_TILEMOD
-    const size_t kk = static_cast<size_t>(tile_begin + (tt < tend ? tt : tend - 1) % T8GPU_EXP_TILEMOD);
-#else
     const size_t kk = static_cast<size_t>(tt < tend ? tt : tend - 1);
-#endif
     const int8v  r = *reinterpret_cast<const __attribute__((address_space(4))) int8v*>(
         reinterpret_cast<const __attribute__((address_space(4))) char*>(reinterpret_cast<uintptr_t>(P.tile_desc)) + 32 * kk);
     Desc d;
@@ -368,6 +362,12 @@ __global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_plain_patch3_bo
     plain_patch3_body<T, KIND, STAGE, true, NT>(P, irr_begin, irr_count, b - reg_wgs, static_cast<int>(gridDim.x) - reg_wgs, prev, src, out, vol, dt, speed);
 }
 
+// dynamic LDS of both patch kernels: the flux slots, 512 LDS records (the patch's cells and those across its sides)
+template <class T>
+size_t patch3_lds(int kind) {
+  return record_lds<T>(kind, static_cast<size_t>(5) * kP3FF, 512);
+}
+
 // tiles [tile_begin, tile_begin + tile_count) of tile_order must all be 3D patch tiles. persistent = false: one patch per
 // workgroup (class-split multi-rank launches).
 template <class T>
@@ -376,64 +376,20 @@ int plain_patch3_stage(int kind, int stage, const T8gpuPlainPlan* plan, int tile
   if (tile_count <= 0) return 0;
   if (irregular && (!plan->face_lr || !plan->face_orig)) return static_cast<int>(hipErrorInvalidValue);
   if (!plan->tile_desc) return static_cast<int>(hipErrorInvalidValue);
-  // (the kernel addresses a plane by a 32-bit byte offset, patch_common.hpp: at32)
-  if (plan->n_slots_addressed <= 0 || static_cast<unsigned long long>(plan->n_slots_addressed) * sizeof(T) >= (1ull << 32))
-    return static_cast<int>(hipErrorInvalidValue);
-  const int    nw  = kind == 0 ? kPrimWords : 5;
-  const int    rec = sizeof(T) == 8 ? (nw > 5 ? 10 : 6) : 12;
-  const size_t lds = sizeof(T) * (static_cast<size_t>(5) * kP3FF + static_cast<size_t>(rec) * 512) +
-                     ((sizeof(T) == 8 && kind == 0) ? 2 * kLogTabEntries * sizeof(double) : 0);
-  const int        cus        = device_cu_count();
-  static const int per_cu_env = env_per_cu("T8GPU_PATCH_WGS");
+  if (!plan_planes_fit_32bit<T>(plan)) return static_cast<int>(hipErrorInvalidValue);
+  const int cus = device_cu_count();
   if (cus == 0) return static_cast<int>(hipErrorInvalidDevice);
-  const int  per_cu    = per_cu_env > 0 ? per_cu_env : (sizeof(T) == 8 ? 2 : 3);
-  const int  resident  = cus * per_cu;
+  const int  resident  = cus * (sizeof(T) == 8 ? 2 : 3);
   const int  grid_size = (!persistent || tile_count < resident) ? tile_count : resident;
   const dim3 grid(grid_size), block(512);
   const bool nt = stream_hint(plan->n_slots_addressed, sizeof(T));   // (flux_math.hpp: stream_store)
-  note_stage_kernel(tile_count, irregular ? (nt ? "k_plain_patch3<T, K, S, true, true>" : "k_plain_patch3<T, K, S, true, false>")
-                                          : (nt ? "k_plain_patch3<T, K, S, false, true>" : "k_plain_patch3<T, K, S, false, false>"), static_cast<int>(sizeof(T)), kind,
-                    stage);
-#define T8_P3I(K, S, I, N)                                                                                                     \
-  do {                                                                                                                       \
-    if (lds > 64 * 1024) {                                                                                                   \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_plain_patch3<T, K, S, I, N>),                         \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));                 \
-      if (e != hipSuccess) return static_cast<int>(e);                                                                       \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((k_plain_patch3<T, K, S, I, N>), grid, block, lds, stream, *plan, tile_begin, tile_count, prev, mid, out, volume, \
-                       dt, speed);                                                                                           \
-  } while (0)
-#define T8_P3(K, S)                  \
-  do {                               \
-    if (irregular && nt)             \
-      T8_P3I(K, S, true, true);      \
-    else if (irregular)              \
-      T8_P3I(K, S, true, false);     \
-    else if (nt)                     \
-      T8_P3I(K, S, false, true);     \
-    else                             \
-      T8_P3I(K, S, false, false);    \
-  } while (0)
-#define T8_P3S(K)          \
-  do {                     \
-    if (stage == 1)        \
-      T8_P3(K, 1);         \
-    else if (stage == 2)   \
-      T8_P3(K, 2);         \
-    else                   \
-      T8_P3(K, 3);         \
-  } while (0)
-  if (kind == 0)
-    T8_P3S(0);
-  else if (kind == 1)
-    T8_P3S(1);
-  else
-    T8_P3S(2);
-#undef T8_P3S
-#undef T8_P3
-#undef T8_P3I
-  return static_cast<int>(hipGetLastError());
+  return dispatch(
+      [&](auto K, auto S, auto IRR, auto NT) {
+        note_stage_kernel<T>(tile_count, "k_plain_patch3", K, S, IRR, NT);
+        return launch(&k_plain_patch3<T, K, S, IRR, NT>, grid, block, patch3_lds<T>(kind), stream, *plan, tile_begin, tile_count, prev, mid,
+                      out, volume, dt, speed);
+      },
+      kind, stage, irregular, nt);
 }
 
 // Regular patches [reg_begin, +reg_count) and irregular patches [irr_begin, +irr_count) in one persistent launch. Returns -1 where
@@ -442,11 +398,9 @@ int plain_patch3_stage(int kind, int stage, const T8gpuPlainPlan* plan, int tile
 template <class T>
 int plain_patch3_both_stage(int kind, int stage, const T8gpuPlainPlan* plan, int reg_begin, int reg_count, int irr_begin, int irr_count,
                             FVars<T> prev, FVars<T> mid, FVars<T> out, const T* volume, T dt, T* speed, hipStream_t stream) {
-  static const bool off = std::getenv("T8GPU_PATCH3_BOTH") && std::getenv("T8GPU_PATCH3_BOTH")[0] == '0';   // (measurements)
-  if (off || reg_count <= 0 || irr_count <= 0) return -1;
+  if (reg_count <= 0 || irr_count <= 0) return -1;
   if (!plan->face_lr || !plan->face_orig || !plan->tile_desc) return static_cast<int>(hipErrorInvalidValue);
-  if (plan->n_slots_addressed <= 0 || static_cast<unsigned long long>(plan->n_slots_addressed) * sizeof(T) >= (1ull << 32))
-    return static_cast<int>(hipErrorInvalidValue);
+  if (!plan_planes_fit_32bit<T>(plan)) return static_cast<int>(hipErrorInvalidValue);
   const int cus = device_cu_count();
   if (cus == 0) return static_cast<int>(hipErrorInvalidDevice);
   const int resident = cus * (sizeof(T) == 8 ? 2 : 3);
@@ -456,49 +410,15 @@ int plain_patch3_both_stage(int kind, int stage, const T8gpuPlainPlan* plan, int
   int reg_wgs = static_cast<int>(resident * w_r / (w_r + w_i) / 8.0 + 0.5) * 8;
   if (reg_wgs < 8) reg_wgs = 8;
   if (reg_wgs > resident - 8) reg_wgs = resident - 8;
-  const int    nw  = kind == 0 ? kPrimWords : 5;
-  const int    rec = sizeof(T) == 8 ? (nw > 5 ? 10 : 6) : 12;
-  const size_t lds = sizeof(T) * (static_cast<size_t>(5) * kP3FF + static_cast<size_t>(rec) * 512) +
-                     ((sizeof(T) == 8 && kind == 0) ? 2 * kLogTabEntries * sizeof(double) : 0);
   const dim3 grid(resident), block(512);
   const bool nt = stream_hint(plan->n_slots_addressed, sizeof(T));   // (flux_math.hpp: stream_store)
-  note_stage_kernel(reg_count + irr_count, nt ? "k_plain_patch3_both<T, K, S, true>" : "k_plain_patch3_both<T, K, S, false>", static_cast<int>(sizeof(T)), kind, stage);
-#define T8_P3BN(K, S, N)                                                                                                         \
-  do {                                                                                                                       \
-    if (lds > 64 * 1024) {                                                                                                   \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_plain_patch3_both<T, K, S, N>),                       \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));                 \
-      if (e != hipSuccess) return static_cast<int>(e);                                                                       \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((k_plain_patch3_both<T, K, S, N>), grid, block, lds, stream, *plan, reg_begin, reg_count, reg_wgs, irr_begin, irr_count, \
-                       prev, mid, out, volume, dt, speed);                                                                   \
-  } while (0)
-#define T8_P3B(K, S)        \
-  do {                      \
-    if (nt)                 \
-      T8_P3BN(K, S, true);  \
-    else                    \
-      T8_P3BN(K, S, false); \
-  } while (0)
-#define T8_P3BS(K)         \
-  do {                     \
-    if (stage == 1)        \
-      T8_P3B(K, 1);        \
-    else if (stage == 2)   \
-      T8_P3B(K, 2);        \
-    else                   \
-      T8_P3B(K, 3);        \
-  } while (0)
-  if (kind == 0)
-    T8_P3BS(0);
-  else if (kind == 1)
-    T8_P3BS(1);
-  else
-    T8_P3BS(2);
-#undef T8_P3BS
-#undef T8_P3B
-#undef T8_P3BN
-  return static_cast<int>(hipGetLastError());
+  return dispatch(
+      [&](auto K, auto S, auto NT) {
+        note_stage_kernel<T>(reg_count + irr_count, "k_plain_patch3_both", K, S, NT);
+        return launch(&k_plain_patch3_both<T, K, S, NT>, grid, block, patch3_lds<T>(kind), stream, *plan, reg_begin, reg_count, reg_wgs,
+                      irr_begin, irr_count, prev, mid, out, volume, dt, speed);
+      },
+      kind, stage, nt);
 }
 
 template int plain_patch3_both_stage<float>(int, int, const T8gpuPlainPlan*, int, int, int, int, FVars<float>, FVars<float>, FVars<float>, const float*,

@@ -96,11 +96,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_persisten
   typedef int int8v __attribute__((ext_vector_type(8)));
   auto load_desc = [&](int tt) {
     const int last = tend - 1;
-#ifdef T8GPU_EXP_TILEMOD   // experiment builds only: every tile is one of the first few, all traffic stays in the caches
-    const size_t k = static_cast<size_t>((tt < tend ? tt : last) % T8GPU_EXP_TILEMOD);
-#else
     const size_t k = static_cast<size_t>(tt < tend ? tt : last);   // (past the end: a valid tile, never used)
-#endif
     const int8v r = *reinterpret_cast<const __attribute__((address_space(4))) int8v*>(
         reinterpret_cast<const __attribute__((address_space(4))) char*>(reinterpret_cast<uintptr_t>(P.tile_desc)) + 32 * k);
     TileDesc d;
@@ -230,11 +226,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_persisten
           // asm statements keep them real branches -- as selects they would cost what they save).
           const int  code   = static_cast<int>(graw >> 13);
           const int  wcode  = __builtin_amdgcn_readfirstlane(code);
-#ifdef T8GPU_EXP_NOAXIS   // experiment builds only: always the general rotation
-          const bool shared = false;
-#else
           const bool shared = wcode < 6 && __all(code == wcode);
-#endif
           const T    sg     = (wcode & 1) ? T(1) : T(-1);
           T          uL, vL, wL, uR, vR, wR, area, n[3], t1[3], t2[3];
           if (shared) {
@@ -270,13 +262,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_persisten
             wR = wL;
           }
           T f[5];
-#ifdef T8GPU_EXP_NOMATH
-          f[0] = L.rho + R.rho + uL; f[1] = vL + wL + uR; f[2] = vR + wR + L.beta + R.beta; f[3] = L.lrho + R.lrho;
-          f[4] = L.p + R.p + L.lbeta + R.lbeta + L.v0 + R.v0 + area;
-          spd = f[0];
-#else
           kepes_core<T>(L, R, uL, vL, wL, uR, vR, wR, area, f, spd);
-#endif
           g[0] = f[0];
           g[4] = f[4];
           if (shared) {
@@ -352,10 +338,7 @@ bool plain_persistent_accepts(int kind, const T8gpuPlainPlan* plan, int tile_cou
   if (off || plan->has_open_faces || !plan->tile_desc || !plan->ell || (plan->ell_width != 8 && plan->ell_width != 16 && plan->ell_width != 24) || !plan->geo_idx || !plan->geo_table || plan->n_geo <= 0 || plan->n_geo > 128 ||
       plan->max_elems > 256 || slots <= 0 || slots > 512 || plan->max_faces > 512)
     return false;
-  const int    nw  = kind == 0 ? kPrimWords : 5;
-  const int    rec = sizeof(T) == 8 ? (nw > 5 ? 10 : 6) : 12;
-  const size_t lds = sizeof(T) * (static_cast<size_t>(5) * 512 + static_cast<size_t>(12) * plan->n_geo + static_cast<size_t>(rec) * slots) +
-                     ((sizeof(T) == 8 && kind == 0) ? 2 * kLogTabEntries * sizeof(double) : 0);
+  const size_t lds = record_lds<T>(kind, static_cast<size_t>(5) * 512 + static_cast<size_t>(12) * plan->n_geo, slots);
   if (lds > 64 * 1024) return false;
   // fp64: the kernel lives on three workgroups per CU. 3 x 53.1 KB (a 3D tile of 376 slots) is nominally inside the 160 KB
   // and yet only two become resident (c5 on 512-face tiles: 3 950 against 4 110 M/s for the one-tile kernel); with a margin
@@ -387,35 +370,14 @@ int plain_persistent_stage(int kind, int stage, const T8gpuPlainPlan* plan, int 
   if (!plain_persistent_accepts<T>(kind, plan, tile_count, &lds, &resident)) return -1;
   const int  grid_size = tile_count < resident ? tile_count : resident;
   const dim3 grid(grid_size), block(256);
-  note_stage_kernel(tile_count, plan->ell_width == 8 ? "k_plain_persistent<T, K, S, 1>" : "k_plain_persistent<T, K, S, 3>", static_cast<int>(sizeof(T)), kind,
-                    stage);
-#define T8_PE(K, S, C) hipLaunchKernelGGL((k_plain_persistent<T, K, S, C>), grid, block, lds, stream, *plan, tile_begin, tile_count, prev, mid, out, volume, dt, speed)
-#define T8_P(K, S)          \
-  do {                      \
-    if (plan->ell_width == 8) \
-      T8_PE(K, S, 1);       \
-    else                    \
-      T8_PE(K, S, 3);       \
-  } while (0)
-#define T8_PS(K)             \
-  do {                       \
-    if (stage == 1)          \
-      T8_P(K, 1);            \
-    else if (stage == 2)     \
-      T8_P(K, 2);            \
-    else                     \
-      T8_P(K, 3);            \
-  } while (0)
-  if (kind == 0)
-    T8_PS(0);
-  else if (kind == 1)
-    T8_PS(1);
-  else
-    T8_PS(2);
-#undef T8_PS
-#undef T8_P
-#undef T8_PE
-  return static_cast<int>(hipGetLastError());
+  return dispatch(
+      [&](auto K, auto S, auto ELL8) {
+        constexpr int C = ELL8 ? 1 : 3;   // ELL chunks of 8 entries per element: 1, or (16 / 24 entries) up to 3
+        note_stage_kernel<T>(tile_count, "k_plain_persistent", K, S, C);
+        return launch(&k_plain_persistent<T, K, S, C>, grid, block, lds, stream, *plan, tile_begin, tile_count, prev, mid, out, volume, dt,
+                      speed);
+      },
+      kind, stage, plan->ell_width == 8);
 }
 
 template int plain_persistent_stage<float>(int, int, const T8gpuPlainPlan*, int, int, FVars<float>, FVars<float>, FVars<float>,

@@ -36,6 +36,7 @@
 #include <cstdlib>
 
 #include "flux_math.hpp"
+#include "fused_common.hpp"
 #include "stage_kernel_note.hpp"
 #include "t8gpu_hip.h"
 
@@ -93,12 +94,6 @@ struct CellData {  // what a flux evaluation needs from one cell: primitives (KE
 template <class T, int KIND>
 T8_DEV CellData<T, KIND> cell_from_state(const T s[5]) {
   CellData<T, KIND> c;
-#ifdef T8GPU_EXP_NOMATH   // experiment builds only: loads, LDS traffic, barriers and stores as in the product, no arithmetic
-  if (KIND == 0) {
-    c.v[0] = s[0]; c.v[1] = s[1]; c.v[2] = s[2]; c.v[3] = s[3]; c.v[4] = s[4]; c.v[5] = s[0]; c.v[6] = s[1]; c.v[7] = s[2]; c.v[8] = s[3];
-    return c;
-  }
-#endif
   if (KIND == 0) {
     // fp64: table-driven logarithm, the 2 KB table read from global memory (it stays in the L1 / K$; an LDS copy per
     // one-wave workgroup would cost the kernel a wavefront per SIMD). fp32: hardware log2.
@@ -115,13 +110,6 @@ T8_DEV CellData<T, KIND> cell_from_state(const T s[5]) {
 // area-scaled xyz flux from L to R through a face with unit normal n
 template <class T, int KIND>
 T8_DEV void cell_flux(const CellData<T, KIND>& L, const CellData<T, KIND>& R, bool wall, int axis, bool positive, T area, T g[5]) {
-#ifdef T8GPU_EXP_NOMATH
-  if (KIND == 0) {
-    g[0] = L.v[0] + R.v[0] + area; g[1] = L.v[1] + R.v[1] + L.v[5]; g[2] = L.v[2] + R.v[2] + R.v[6]; g[3] = L.v[3] + R.v[3] + L.v[7];
-    g[4] = L.v[4] + R.v[4] + R.v[8] + T(axis + (wall ? 1 : 0) + (positive ? 2 : 0));
-    return;
-  }
-#endif
   if (KIND == 0) {
     T spd;
     Prim<T> a, b;
@@ -270,9 +258,6 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
   const T   edge    = (RANK == 3 ? t8_cbrt(vol) : t8_sqrt(vol)) / T(4);
   const T   surface = RANK == 3 ? edge * edge : edge;
   int       npass   = nbf;  // generic passes run until the busiest block of the wave is done
-#ifdef T8GPU_EXP_NOGENERIC   // experiment builds only (wrong results): no generic passes / no far cells of the + faces
-  npass = 0;
-#endif
   if (RANK == 2) {
     npass = max(npass, __shfl_xor(npass, 16, 64));
     npass = max(npass, __shfl_xor(npass, 32, 64));
@@ -292,11 +277,7 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
                     fz = RANK == 3 ? plus_face<T>(brec[3], live) : PlusFace<T>{false, false, 0, 0, T(0)};
   // lane cl < PF fetches far cell `cl % SF` of the block's +(cl / SF) face
   const int  pd = cl / SF, psub = cl % SF;
-#ifdef T8GPU_EXP_NOFAR
-  const bool p_on = false;
-#else
   const bool p_on = cl < PF && (pd == 0 ? fx.on : (pd == 1 ? fy.on : fz.on));
-#endif
   // (the tangential strides of side pd: 4 / 16 across x, 1 / 16 across y, 1 / 4 across z)
   const int  pla = pd == 0 ? 2 : 0, plb = pd == 2 ? 2 : 4, pti = psub & 3, ptj = RANK == 3 ? psub >> 2 : 0;
   T          pfar[5];
@@ -319,11 +300,7 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
   const CellData<T, KIND> mine = cell_from_state<T, KIND>(s0);
 #pragma unroll
   for (int w = 0; w < NW; w++) pe[(w) * PEL + (c)] = mine.v[w];
-#ifdef T8GPU_EXP_NOFAR
-  if (false) {
-#else
   if (cl < PF) {
-#endif
     const CellData<T, KIND> far = cell_from_state<T, KIND>(pfar);
 #pragma unroll
     for (int w = 0; w < NW; w++) pe[(w) * PEL + (64 + (c / S) * PF + cl)] = far.v[w];
@@ -479,11 +456,7 @@ __global__ __launch_bounds__(64) void k_subgrid_fused(T8gpuSubgridPlan P, int bl
   __shared__ T xb[5 * 64];    // flux exchange buffer (+ passes: per cell; generic passes: [slot * SF + sub-face])
   // (RANK 3: the block index is wave-uniform -- blockIdx arithmetic only --, so the per-block loads (volume, face lists,
   //  face records) stay scalar loads and their branches scalar branches)
-#ifdef T8GPU_EXP_TILEMOD   // experiment builds only: every wavefront works on one of the first few blocks (no HBM traffic)
-  const int pos_base = sg_xcd_position(blockIdx.x, gridDim.x) % T8GPU_EXP_TILEMOD;
-#else
   const int pos_base = sg_xcd_position(blockIdx.x, gridDim.x);
-#endif
   subgrid_block<T, KIND, STAGE, RANK, EARLY_PREV, WIDE, false>(P, block_begin, block_count, pos_base, threadIdx.x, prev, src, out, volumes,
                                                                dt, pe, xb);
 }
@@ -512,11 +485,7 @@ __global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_subgrid_family(
   constexpr int FAM_WORDS = NW * 704 + 3 * 5 * 64 + 5 * 512;       // this kernel's arrays
   constexpr int BLK_WORDS = NW * 112 + 5 * 64;                      // one wavefront of the block algorithm
   constexpr int RESTB     = sizeof(T) == 8 ? 4 : 8;                 // leftover blocks per workgroup (fp64: LDS for 4 only)
-#ifdef T8GPU_EXP_FAM_PAD   // experiment builds: extra LDS words, to see how many workgroups per CU the kernel really gets
-  __shared__ T lds[(FAM_WORDS > RESTB * BLK_WORDS ? FAM_WORDS : RESTB * BLK_WORDS) + T8GPU_EXP_FAM_PAD];
-#else
   __shared__ T lds[FAM_WORDS > RESTB * BLK_WORDS ? FAM_WORDS : RESTB * BLK_WORDS];
-#endif
   const int tid = threadIdx.x, c = tid & 63;
   const int w   = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: the per-block reads below stay scalar
   // The workgroups behind the cubes take the blocks outside every cube (the coarse side of 2:1 interfaces and their
@@ -855,41 +824,18 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
   // one launch of the block kernel over records `pl.block_rec[begin, begin + count)`
   auto blocks = [&](const T8gpuSubgridPlan& pl, int begin, int count) {
     const dim3 grid(pl.rank == 3 ? count : (count + 3) / 4), block(64);
-    {
-      char pat[96];
-      std::snprintf(pat, sizeof(pat), "k_subgrid_fused<T, K, S, %d, %s, %s>", pl.rank == 3 ? 3 : 2, early ? "true" : "false", wide ? "true" : "false");
-      note_stage_kernel(count, pat, static_cast<int>(sizeof(T)), kind, stage);
-    }
-#define T8_SG(K, S, R)                                                                                                     \
-  do {                                                                                                                     \
-    if (wide)                                                                                                              \
-      hipLaunchKernelGGL((k_subgrid_fused<T, K, S, R, early, true>), grid, block, 0, s, pl, begin, count, smk<T>(prev),   \
-                         smk<T>(mid), smk<T>(out), volumes, dt);                                                           \
-    else                                                                                                                   \
-      hipLaunchKernelGGL((k_subgrid_fused<T, K, S, R, early, false>), grid, block, 0, s, pl, begin, count, smk<T>(prev),  \
-                         smk<T>(mid), smk<T>(out), volumes, dt);                                                           \
-  } while (0)
-#define T8_SGR(K, S)  \
-  do {                \
-    if (pl.rank == 3) \
-      T8_SG(K, S, 3); \
-    else              \
-      T8_SG(K, S, 2); \
-  } while (0)
-    if (kind == 0) {
-      if (stage == 1) T8_SGR(0, 1); else if (stage == 2) T8_SGR(0, 2); else T8_SGR(0, 3);
-    } else if (kind == 1) {
-      if (stage == 1) T8_SGR(1, 1); else if (stage == 2) T8_SGR(1, 2); else T8_SGR(1, 3);
-    } else {
-      if (stage == 1) T8_SGR(2, 1); else if (stage == 2) T8_SGR(2, 2); else T8_SGR(2, 3);
-    }
-#undef T8_SGR
-#undef T8_SG
+    return dispatch(
+        [&](auto K, auto S, auto RANK3, auto WIDE) {
+          constexpr int R = RANK3 ? 3 : 2;
+          note_stage_kernel<T>(count, "k_subgrid_fused", K, S, R, early, WIDE);
+          return launch(&k_subgrid_fused<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
+                        smk<T>(out), volumes, dt);
+        },
+        kind, stage, pl.rank == 3, wide);
   };
   // A launch that covers the whole plan of a 3D mesh: 2x2x2 cubes of same-level blocks through the family kernel, the
-  // other blocks through the block kernel (T8GPU_SG_FAMILY=0: every block through the block kernel -- same bits).
-  // (T8GPU_SG_FAMILY=0: every block through the block kernel -- same bits. Measured on c3: KEPES fp32 +6 %, fp64 +8 %,
-  //  HLL fp32 +9 %, fp64 +3 %, HLLC fp32 +5 %.)
+  // other blocks through the block kernel (T8GPU_SG_FAMILY=0: every block through the block kernel -- same bits. Measured
+  // on c3: KEPES fp32 +6 %, fp64 +8 %, HLL fp32 +9 %, fp64 +3 %, HLLC fp32 +5 %.)
   static const bool fam_off = std::getenv("T8GPU_SG_FAMILY") && std::getenv("T8GPU_SG_FAMILY")[0] == '0';
   // The cubes consist of deep interior blocks only, and rest_rec lists the other blocks in block_order order, so with
   // nf = 8 * n_families: positions [0, n_deep) = the cubes + rest_rec[0, n_deep - nf), and position p >= n_deep = rest_rec[p - nf].
@@ -903,11 +849,9 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
     if (have_fam && block_begin >= plan->n_deep_blocks) {
       T8gpuSubgridPlan rest = *plan;
       rest.block_rec        = plan->rest_rec;
-      blocks(rest, block_begin - nf, block_count);
-    } else {
-      blocks(*plan, block_begin, block_count);
+      return blocks(rest, block_begin - nf, block_count);
     }
-    return static_cast<int>(hipGetLastError());
+    return blocks(*plan, block_begin, block_count);
   }
   // non-temporal stage results / previous-state loads where the stage's planes are a stream for the caches (flux_math.hpp)
   const bool nt = stream_hint(cells, sizeof(T));
@@ -918,43 +862,14 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
   // per square, four leftover blocks per wavefront
   const int  restb = plan->rank == 3 ? (sizeof(T) == 8 ? 4 : 8) : 4;   // (k_subgrid_family: RESTB)
   const dim3 grid(plan->n_families + (n_rest_here + restb - 1) / restb), block(plan->rank == 3 ? 512 : 64);
-  {
-    char pat[96];
-    std::snprintf(pat, sizeof(pat), "%s<T, K, S, %s, %s>", plan->rank == 3 ? "k_subgrid_family" : "k_subgrid_family2", wide ? "true" : "false", nt ? "true" : "false");
-    note_stage_kernel(block_count, pat, static_cast<int>(sizeof(T)), kind, stage);
-  }
-#define T8_FMN(K, S, N)                                                                                                         \
-  do {                                                                                                                          \
-    if (plan->rank == 3 && wide)                                                                                                \
-      hipLaunchKernelGGL((k_subgrid_family<T, K, S, true, N>), grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out),   \
-                         volumes, dt);                                                                                          \
-    else if (plan->rank == 3)                                                                                                   \
-      hipLaunchKernelGGL((k_subgrid_family<T, K, S, false, N>), grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out),  \
-                         volumes, dt);                                                                                          \
-    else if (wide)                                                                                                              \
-      hipLaunchKernelGGL((k_subgrid_family2<T, K, S, true, N>), grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out),  \
-                         volumes, dt);                                                                                          \
-    else                                                                                                                        \
-      hipLaunchKernelGGL((k_subgrid_family2<T, K, S, false, N>), grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), \
-                         volumes, dt);                                                                                          \
-  } while (0)
-#define T8_FM(K, S)        \
-  do {                     \
-    if (nt)                \
-      T8_FMN(K, S, true);  \
-    else                   \
-      T8_FMN(K, S, false); \
-  } while (0)
-  if (kind == 0) {
-    if (stage == 1) T8_FM(0, 1); else if (stage == 2) T8_FM(0, 2); else T8_FM(0, 3);
-  } else if (kind == 1) {
-    if (stage == 1) T8_FM(1, 1); else if (stage == 2) T8_FM(1, 2); else T8_FM(1, 3);
-  } else {
-    if (stage == 1) T8_FM(2, 1); else if (stage == 2) T8_FM(2, 2); else T8_FM(2, 3);
-  }
-#undef T8_FM
-#undef T8_FMN
-  return static_cast<int>(hipGetLastError());
+  return dispatch(
+      [&](auto K, auto S, auto RANK3, auto WIDE, auto NT) {
+        const char* name   = RANK3 ? "k_subgrid_family" : "k_subgrid_family2";
+        const auto  kernel = RANK3 ? &k_subgrid_family<T, K, S, WIDE, NT> : &k_subgrid_family2<T, K, S, WIDE, NT>;
+        note_stage_kernel<T>(block_count, name, K, S, WIDE, NT);
+        return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
+      },
+      kind, stage, plan->rank == 3, wide, nt);
 }
 
 }  // namespace t8gpu_hip

@@ -21,6 +21,12 @@ T8_DEV T& at32(T* base, unsigned i) {
   return *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + i * static_cast<unsigned>(sizeof(T)));
 }
 
+// may the patch kernels address this plan's planes through at32? (every plane shorter than 4 GiB)
+template <class T>
+bool plan_planes_fit_32bit(const T8gpuPlainPlan* plan) {
+  return plan->n_slots_addressed > 0 && static_cast<unsigned long long>(plan->n_slots_addressed) * sizeof(T) < (1ull << 32);
+}
+
 constexpr int kPatchFF = 544;   // flux slots per variable: 256 +x faces, 256 +y faces, 16 -x side, 16 -y side
 
 T8_DEV int patch_morton(int i, int j) {
@@ -59,13 +65,7 @@ T8_DEV void patch_face(bool y, const T* wl, const T* wr, T area, T g[5], T& spd)
     T uL, vL, wL, uR, vR, wR;
     frame_in<T>(y, L.vx, L.vy, L.vz, uL, vL, wL);
     frame_in<T>(y, R.vx, R.vy, R.vz, uR, vR, wR);
-#ifdef T8GPU_EXP_NOMATH
-    f[0] = L.rho + R.rho + uL; f[1] = vL + wL + uR; f[2] = vR + wR + L.beta + R.beta; f[3] = L.lrho + R.lrho;
-    f[4] = L.p + R.p + L.lbeta + R.lbeta + L.v0 + R.v0 + area;
-    spd = f[0];
-#else
     kepes_core<T>(L, R, uL, vL, wL, uR, vR, wR, area, f, spd);
-#endif
   } else {
     T a[5], b[5];
     a[0] = wl[0]; a[4] = wl[4];

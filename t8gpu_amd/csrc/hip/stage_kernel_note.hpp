@@ -4,9 +4,7 @@
 #ifndef T8GPU_HIP_STAGE_KERNEL_NOTE_HPP
 #define T8GPU_HIP_STAGE_KERNEL_NOTE_HPP
 
-#include <cctype>
 #include <cstdio>
-#include <cstring>
 
 namespace t8gpu_hip {
 
@@ -18,35 +16,22 @@ StageKernelNote& stage_kernel_note();   // (kernels_compat.hip)
 
 inline void stage_kernel_note_reset() { stage_kernel_note().weight = -1; }
 
-// pattern: the kernel as rocprofv3 prints it, with the identifiers T, K, S for float type, flux kind and stage, e.g.
-// "k_plain_stage<T, K, S>"; weight: the work units (tiles, blocks) of this launch -- the heaviest launch of a call stays.
-inline void note_stage_kernel(long long weight, const char* pattern, int tsize, int kind, int stage) {
+inline int stage_kernel_arg(char* s, size_t n, bool v) { return std::snprintf(s, n, ", %s", v ? "true" : "false"); }
+inline int stage_kernel_arg(char* s, size_t n, int v) { return std::snprintf(s, n, ", %d", v); }
+
+// Notes the launch of kernel<T, args...> (args: the launch's compile-time ints and bools, e.g. dispatch()'s constants) by
+// its name as rocprofv3 prints it -- the demangled symbol without namespace and parameter list: float / double, decimal
+// ints, true / false, separated by ", ". weight: the work units (tiles, blocks) of this launch -- the heaviest launch of a
+// call stays.
+template <class T, class... A>
+void note_stage_kernel(long long weight, const char* kernel, A... args) {
   StageKernelNote& n = stage_kernel_note();
   if (weight <= n.weight) return;
-  n.weight   = weight;
-  size_t o   = 0;
-  auto   put = [&](const char* s) {
-    for (; *s && o + 1 < sizeof(n.name); s++) n.name[o++] = *s;
-  };
-  for (const char* p = pattern; *p;) {
-    const bool ident_before = p > pattern && (std::isalnum(static_cast<unsigned char>(p[-1])) || p[-1] == '_');
-    const bool ident_after  = std::isalnum(static_cast<unsigned char>(p[1])) || p[1] == '_';
-    char       num[16];
-    if (!ident_before && !ident_after && (*p == 'T' || *p == 'K' || *p == 'S')) {
-      if (*p == 'T') {
-        put(tsize == 8 ? "double" : "float");
-      } else {
-        std::snprintf(num, sizeof(num), "%d", *p == 'K' ? kind : stage);
-        put(num);
-      }
-      p++;
-    } else {
-      const char c[2] = {*p, 0};
-      put(c);
-      p++;
-    }
-  }
-  n.name[o] = 0;
+  n.weight     = weight;
+  const size_t cap = sizeof(n.name);
+  size_t       o   = std::snprintf(n.name, cap, "%s<%s", kernel, sizeof(T) == 8 ? "double" : "float");
+  ((o += o < cap ? stage_kernel_arg(n.name + o, cap - o, args) : 0), ...);
+  if (o < cap) std::snprintf(n.name + o, cap - o, ">");
 }
 
 }  // namespace t8gpu_hip
