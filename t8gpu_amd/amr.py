@@ -14,24 +14,6 @@ from . import hip
 from .solver import FLUXES, PlainSolver
 
 
-def _inherited_plan_options(solver):
-    """Tile caps and patch forms of the adapted mesh's plan: those the previous plan settled on (fused.PlainPlan may build a
-    plan twice to find out which kernel a mesh class gets; an adaptive run should pay for that once, not at every adapt)."""
-    plan = getattr(solver, "plan", None)
-    if plan is None:
-        return None
-    opts = {}
-    if getattr(plan, "auto_fcap", None) is not None:
-        opts["fcap"] = plan.auto_fcap
-        opts["fcap_elements"] = getattr(plan, "auto_fcap_elements", None)     # (the mesh size the cap was chosen for)
-    if getattr(plan, "auto_irregular", None) is not None:
-        opts["irregular"] = plan.auto_irregular
-        # (like the cap, the patch form is decided again once the mesh size has changed by more than a factor two since it was
-        #  chosen: fused.PlainPlan drops both under that rule)
-        opts["fcap_elements"] = getattr(plan, "auto_fcap_elements", None)
-    return opts or None
-
-
 def refinement_criteria(solver):
     """estimate_gradient + compute_refinement_criteria (solver.cu:245-263); returns a device tensor [N]."""
     s = hip.stream_ptr()
@@ -59,8 +41,8 @@ def adapt(solver, threshold=10.0, min_level=1, max_level=4, family_members_avera
     new_part = new_mesh.partition(0, 1, subgrid=False, normal_dim=part.normal_dim)
     t2 = time.perf_counter()
     dim = mesh.dim if volume_dim is None else volume_dim
-    new = PlainSolver(new_part, solver.dtype, flux_kind=solver.kind, mode=solver.mode,
-                      state="zeros", plan_options=_inherited_plan_options(solver), inflow_states=solver.inflow_states)
+    new = PlainSolver(new_part, solver.dtype, flux_kind=solver.kind, mode=solver.mode, state="zeros",
+                      plan_options=None if solver.plan is None else solver.plan.inherited_options(), inflow_states=solver.inflow_states)
     t3 = time.perf_counter()
     new.next, new.prev = solver.next, solver.prev
     ad = torch.from_numpy(adapt_data).cuda()
@@ -81,68 +63,45 @@ def adapt(solver, threshold=10.0, min_level=1, max_level=4, family_members_avera
     return new, marks, adapt_data
 
 
-class PartitionedAdapt:
-    """adapt() + partition() for an SFC-partitioned plain-element run (MeshManager::adapt followed by
-    MeshManager::partition, t8gpu/mesh/mesh_manager.inl:196-330, 645-723), one rank per GPU.
+class _Repartition:
+    """The forest step and message plan of an SFC-partitioned adapt (MeshManager::adapt followed by MeshManager::partition),
+    one rank per GPU. Every rank holds the (cheap) forest description, so the forest operations are replicated and only the
+    element payloads travel: marks that would split a family over two ranks are dropped, the forest is adapted, each rank
+    transfers its own elements on the device into temporary planes and ships contiguous runs of them (one message per
+    destination) to their owners in the new equal split -- the reference instead lets the new owner PULL through CUDA-IPC
+    pointers (partition_data<<<>>>, mesh_manager.inl:626-643). Split in prepare (the constructor) / transport / finish so that
+    the transport can be RCCL (torch.distributed P2P), gloo (CPU tests) or a loopback (one-GPU tests). A subclass packs and
+    unpacks its payload."""
 
-    Every rank holds the (cheap) forest description, so the forest operations are replicated and only the
-    element payloads travel: each rank adapts its own elements on the device, then ships contiguous runs of
-    the adapted elements (5 variables + volume, one message per destination) to their owners in the new
-    equal split -- the reference instead lets the new owner PULL through CUDA-IPC pointers
-    (partition_data<<<>>>, mesh_manager.inl:626-643). Split in prepare / transport / finish so that the
-    transport can be RCCL (torch.distributed P2P), gloo (CPU tests) or a loopback (one-GPU tests).
-    """
-
-    def __init__(self, solver, all_criteria, threshold=10.0, min_level=1, max_level=4, family_members_averaged=4):
+    def __init__(self, solver, marks):
         part = solver.part
         self.solver, self.rank, self.world = solver, part.rank, part.nranks
         mesh = part.mesh
         old_off = mesh.partition_offsets(self.world)
-        marks = mesh.marks_from_criteria(all_criteria, threshold, min_level, max_level, family_members_averaged)
-        marks = mesh.unmark_split_families(marks, old_off[1:-1])
-        self.marks = marks
-        self.new_mesh, adapt_data = mesh.adapt(marks)
-        n_new = self.new_mesh.num_elements
+        self.marks = mesh.unmark_split_families(marks, old_off[1:-1])
+        self.new_mesh, adapt_data = mesh.adapt(self.marks)
         # new elements made from rank p's old elements: [have_off[p], have_off[p+1])
         self.have_off = np.searchsorted(adapt_data[:-1], old_off, side="left").astype(np.int64)
-        self.have_off[-1] = n_new
+        self.have_off[-1] = self.new_mesh.num_elements
         self.new_off = self.new_mesh.partition_offsets(self.world)
         a, b = int(self.have_off[self.rank]), int(self.have_off[self.rank + 1])
         self.n_have = b - a
-        dtype, dev = solver.dtype, solver.planes.device
-        # 1. local data transfer (adapt_variables_and_volume) into 6 temporary planes
-        self.tmp = torch.zeros((6, max(1, self.n_have)), dtype=dtype, device=dev)
-        ad_local = torch.from_numpy((adapt_data[a:b + 1] - old_off[self.rank]).astype(np.int32)).to(dev)
-        if self.n_have:
-            if dev.type == "cuda":
-                hip.call("t8gpu_hip_adapt_variables_and_volume", dtype, self.n_have, mesh.dim, hip.ptr(ad_local),
-                         solver.get_own_variables(solver.next), hip.vars_of(self.tmp), hip.ptr(solver.planes[25]),
-                         hip.ptr(self.tmp[5]), hip.stream_ptr())
-            else:
-                raise hip.T8gpuHipError("the data transfer kernel needs a GPU")
-        # 2. the new partition and an empty solver for it
-        self.new_part = self.new_mesh.partition(self.rank, self.world, subgrid=False, normal_dim=part.normal_dim)
-        self.new_solver = PlainSolver(self.new_part, dtype, flux_kind=solver.kind, mode=solver.mode,
-                                      state="zeros", inflow_states=solver.inflow_states,
-                                      plan_options=_inherited_plan_options(solver))
-        self.new_solver.next, self.new_solver.prev = solver.next, solver.prev
-        # 3. message plan: intersections of what I have with what every rank will own (and vice versa)
+        # the old -> new correspondence of this rank's adapted elements, relative to its old ones (the transfer kernels' input)
+        self.adapt_local = (adapt_data[a:b + 1] - old_off[self.rank]).astype(np.int32)
+        # message plan: intersections of what I have with what every rank will own (and vice versa)
         self.sends, self.recvs = [], []
         lo_r, hi_r = int(self.new_off[self.rank]), int(self.new_off[self.rank + 1])
         for q in range(self.world):
             s0, s1 = max(a, int(self.new_off[q])), min(b, int(self.new_off[q + 1]))
             if s1 > s0:
-                self.sends.append((q, s0 - a, s1 - s0))                  # (peer, first in tmp, count)
+                self.sends.append((q, s0 - a, s1 - s0))                  # (peer, first in the temporary planes, count)
             r0, r1 = max(int(self.have_off[q]), lo_r), min(int(self.have_off[q + 1]), hi_r)
             if r1 > r0:
                 self.recvs.append((q, r0 - lo_r, r1 - r0))               # (peer, first in the new planes, count)
-        self.sendbufs = {q: torch.empty(6 * n, dtype=dtype, device=dev) for q, _, n in self.sends if q != self.rank}
-        self.recvbufs = {q: torch.empty(6 * n, dtype=dtype, device=dev) for q, _, n in self.recvs if q != self.rank}
-        s = hip.stream_ptr()
-        for q, first, n in self.sends:
-            if q != self.rank:
-                hip.call("t8gpu_hip_gather_elements", dtype, n, first, hip.vars_of(self.tmp), hip.ptr(self.tmp[5]),
-                         hip.ptr(self.sendbufs[q]), s)
+
+    def kept_first(self):
+        """first element of the temporary planes that stays on this rank (its receive from itself)"""
+        return [f for p, f, m in self.sends if p == self.rank][0]
 
     def transport(self, dist, host_staged=False):
         """host_staged: move the messages through host memory (gloo, which cannot send device buffers)."""
@@ -163,13 +122,48 @@ class PartitionedAdapt:
             for q, b in self.recvbufs.items():
                 b.copy_(rbuf[q])
 
+
+class PartitionedAdapt(_Repartition):
+    """adapt() + partition() for an SFC-partitioned plain-element run (MeshManager::adapt followed by
+    MeshManager::partition, t8gpu/mesh/mesh_manager.inl:196-330, 645-723): a message is 5 variables + volume per element,
+    packed by a gather kernel."""
+
+    def __init__(self, solver, all_criteria, threshold=10.0, min_level=1, max_level=4, family_members_averaged=4):
+        part = solver.part
+        super().__init__(solver, part.mesh.marks_from_criteria(all_criteria, threshold, min_level, max_level, family_members_averaged))
+        dtype, dev = solver.dtype, solver.planes.device
+        # 1. local data transfer (adapt_variables_and_volume) into 6 temporary planes
+        self.tmp = torch.zeros((6, max(1, self.n_have)), dtype=dtype, device=dev)
+        if self.n_have:
+            if dev.type == "cuda":
+                ad_local = torch.from_numpy(self.adapt_local).to(dev)
+                hip.call("t8gpu_hip_adapt_variables_and_volume", dtype, self.n_have, part.mesh.dim, hip.ptr(ad_local),
+                         solver.get_own_variables(solver.next), hip.vars_of(self.tmp), hip.ptr(solver.planes[25]),
+                         hip.ptr(self.tmp[5]), hip.stream_ptr())
+            else:
+                raise hip.T8gpuHipError("the data transfer kernel needs a GPU")
+        # 2. the new partition and an empty solver for it
+        self.new_part = self.new_mesh.partition(self.rank, self.world, subgrid=False, normal_dim=part.normal_dim)
+        self.new_solver = PlainSolver(self.new_part, dtype, flux_kind=solver.kind, mode=solver.mode,
+                                      state="zeros", inflow_states=solver.inflow_states,
+                                      plan_options=None if solver.plan is None else solver.plan.inherited_options())
+        self.new_solver.next, self.new_solver.prev = solver.next, solver.prev
+        # 3. the messages
+        self.sendbufs = {q: torch.empty(6 * n, dtype=dtype, device=dev) for q, _, n in self.sends if q != self.rank}
+        self.recvbufs = {q: torch.empty(6 * n, dtype=dtype, device=dev) for q, _, n in self.recvs if q != self.rank}
+        s = hip.stream_ptr()
+        for q, first, n in self.sends:
+            if q != self.rank:
+                hip.call("t8gpu_hip_gather_elements", dtype, n, first, hip.vars_of(self.tmp), hip.ptr(self.tmp[5]),
+                         hip.ptr(self.sendbufs[q]), s)
+
     def finish(self):
         new, dtype = self.new_solver, self.solver.dtype
         s = hip.stream_ptr()
         nv = new.get_own_variables(new.next)
         for q, first, n in self.recvs:
             if q == self.rank:       # stays here: straight from the temporary planes
-                src_first = [f for p, f, m in self.sends if p == self.rank][0]
+                src_first = self.kept_first()
                 new.planes[5 * new.next:5 * new.next + 5, first:first + n] = self.tmp[0:5, src_first:src_first + n]
                 new.planes[25, first:first + n] = self.tmp[5, src_first:src_first + n]
             else:
@@ -243,37 +237,22 @@ def adapt_subgrid(solver, threshold=0.02, min_level=1, max_level=6, family_membe
     return new, marks, adapt_data
 
 
-class PartitionedSubgridAdapt:
+class PartitionedSubgridAdapt(_Repartition):
     """adapt() + partition() for an SFC-partitioned Subgrid run (SubgridMeshManager::adapt followed by
-    SubgridMeshManager::partition, t8gpu/mesh/subgrid_mesh_manager.inl:428-558, 1217-1369), one rank per GPU.
-
-    Same scheme as PartitionedAdapt: the forest operations are replicated, each rank transfers its own blocks
-    on the device (block-wise injection / mean, subgrid_mesh_manager.inl:246-425) and ships contiguous runs of
-    adapted blocks -- 5 x 4^rank values + one volume per block, one message per destination -- to their
-    owners in the new equal split. A run of blocks is contiguous in every variable plane, so a message is
-    six slices; no gather kernel is needed."""
+    SubgridMeshManager::partition, t8gpu/mesh/subgrid_mesh_manager.inl:428-558, 1217-1369): the transfer is block-wise
+    injection / mean (subgrid_mesh_manager.inl:246-425), a message is 5 x 4^rank values + one volume per block. A run of
+    blocks is contiguous in every variable plane, so a message is six slices; no gather kernel is needed."""
 
     def __init__(self, solver, all_criteria, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4):
         from .solver import SubgridSolver
         part = solver.part
-        self.solver, self.rank, self.world = solver, part.rank, part.nranks
-        mesh, S = part.mesh, solver.S
-        self.S = S
-        old_off = mesh.partition_offsets(self.world)
-        marks = mesh.marks_from_criteria(all_criteria, threshold, min_level, max_level, family_members_averaged)
-        self.marks = mesh.unmark_split_families(marks, old_off[1:-1])
-        self.new_mesh, adapt_data = mesh.adapt(self.marks)
-        n_new = self.new_mesh.num_elements
-        self.have_off = np.searchsorted(adapt_data[:-1], old_off, side="left").astype(np.int64)
-        self.have_off[-1] = n_new
-        self.new_off = self.new_mesh.partition_offsets(self.world)
-        a, b = int(self.have_off[self.rank]), int(self.have_off[self.rank + 1])
-        self.n_have = b - a
+        super().__init__(solver, part.mesh.marks_from_criteria(all_criteria, threshold, min_level, max_level, family_members_averaged))
+        S = self.S = solver.S
         dtype, dev = solver.dtype, solver.planes.device
         self.tmp = torch.zeros((5, max(1, self.n_have) * S), dtype=dtype, device=dev)
         self.tmp_vol = torch.zeros(max(1, self.n_have), dtype=dtype, device=dev)
         if self.n_have:
-            ad_local = torch.from_numpy((adapt_data[a:b + 1] - old_off[self.rank]).astype(np.int32)).to(dev)
+            ad_local = torch.from_numpy(self.adapt_local).to(dev)
             hip.call("t8gpu_hip_subgrid_adapt_variables_and_volume", dtype, solver.rank, self.n_have, hip.ptr(ad_local),
                      solver.get_own_variables(solver.next), hip.vars_of(self.tmp), hip.ptr(solver.volumes), hip.ptr(self.tmp_vol),
                      hip.stream_ptr())
@@ -281,15 +260,6 @@ class PartitionedSubgridAdapt:
         tot = self.new_part.N + self.new_part.G
         self.new_solver = SubgridSolver(self.new_part, dtype, flux_kind=solver.kind, mode=solver.mode, state=np.zeros((5, tot * S)))
         self.new_solver.next, self.new_solver.prev = solver.next, solver.prev
-        self.sends, self.recvs = [], []
-        lo_r, hi_r = int(self.new_off[self.rank]), int(self.new_off[self.rank + 1])
-        for q in range(self.world):
-            s0, s1 = max(a, int(self.new_off[q])), min(b, int(self.new_off[q + 1]))
-            if s1 > s0:
-                self.sends.append((q, s0 - a, s1 - s0))                  # (peer, first block in tmp, count)
-            r0, r1 = max(int(self.have_off[q]), lo_r), min(int(self.have_off[q + 1]), hi_r)
-            if r1 > r0:
-                self.recvs.append((q, r0 - lo_r, r1 - r0))               # (peer, first block in the new planes, count)
         w = 5 * S + 1
         self.sendbufs, self.recvbufs = {}, {}
         for q, first, n in self.sends:
@@ -302,14 +272,12 @@ class PartitionedSubgridAdapt:
             if q != self.rank:
                 self.recvbufs[q] = torch.empty(w * n, dtype=dtype, device=dev)
 
-    transport = PartitionedAdapt.transport
-
     def finish(self):
         new, S = self.new_solver, self.S
         dst = new.planes[5 * new.next:5 * new.next + 5]
         for q, first, n in self.recvs:
             if q == self.rank:
-                src_first = [f for p, f, m in self.sends if p == self.rank][0]
+                src_first = self.kept_first()
                 dst[:, first * S:(first + n) * S] = self.tmp[:, src_first * S:(src_first + n) * S]
                 new.volumes[first:first + n] = self.tmp_vol[src_first:src_first + n]
             else:

@@ -1,5 +1,6 @@
 """Device-side plan objects of the fused tile kernels (uploads the host plan, fills the C struct)."""
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -37,117 +38,115 @@ class PlainPlan:
         """The host half alone (no GPU): the tile plan and the caps / patch forms the rules below settle on (`host`, `auto_fcap`,
         `irregular`, `auto_irregular`). Tests pin the rules through this."""
         self = object.__new__(cls)
-        args = dict(tmax=None, fcap=None, compressed=True, dictionary=True, patches=None, flux_kind=None, irregular=None, fcap_elements=None,
-                    two_classes=None)
-        args.update(kw)
-        self._plan_on_host(part, dtype, **args)
+        self._plan_on_host(part, dtype, **kw)
         return self
 
-    def _plan_on_host(self, part, dtype, tmax, fcap, compressed, dictionary, patches, flux_kind, irregular, fcap_elements=None,
-                      two_classes=None):
-        import os
-        # An inherited face cap (amr._inherited_plan_options) was chosen for a mesh of `fcap_elements` elements: which kernel a
-        # plan gets depends on its tile count, so a mesh that has since grown or shrunk by more than a factor two decides again
-        # (a run that starts from a coarse mesh would otherwise keep the small mesh's 768-face one-tile plan for good).
+    def inherited_options(self):
+        """Plan options of a mesh adapted from this one (amr): the cap and patch form settled on here, which may have taken two
+        builds to find, and the mesh size they were chosen for (they expire with it: _plan_on_host)."""
+        opts = dict(irregular=self.auto_irregular, fcap_elements=self.auto_fcap_elements)
+        if self.auto_fcap is not None:
+            opts["fcap"] = self.auto_fcap
+        return opts
+
+    def _plan_on_host(self, part, dtype, tmax=None, fcap=None, compressed=True, dictionary=True, patches=None, flux_kind=None,
+                      irregular=None, fcap_elements=None, two_classes=None):
+        """Settles tile caps and patch forms and builds self.host; returns whether the per-face geometry rows stay on the host.
+        The switches (README) are read here, once."""
+        env = os.environ
+        env_patch = env.get("T8GPU_PATCH", "1") != "0"
+        env_irregular = env.get("T8GPU_PATCH_IRREGULAR")
+        env_tmax = int(env["T8GPU_TMAX"]) if "T8GPU_TMAX" in env else None
+        env_fcap = int(env["T8GPU_FCAP"]) if "T8GPU_FCAP" in env else None
+        fp32, fp64, dim3 = dtype == torch.float32, dtype == torch.float64, getattr(part.mesh, "dim", 2) == 3
+        multi_rank = getattr(part, "nranks", 1) > 1
+        tuned = compressed and dictionary        # the kernels with a geometry dictionary: the rules below are about them
+        # -- the request. An inherited cap and patch form were chosen for a mesh of `fcap_elements` elements: which kernel a plan
+        # gets depends on its tile count, so a mesh that has grown or shrunk by more than a factor two since decides again.
         if fcap_elements and not (fcap_elements // 2 <= part.N <= 2 * fcap_elements):
-            fcap = None
-            irregular = None          # (an inherited patch form was decided on that mesh too: ADVICE r3)
+            fcap = irregular = None
         self.auto_fcap_elements = fcap_elements if (fcap is not None or irregular is not None) and fcap_elements else part.N
         if patches is None:
-            patches = compressed and os.environ.get("T8GPU_PATCH", "1") != "0"
-        self.patches = patches if compressed else False          # True / False, or 2 / 3 for one kind only
-        # 3D: blocks next to periodic wraps / walls / coarser - side neighbours become (irregular) patches too
-        irregular_auto = irregular is None and "T8GPU_PATCH_IRREGULAR" not in os.environ   # (nobody asked: the rules below may drop it)
+            patches = compressed and env_patch
+        # (True / False, or 2 / 3: one kind only.) Patch kernels address a plane by a 32-bit byte offset: 4 GiB planes keep tiles.
+        if not compressed or (part.N + part.G) * (4 if fp32 else 8) >= 2 ** 32:
+            patches = False
+        # 3D blocks next to wraps / walls / coarser neighbours as (irregular) patches: if nobody asked, the rules may drop it
+        irregular_auto = irregular is None and env_irregular is None
         if irregular is None:
-            irregular = {"0": False, "all": "all"}.get(os.environ.get("T8GPU_PATCH_IRREGULAR", "1"), True)
-        self.irregular = irregular
-        # the patch kernels address a plane by a 32-bit byte offset: meshes whose planes reach 4 GiB keep the tile kernels
-        if (part.N + part.G) * (4 if dtype == torch.float32 else 8) >= 2 ** 32:
-            self.patches = False
-        # tuning knobs of the tiling. A mesh that would give fewer than 512 tiles (two per CU) gets half-size tiles:
-        # c1 (65 536 elements) runs 16 % faster on 512 tiles of 128 than on 256 tiles of 256.
-        given_fcap = fcap
-        small = part.N < 512 * 256 and tmax is None and fcap is None and "T8GPU_TMAX" not in os.environ
-        tmax = int(os.environ.get("T8GPU_TMAX", 128 if small else 256)) if tmax is None else tmax
-        if small:
-            fcap = int(os.environ.get("T8GPU_FCAP", 256))
-        # 512 faces = two passes of 256: what the persistent kernel takes, and the default. (Round 1 measured larger tiles
-        # 1-8 % slower on 3D meshes because the one-tile kernel then lost its fourth workgroup per CU; since round 2 that
-        # kernel holds three either way, and 3D AMR meshes get 768 -- below.) A 512-lane workgroup with one lane per own +
-        # halo element and two passes of 512 faces was 5-7 % slower (8 waves per barrier, 2 workgroups per CU).
-        # the face cap chosen by the heuristics below, or handed down from the plan of the mesh this one was adapted from
-        # (amr._inherited_plan_options); None: the default
-        self.auto_fcap = given_fcap
-        # Partitioned meshes: interior tiles in ONE class (tile_order = interior | ghost-reading) -- the two-lane step driver
-        # (stepper.hip) launches [0, n_interior) as one kernel per stage. two_classes=False keeps the deep / near-boundary
-        # split (the lanes then run the near-boundary tiles on the comm lane behind the ghost-reading ones).
-        if two_classes is None:
-            two_classes = getattr(part, "nranks", 1) > 1
-        self.two_classes = bool(two_classes)
-        retry_768 = given_fcap in (384, 480) and dtype == torch.float64      # an inherited cap still has to fit the persistent kernel
-        if (fcap is None and "T8GPU_FCAP" not in os.environ and not small and dtype == torch.float64 and
-                getattr(part.mesh, "dim", 2) == 3):
+            irregular = {"0": False, "all": "all"}.get(env_irregular, True)
+        self.patches, self.irregular = patches, irregular
+        # Partitioned meshes: interior tiles in ONE class, launched as one kernel per stage by the two-lane step driver
+        # (stepper.hip). two_classes=False keeps the deep / near-boundary split (near-boundary tiles then run on the comm lane).
+        self.two_classes = bool(multi_rank if two_classes is None else two_classes)
+
+        def build(cap, want_face_geo=not tuned):     # (the per-face geometry rows: read by the kernels without a dictionary)
+            return HostPlainPlan.from_partition(part, two_classes=self.two_classes, tmax=tmax, fcap=cap, want_face_geo=want_face_geo,
+                                                patches=self.patches, irregular=self.irregular)
+        def persistent_accepts(h, n_generic=None):
+            return tuned and self._persistent_accepts(h, dtype, flux_kind, n_generic)
+
+        # -- the rules. A mesh that would give fewer than 512 tiles (two per CU) gets half-size tiles: c1 (65 536 elements)
+        # runs 16 % faster on 512 tiles of 128 than on 256 tiles of 256.
+        small = part.N < 512 * 256 and tmax is None and fcap is None and env_tmax is None
+        if tmax is None:
+            tmax = 128 if small else 256 if env_tmax is None else env_tmax
+        # 512 faces = two passes of 256: what the persistent kernel takes, and the default (3D AMR meshes: below). A 512-lane
+        # workgroup with one lane per own + halo element and two passes of 512 faces was 5-7 % slower (8 waves per barrier).
+        cap = fcap
+        if fcap is None and env_fcap is None and not small and fp64 and dim3:
             # fp64 on 3D meshes. Curved meshes (no small geometry dictionary) run the one-tile kernel, which holds three
-            # workgroups per CU whatever the LDS (146 VGPRs) and does better on tiles of up to 768 faces in three passes
-            # (~200 instead of 134 elements per 256-lane workgroup): c5p 4 230 -> 4 545, c5t 4 380 -> 4 540 M cell-updates/s.
-            # Cartesian 3D AMR (elements with more than 8 faces) runs the persistent kernel IF its third workgroup per CU
-            # fits: 480-face tiles (51.7 KB of LDS) do, 512-face tiles (53.1 KB) do not -- c5 4 110 (one-tile, 512) ->
-            # 4 450 (one-tile, 768) -> 4 770 (persistent, 480). 2D meshes keep 512 (their 35 KB tiles are what the DENSE
-            # budget needs; 768: -13 %), and so does fp32 (four to five workgroups per CU on 512-face tiles either way).
+            # workgroups per CU whatever the LDS and does better on tiles of up to 768 faces in three passes: c5p 4 230 -> 4 545,
+            # c5t 4 380 -> 4 540 M cell-updates/s. Cartesian 3D AMR (elements with more than 8 faces) runs the persistent kernel
+            # IF its third workgroup per CU fits: 480-face tiles (51.7 KB of LDS) do, 512-face tiles (53.1 KB) do not -- c5 4 110
+            # (one-tile, 512) -> 4 450 (one-tile, 768) -> 4 770 (persistent, 480). 2D meshes (768: -13 %) and fp32 keep 512.
             # (A partitioned run launches tile classes, i.e. the one-tile kernel: 768 there too.)
             if self._many_geometries(part):
-                fcap = self.auto_fcap = 768
+                cap = 768
             elif self._wide_rows(part):
-                if getattr(part, "nranks", 1) > 1:
-                    fcap = self.auto_fcap = 768
-                else:
-                    fcap, retry_768 = 480, True
-                    self.auto_fcap = 480
-        fcap = int(os.environ.get("T8GPU_FCAP", 512)) if fcap is None else fcap
-        # the per-face geometry rows are only read by the kernels without a dictionary (generic kernel, dictionary=False)
-        self.host = HostPlainPlan.from_partition(part, two_classes=self.two_classes, tmax=tmax, fcap=fcap, want_face_geo=not (compressed and dictionary), patches=self.patches, irregular=self.irregular)
-        if retry_768:
-            # 480-face tiles only pay if the persistent kernel takes the plan: the LAUNCHER'S OWN test is asked (C-ABI query;
-            # it covers the LDS margin, the tile-count gate for mid-size meshes, the flux kind and T8GPU_PERSISTENT=0 --
-            # ADVICE r2: a partial copy of that test used to live here). Otherwise the one-tile kernel runs, which does
-            # better on 768-face tiles.
-            if not (compressed and dictionary and self._persistent_accepts(self.host, dtype, flux_kind)):
-                fcap = self.auto_fcap = 768
-                self.host = HostPlainPlan.from_partition(part, two_classes=self.two_classes, tmax=tmax, fcap=fcap, want_face_geo=not (compressed and dictionary), patches=self.patches, irregular=self.irregular)
-        if (given_fcap is None and "T8GPU_FCAP" not in os.environ and compressed and dictionary and fcap in (480, 512)
-                and getattr(part.mesh, "dim", 2) == 3 and self.host.n_patches * 256 > part.N // 2
-                and self.host.n_patches < self.host.ntiles):
+                cap = 768 if multi_rank else 480
+        # the cap chosen by the rules or inherited from the plan of the mesh this one was adapted from; None: the default
+        self.auto_fcap = cap
+        if cap is None:
+            cap = (256 if small else 512) if env_fcap is None else env_fcap
+        h = build(cap)
+        if fp64 and self.auto_fcap in (384, 480) and not persistent_accepts(h):
+            # 384 / 480-face tiles only pay if the persistent kernel takes the plan: the LAUNCHER'S OWN test is asked (C-ABI
+            # query: the LDS margin, the tile-count gate for mid-size meshes, the flux kind, T8GPU_PERSISTENT=0). Otherwise the
+            # one-tile kernel runs, which does better on 768-face tiles.
+            cap = self.auto_fcap = 768
+            h = build(cap)
+        if (fcap is None and env_fcap is None and tuned and dim3 and cap in (480, 512) and h.n_patches * 256 > part.N // 2
+                and h.n_patches < h.ntiles):
             # Most of a 3D mesh in patches: the generic tiles are what is left BETWEEN patches -- short stretches (c5: 144
             # elements / 520 faces each, a 2-cell slab of fine cells beside coarse ones) that a 480-face cap cuts 120 + 24 and a
             # 512-face cap 140 + 4. Measured on c5, fp64 (scripts/fcap_scan.sh): 256: 5 340, 300: 5 640, 360-400: 5 720-5 760,
             # 440: 5 540, 480: 5 420 M/s; fp32: 512: 9 310, 384: 9 950 (a plan without patches prefers 480: 4 550 against
-            # 4 130 at 380).
-            trial = HostPlainPlan.from_partition(part, two_classes=self.two_classes, tmax=tmax, fcap=384, want_face_geo=False, patches=self.patches, irregular=self.irregular)
-            # (fp64: only if the persistent kernel still takes the plan -- the one-tile kernel wants 768; fp32 runs either kernel well)
-            if dtype == torch.float32 or self._persistent_accepts(trial, dtype, flux_kind):
-                fcap = self.auto_fcap = 384
-                self.host = trial
+            # 4 130 at 380). fp64 only if the persistent kernel still takes the plan -- the one-tile kernel wants 768; fp32
+            # runs either kernel well.
+            trial = build(384)
+            if fp32 or persistent_accepts(trial):
+                cap = self.auto_fcap = 384
+                h = trial
         # fp32: the irregular patch form pays only where the alternative is a launch of generic tiles too small for the
         # persistent kernel (the uniform box c5u: 10 480 -> 12 680 M/s); where the blocks would simply join a large generic
         # launch it costs (c5: 10 630 -> 9 960) -- in fp32 its selects and signs weigh more against the flux than in fp64
         # (c5 fp64: 5 560 -> 5 760). Asked of the launcher with the tile count the plan would have without the form.
-        n_irr = sum(self.host.n_irregular_class)
-        if (dtype == torch.float32 and self.irregular is True and irregular_auto and n_irr and compressed and dictionary
-                and self._persistent_accepts(self.host, dtype, flux_kind, n_generic=self.host.ntiles - self.host.n_patches + 2 * n_irr)):
+        n_irr = sum(h.n_irregular_class)
+        if fp32 and irregular_auto and n_irr and persistent_accepts(h, n_generic=h.ntiles - h.n_patches + 2 * n_irr):
             self.irregular = False
-            self.host = HostPlainPlan.from_partition(part, two_classes=self.two_classes, tmax=tmax, fcap=fcap, want_face_geo=False, patches=self.patches, irregular=False)
-        h = self.host
-        # What an ADAPTED mesh's plan inherits (amr._inherited_plan_options): where nearly every patch is an irregular one -- thin
-        # refined sheets: c5a has 5 944 irregular and 8 regular patches -- the irregular form buys nothing (it runs at the speed of
-        # the persistent tile kernel on such cells) and costs planning time in every cycle; keep it where regular patches carry
-        # a good part of the mesh (uniform boxes with wraps or walls: c5u +26 %).
+            h = build(cap)
+        # What an ADAPTED mesh's plan inherits: where nearly every patch is an irregular one -- thin refined sheets: c5a has
+        # 5 944 irregular and 8 regular patches -- the irregular form buys nothing (it runs at the speed of the persistent tile
+        # kernel on such cells) and costs planning time in every cycle; keep it where regular patches carry a good part of the
+        # mesh (uniform boxes with wraps or walls: c5u +26 %).
         n_irr = sum(h.n_irregular_class)
         self.auto_irregular = self.irregular if n_irr <= 4 * (h.n_patches - n_irr) else False
         # the pipelined kernel with a geometry dictionary never reads the per-face rows (32 B per face: 700 MB at c4)
-        skip_geo = (compressed and dictionary and h.geo_table.shape[0] > 0 and h.max_elems <= 256 and h.max_slots <= 512
-                    and h.max_faces <= 1024)
+        skip_geo = (tuned and h.geo_table.shape[0] > 0 and h.max_elems <= 256 and h.max_slots <= 512 and h.max_faces <= 1024)
         if not skip_geo and h.face_geo.shape[0] == 0 and h.face_lr.size:     # the kernels this plan gets do read the rows
-            self.host = h = HostPlainPlan.from_partition(part, two_classes=self.two_classes, tmax=tmax, fcap=fcap, want_face_geo=True, patches=self.patches, irregular=self.irregular)
+            h = build(cap, want_face_geo=True)
+        self.host = h
         return skip_geo
 
     def _upload(self, dtype, compressed, dictionary, skip_geo, part):
@@ -206,34 +205,33 @@ class PlainPlan:
         self.c.inflow = table.data_ptr()
 
     @staticmethod
-    def _needs_csr(h):
-        """Would the generic tiles of the compressed form of host plan `h` run the generic kernel, which walks the CSR lists?
-        (t8gpu_hip_plain_needs_csr: the launcher's own test.)"""
+    def _query(h):
+        """What the launcher's own tests below read of host plan `h`: its integer fields and which compressed arrays exist (never
+        dereferenced). So they can be asked before anything is uploaded, and without a GPU."""
         c = T8gpuPlainPlan()
-        one = C.c_void_p(1)                                     # "present": never dereferenced by the query
-        c.tile_desc, c.ell = one, one
-        c.ell_width, c.max_elems, c.max_halo, c.max_faces, c.max_slots = h.ell_width, h.max_elems, h.max_halo, h.max_faces, h.max_slots
-        fn = hip.lib().t8gpu_hip_plain_needs_csr
-        fn.restype = C.c_int
-        return bool(fn(C.byref(c)))
-
-    @staticmethod
-    def _persistent_accepts(h, dtype, flux_kind=None, n_generic=None):
-        """Would a whole-plan launch of host plan `h` run the persistent tile kernel? (t8gpu_hip_plain_persistent_accepts:
-        the launcher's decision; only integer fields and the presence of the compressed arrays matter, so it can be asked
-        before anything is uploaded -- and without a GPU.)"""
-        c = T8gpuPlainPlan()
-        one = C.c_void_p(1)                                     # "present": never dereferenced by the query
+        one = C.c_void_p(1)                                     # "present"
         c.tile_desc, c.ell = one, one
         if h.geo_table.shape[0] > 0:
             c.geo_idx, c.geo_table = one, one
         c.n_geo, c.ell_width = h.geo_table.shape[0], h.ell_width
         c.ntiles, c.max_elems, c.max_halo, c.max_faces, c.max_slots = h.ntiles, h.max_elems, h.max_halo, h.max_faces, h.max_slots
-        c.has_open_faces = int(getattr(h, "open_faces", False))
-        fn = hip.lib().t8gpu_hip_plain_persistent_accepts
-        fn.restype = C.c_int
+        c.has_open_faces = int(h.open_faces)
+        return c
+
+    @staticmethod
+    def _needs_csr(h):
+        """Would the generic tiles of the compressed form of host plan `h` run the generic kernel, which walks the CSR lists?
+        (t8gpu_hip_plain_needs_csr: the launcher's own test.)"""
+        return bool(hip.lib().t8gpu_hip_plain_needs_csr(C.byref(PlainPlan._query(h))))
+
+    @staticmethod
+    def _persistent_accepts(h, dtype, flux_kind=None, n_generic=None):
+        """Would a whole-plan launch of host plan `h` run the persistent tile kernel? (t8gpu_hip_plain_persistent_accepts:
+        the launcher's decision.)"""
         n_generic = h.ntiles - h.n_patches if n_generic is None else n_generic
-        return bool(fn(C.byref(c), int(hip.KEPES if flux_kind is None else flux_kind), 4 if dtype == torch.float32 else 8, int(n_generic)))
+        kind = hip.KEPES if flux_kind is None else flux_kind
+        return bool(hip.lib().t8gpu_hip_plain_persistent_accepts(C.byref(PlainPlan._query(h)), int(kind), 4 if dtype == torch.float32 else 8,
+                                                                 int(n_generic)))
 
     @staticmethod
     def _wide_rows(part):

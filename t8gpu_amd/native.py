@@ -97,12 +97,13 @@ class NativeHalo:
 
 class NativeStepper:
     """t8gpu_hip_plain_stepper_*: the whole iterate() enqueued by one C call."""
+    _create = "t8gpu_hip_plain_stepper_create"
 
     def __init__(self, plan, halo=None):
         self.plan, self.halo = plan, halo
         self.handle = C.c_void_p()
-        hip.check(hip.lib().t8gpu_hip_plain_stepper_create(C.byref(plan.c), C.byref(halo.c) if halo is not None else None,
-                                                           C.byref(self.handle)))
+        hip.check(getattr(hip.lib(), self._create)(C.byref(plan.c), C.byref(halo.c) if halo is not None else None,
+                                                   C.byref(self.handle)))
 
     def __del__(self):
         if getattr(self, "handle", None):
@@ -149,12 +150,7 @@ class NativeStepper:
 class NativeSubgridStepper(NativeStepper):
     """t8gpu_hip_subgrid_stepper_*: SubgridCompressibleEulerSolver::iterate enqueued by one C call (block classes on
     the two lanes, one RCCL exchange of whole ghost blocks per stage)."""
-
-    def __init__(self, plan, halo=None):
-        self.plan, self.halo = plan, halo
-        self.handle = C.c_void_p()
-        hip.check(hip.lib().t8gpu_hip_subgrid_stepper_create(C.byref(plan.c), C.byref(halo.c) if halo is not None else None,
-                                                             C.byref(self.handle)))
+    _create = "t8gpu_hip_subgrid_stepper_create"
 
     def iterate(self, solver, delta_t, stream=None):
         self.iterate_steps(solver, delta_t, 1, solver.prev, solver.next, stream)

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, native
 
 STEP0, STEP1, STEP2, STEP3, FLUXES = range(5)
 
@@ -69,32 +69,126 @@ def check_inflow_states(part, inflow_states):
     return s
 
 
-class PlainSolver:
+class _Solver:
+    """What PlainSolver and SubgridSolver share: the step roles (`next` / `prev`, solver.h:100-101), the stage loop with its
+    halo overlap and both step drivers. A solver supplies `owned_cells` (the columns of state()), `_units()` (tiles or
+    blocks of its fused plan), `_stage_compat` and `_native_stepper`."""
+
+    def __init__(self, part, dtype, flux_kind, mode):
+        if not torch.cuda.is_available():
+            raise hip.T8gpuHipError(f"{type(self).__name__} needs a GPU: the hot path has no CPU implementation")
+        if mode not in ("compat", "fused"):
+            raise ValueError(mode)
+        hip.lib()
+        self.part, self.dtype, self.kind, self.mode = part, dtype, flux_kind, mode
+        self.N, self.G, self.F, self.B = part.N, part.G, part.F, part.B
+        self.fn = _dev(part.face_neighbors)
+        self.next, self.prev = STEP0, STEP3  # solver.h:100-101
+        self.plan = self.stepper = None
+
+    # -- accessors named after the reference API ------------------------------------------------
+    def get_own_variables(self, step):
+        return hip.vars_of(self.planes, step)
+
+    def state(self, step=None):
+        s = self.next if step is None else step
+        return self.planes[5 * s:5 * s + 5, :self.owned_cells]
+
+    def step_planes(self, step):
+        return self.planes[5 * step:5 * step + 5]
+
+    def begin_step(self):
+        self.next, self.prev = self.prev, self.next  # solver.cu:76, solver.inl:154
+
+    def stage_steps(self, k):
+        """(source step, destination step) of RK stage k = 0, 1, 2 (solver.cu:81-174)."""
+        return (self.prev, STEP1, STEP2)[k], (STEP1, STEP2, self.next)[k]
+
+    def run_stage(self, k, delta_t, stream=None, halo=None, split=False):
+        """Flux evaluation on the stage's source state + RK update. With a halo exchange (or split=True) the fused kernels run
+        the interior tiles / blocks (those that read no ghost) first and the others after finish()."""
+        s = hip.stream_ptr(stream)
+        src, dst = self.stage_steps(k)
+        ni, nt = (self.plan.host.n_interior, self._units()) if self.mode == "fused" else (0, 0)
+
+        def stage(stream, *units):
+            if self.mode == "compat":
+                self._stage_compat(k + 1, src, dst, delta_t, stream)
+            else:
+                self.plan.stage(self, k + 1, src, dst, delta_t, stream, *units)
+
+        if halo is not None and halo.overlapped and 0 < ni < nt:
+            # boundary pipeline on the comm stream: ghosts, then the units that read them; the interior ones beside it
+            halo.start(self.step_planes(src), then=lambda: stage(hip.stream_ptr(), ni, nt - ni))
+            stage(s, 0, ni)
+            halo.finish()
+            return
+        if halo is not None:
+            halo.start(self.step_planes(src))
+        if (halo is None and not split) or ni == nt or ni == 0:     # one launch (the compat tier: always)
+            if halo is not None:
+                halo.finish()
+            stage(s)
+            return
+        stage(s, 0, ni)
+        if halo is not None:
+            halo.finish()
+        stage(s, ni, nt - ni)
+
+    def use_native_stepper(self, native_halo=None):
+        """Drive iterate() through the C++ stepper (one C call per run of steps, RCCL called natively)."""
+        assert self.mode == "fused"
+        self.stepper = self._native_stepper(self.plan, native_halo)
+        return self.stepper
+
+    def iterate_steps(self, n_steps, delta_t, stream=None, halo=None):
+        """n_steps steps with a fixed delta_t. With the native stepper this is ONE call: the exchange stream and
+        the compute stream then meet only at its entry and exit (see csrc/hip/stepper.hip)."""
+        if n_steps <= 0:
+            return
+        if self.stepper is None:
+            for _ in range(n_steps):
+                self.iterate(delta_t, stream, halo)
+            return
+        self.begin_step()
+        first_prev, first_next = self.prev, self.next
+        for _ in range(n_steps - 1):
+            self.begin_step()
+        self.stepper.iterate_steps(self, delta_t, n_steps, first_prev, first_next, stream)
+
+    def iterate(self, delta_t, stream=None, halo=None):
+        """One SSP-RK3 step (CompressibleEulerSolver::iterate, SubgridCompressibleEulerSolver::iterate). `halo` (a
+        halo.HaloExchange) refreshes the ghost slots of each stage's source state while the interior tiles are already running."""
+        self.begin_step()
+        if self.stepper is not None:
+            self.stepper.iterate(self, delta_t, stream)
+            return
+        for k in range(3):
+            self.run_stage(k, delta_t, stream, halo)
+
+
+class PlainSolver(_Solver):
     """Plain elements. mode = "compat": reference data flow (face kernel + atomics, RK kernel);
     mode = "fused": tile kernels (flux + RK in one pass, no flux planes in HBM).
     Boundary faces follow part.boundary_kinds (0 wall, 1 outflow, 2 + k inflow with state k; absent: walls);
     inflow_states = (K, 5) conservative states, required iff some face is an inflow face."""
+    _native_stepper = native.NativeStepper
 
     def __init__(self, part, dtype=torch.float64, flux_kind=hip.KEPES, mode="compat", capacity=None, state=None,
                  device=None, plan_options=None, inflow_states=None):
         inflow_states = check_inflow_states(part, inflow_states)
-        if not torch.cuda.is_available():
-            raise hip.T8gpuHipError("PlainSolver needs a GPU: the hot path has no CPU implementation")
-        hip.lib()
-        self.part, self.dtype, self.kind, self.mode = part, dtype, flux_kind, mode
+        super().__init__(part, dtype, flux_kind, mode)
         tot = part.N + part.G
-        self.N, self.G, self.F, self.B, self.ndim = part.N, part.G, part.F, part.B, part.normal_dim
+        self.ndim, self.owned_cells = part.normal_dim, part.N
         self.stride = capacity or tot
         self.planes = torch.zeros((26, self.stride), dtype=dtype, device="cuda")
         if not (isinstance(state, str) and state == "zeros"):     # "zeros": the caller fills the planes on the device (amr.adapt)
             ic = part.kh_initial_state() if state is None else state
             self.planes[0:5, :tot] = _dev(ic, dtype)
         self.planes[25, :tot] = _dev(part.volumes, dtype)
-        self.fn = _dev(part.face_neighbors)
         self.indices = None  # ghosts already resolve to local slots (SURVEY 8e)
         self._normals = self._areas = None     # per-face geometry of the compat kernels: uploaded when first asked for
         self.speed = torch.zeros(max(1, part.F + part.B), dtype=dtype, device="cuda")
-        self.next, self.prev = STEP0, STEP3  # solver.h:100-101
         # open boundaries: the kinds (compat kernels) and the inflow table, uploaded once here (launches never allocate or copy)
         kinds = boundary_kinds_of(part)
         self.open_boundaries = kinds is not None and bool(np.any(kinds != 0))
@@ -108,7 +202,6 @@ class PlainSolver:
             hip.call("t8gpu_hip_plain_inflow_table", dtype, hip.ptr(st), int(states.shape[0]), hip.ptr(self.inflow_table),
                      hip.stream_ptr())
             torch.cuda.current_stream().synchronize()     # (`st` is released on return)
-        self.plan = None
         if mode == "fused":
             from . import fused
             import time
@@ -117,8 +210,6 @@ class PlainSolver:
             if self.plan.c.has_open_faces:
                 self.plan.attach_inflow(self.inflow_table)
             self.plan_build_s = time.perf_counter() - t0          # host tile plan + its upload (amr.adapt reports it)
-        elif mode != "compat":
-            raise ValueError(mode)
 
     @property
     def normals(self):
@@ -134,16 +225,8 @@ class PlainSolver:
             self._areas = _dev(self.part.areas, self.dtype)
         return self._areas
 
-    # -- accessors named after the reference API ------------------------------------------------
-    def get_own_variables(self, step):
-        return hip.vars_of(self.planes, step)
-
     def get_own_volume(self):
         return self.planes[25]
-
-    def state(self, step=None):
-        s = self.next if step is None else step
-        return self.planes[5 * s:5 * s + 5, :self.N]
 
     # -- one flux evaluation + RK stage in the reference's data flow -----------------------------
     def _stage_compat(self, stage, src, dst, dt, stream):
@@ -194,120 +277,37 @@ class PlainSolver:
         level = self.part.mesh.finest_level if max_level is None else max_level
         return cfl * 0.5 ** level / float(speed.item())
 
-    def begin_step(self):
-        self.next, self.prev = self.prev, self.next  # solver.cu:76
-
-    def stage_steps(self, k):
-        """(source step, destination step) of RK stage k = 0, 1, 2 (solver.cu:81-174)."""
-        return (self.prev, STEP1, STEP2)[k], (STEP1, STEP2, self.next)[k]
-
-    def step_planes(self, step):
-        return self.planes[5 * step:5 * step + 5]
-
-    def run_stage(self, k, delta_t, stream=None, halo=None, split=False):
-        """Flux evaluation on the stage's source state + RK update. With a halo exchange (or split=True)
-        the fused kernels run the interior tiles first and the ghost-reading tiles after finish()."""
-        s = hip.stream_ptr(stream)
-        src, dst = self.stage_steps(k)
-        ni, nt = (self.plan.host.n_interior, self.plan.host.ntiles) if self.mode == "fused" else (0, 0)
-        if halo is not None and halo.overlapped and 0 < ni < nt:
-            # boundary pipeline on the comm stream: ghosts, then the tiles that read them; interior tiles beside it
-            halo.start(self.step_planes(src), then=lambda: self.plan.stage(self, k + 1, src, dst, delta_t, hip.stream_ptr(), ni, nt - ni))
-            self.plan.stage(self, k + 1, src, dst, delta_t, s, 0, ni)
-            halo.finish()
-            return
-        if halo is not None:
-            halo.start(self.step_planes(src))
-        if self.mode == "compat":
-            if halo is not None:
-                halo.finish()
-            self._stage_compat(k + 1, src, dst, delta_t, s)
-            return
-        ni, nt = self.plan.host.n_interior, self.plan.host.ntiles
-        if (halo is None and not split) or ni == nt or ni == 0:
-            if halo is not None:
-                halo.finish()
-            self.plan.stage(self, k + 1, src, dst, delta_t, s)
-        else:
-            self.plan.stage(self, k + 1, src, dst, delta_t, s, 0, ni)
-            if halo is not None:
-                halo.finish()
-            self.plan.stage(self, k + 1, src, dst, delta_t, s, ni, nt - ni)
-
-    def use_native_stepper(self, native_halo=None):
-        """Drive iterate() through the C++ stepper (one C call per step, RCCL called natively)."""
-        from . import native
-        assert self.mode == "fused"
-        self.stepper = native.NativeStepper(self.plan, native_halo)
-        return self.stepper
-
-    def iterate_steps(self, n_steps, delta_t, stream=None, halo=None):
-        """n_steps steps with a fixed delta_t. With the native stepper this is ONE call: the exchange stream and
-        the compute stream then meet only at its entry and exit (see csrc/hip/stepper.hip)."""
-        if n_steps <= 0:
-            return
-        if getattr(self, "stepper", None) is None:
-            for _ in range(n_steps):
-                self.iterate(delta_t, stream, halo)
-            return
-        self.begin_step()
-        first_prev, first_next = self.prev, self.next
-        for _ in range(n_steps - 1):
-            self.begin_step()
-        self.stepper.iterate_steps(self, delta_t, n_steps, first_prev, first_next, stream)
-
-    def iterate(self, delta_t, stream=None, halo=None):
-        """One SSP-RK3 step (CompressibleEulerSolver::iterate). `halo` (a halo.HaloExchange) refreshes
-        the ghost slots of each stage's source state while the interior tiles are already running."""
-        self.begin_step()
-        if getattr(self, "stepper", None) is not None:
-            self.stepper.iterate(self, delta_t, stream)
-            return
-        for k in range(3):
-            self.run_stage(k, delta_t, stream, halo)
+    def _units(self):
+        return self.plan.host.ntiles
 
 
-class SubgridSolver:
+class SubgridSolver(_Solver):
     """Subgrid<4,4> / Subgrid<4,4,4>: planes[25, (N+G)*S] in subcells + per-block volumes."""
+    _native_stepper = native.NativeSubgridStepper
 
     def __init__(self, part, dtype=torch.float32, flux_kind=hip.KEPES, mode="compat", state=None):
         kinds = boundary_kinds_of(part)
         if kinds is not None and np.any(kinds != 0):
             raise ValueError("SubgridSolver supports reflective walls only: the partition has outflow / inflow boundary faces "
                              "(open boundaries are implemented for plain elements, PlainSolver)")
-        if not torch.cuda.is_available():
-            raise hip.T8gpuHipError("SubgridSolver needs a GPU: the hot path has no CPU implementation")
-        hip.lib()
         assert part.subgrid
-        self.part, self.dtype, self.kind, self.mode = part, dtype, flux_kind, mode
+        super().__init__(part, dtype, flux_kind, mode)
         self.rank = part.mesh.dim
         self.S = 4 ** self.rank
         tot = part.N + part.G
-        self.N, self.G, self.F, self.B = part.N, part.G, part.F, part.B
+        self.owned_cells = part.N * self.S
         self.stride = tot * self.S
         self.planes = torch.zeros((25, self.stride), dtype=dtype, device="cuda")
         ic = part.kh_initial_state() if state is None else state
         self.planes[0:5] = _dev(ic, dtype)
         self.volumes = _dev(part.volumes, dtype)
-        self.fn = _dev(part.face_neighbors)
         self.level_diff = _dev(part.level_diff)
         self.nb_offset = _dev(part.nb_offset)
         self.normals = _dev(part.normals, dtype)
         self.areas = _dev(part.areas, dtype)
-        self.next, self.prev = STEP0, STEP3
-        self.plan = None
         if mode == "fused":
             from . import fused
             self.plan = fused.SubgridPlan(part, dtype)
-        elif mode != "compat":
-            raise ValueError(mode)
-
-    def get_own_variables(self, step):
-        return hip.vars_of(self.planes, step)
-
-    def state(self, step=None):
-        s = self.next if step is None else step
-        return self.planes[5 * s:5 * s + 5, :self.N * self.S]
 
     def _stage_compat(self, stage, src, dst, dt, stream):
         st, fl = self.get_own_variables(src), self.get_own_variables(FLUXES)
@@ -325,71 +325,5 @@ class SubgridSolver:
                  self.get_own_variables(self.prev), st, self.get_own_variables(dst), fl, hip.ptr(self.volumes),
                  hip.fscalar(self.dtype, dt), stream)
 
-    def begin_step(self):
-        self.prev, self.next = self.next, self.prev  # solver.inl:154
-
-    def stage_steps(self, k):
-        return (self.prev, STEP1, STEP2)[k], (STEP1, STEP2, self.next)[k]
-
-    def step_planes(self, step):
-        return self.planes[5 * step:5 * step + 5]
-
-    def run_stage(self, k, delta_t, stream=None, halo=None, split=False):
-        """One flux evaluation + RK stage; with a halo exchange (or split=True) the fused kernel runs the
-        blocks that touch no ghost block first and the others after the ghosts have arrived."""
-        s = hip.stream_ptr(stream)
-        src, dst = self.stage_steps(k)
-        ni, nt = (self.plan.host.n_interior, self.N) if self.mode == "fused" else (0, 0)
-        if halo is not None and halo.overlapped and 0 < ni < nt:
-            # boundary pipeline on the comm stream: ghost blocks, then the blocks that read them; the rest beside it
-            halo.start(self.step_planes(src), then=lambda: self.plan.stage(self, k + 1, src, dst, delta_t, hip.stream_ptr(), ni, nt - ni))
-            self.plan.stage(self, k + 1, src, dst, delta_t, s, 0, ni)
-            halo.finish()
-            return
-        if halo is not None:
-            halo.start(self.step_planes(src))
-        if self.mode == "compat":
-            if halo is not None:
-                halo.finish()
-            self._stage_compat(k + 1, src, dst, delta_t, s)
-            return
-        ni, nt = self.plan.host.n_interior, self.N
-        if (halo is None and not split) or ni == nt or ni == 0:
-            if halo is not None:
-                halo.finish()
-            self.plan.stage(self, k + 1, src, dst, delta_t, s)
-        else:
-            self.plan.stage(self, k + 1, src, dst, delta_t, s, 0, ni)
-            if halo is not None:
-                halo.finish()
-            self.plan.stage(self, k + 1, src, dst, delta_t, s, ni, nt - ni)
-
-    def use_native_stepper(self, native_halo=None):
-        """Drive iterate() through the C++ stepper (one C call per run of steps, RCCL called natively)."""
-        from . import native
-        assert self.mode == "fused"
-        self.stepper = native.NativeSubgridStepper(self.plan, native_halo)
-        return self.stepper
-
-    def iterate_steps(self, n_steps, delta_t, stream=None, halo=None):
-        """n_steps steps with a fixed delta_t; ONE call with the native stepper (csrc/hip/stepper.hip)."""
-        if n_steps <= 0:
-            return
-        if getattr(self, "stepper", None) is None:
-            for _ in range(n_steps):
-                self.iterate(delta_t, stream, halo)
-            return
-        self.begin_step()
-        first_prev, first_next = self.prev, self.next
-        for _ in range(n_steps - 1):
-            self.begin_step()
-        self.stepper.iterate_steps(self, delta_t, n_steps, first_prev, first_next, stream)
-
-    def iterate(self, delta_t, stream=None, halo=None):
-        """SubgridCompressibleEulerSolver::iterate; `halo` refreshes the ghost blocks of each stage's source."""
-        self.begin_step()
-        if getattr(self, "stepper", None) is not None:
-            self.stepper.iterate(self, delta_t, stream)
-            return
-        for k in range(3):
-            self.run_stage(k, delta_t, stream, halo)
+    def _units(self):
+        return self.N

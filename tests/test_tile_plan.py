@@ -311,3 +311,91 @@ def test_patch_form_and_cap_rules_of_the_device_plan():
     s = PlainPlan.on_host(sheet, torch.float64)
     n_irr = sum(s.host.n_irregular_class)
     assert s.auto_irregular == (n_irr <= 4 * (s.host.n_patches - n_irr))
+
+
+
+def _caps(p):
+    return p.host.tmax, p.host.fcap, p.auto_fcap
+
+
+def test_small_mesh_caps_of_the_device_plan(monkeypatch):
+    """Fewer than 512 * 256 elements: 128-element, 256-face tiles (T8GPU_FCAP sets that cap too) -- unless a tile size was asked
+    for, by argument or T8GPU_TMAX; then 512 faces (or T8GPU_FCAP)."""
+    import torch
+    from t8gpu_amd.fused import PlainPlan
+    part = SynthMesh(2, 4, 7, band=0.05).partition()
+    assert part.N < 512 * 256
+    for k in ("T8GPU_TMAX", "T8GPU_FCAP"):
+        monkeypatch.delenv(k, raising=False)
+    assert _caps(PlainPlan.on_host(part, torch.float64)) == (128, 256, None)
+    assert _caps(PlainPlan.on_host(part, torch.float64, tmax=256)) == (256, 512, None)
+    monkeypatch.setenv("T8GPU_FCAP", "200")
+    assert _caps(PlainPlan.on_host(part, torch.float64)) == (128, 200, None)
+    monkeypatch.setenv("T8GPU_TMAX", "64")
+    assert _caps(PlainPlan.on_host(part, torch.float32)) == (64, 200, None)
+    monkeypatch.delenv("T8GPU_FCAP")
+    assert _caps(PlainPlan.on_host(part, torch.float32)) == (64, 512, None)
+
+
+def test_768_face_fallback_when_the_launcher_refuses_480():
+    """fp64, 3D AMR (elements with more than 8 faces): 480-face tiles stay only if the persistent kernel takes the plan -- a
+    small fp64 KEPES launch it refuses, HLL it takes. A given 384 / 480 cap is checked the same way in fp64, not in fp32; a
+    partitioned run gets 768 straight away."""
+    import torch
+    from t8gpu_amd import hip
+    from t8gpu_amd.fused import PlainPlan
+    mesh = SynthMesh(3, 3, 5, band=0.05)
+    part = mesh.partition()
+    h480 = HostPlainPlan.from_partition(part, tmax=256, fcap=480, want_face_geo=False, patches=True)
+    assert PlainPlan._wide_rows(part) and not PlainPlan._persistent_accepts(h480, torch.float64, hip.KEPES)
+    assert PlainPlan._persistent_accepts(h480, torch.float64, hip.HLL)
+    assert _caps(PlainPlan.on_host(part, torch.float64, tmax=256, flux_kind=hip.KEPES)) == (256, 768, 768)
+    assert _caps(PlainPlan.on_host(part, torch.float64, tmax=256, flux_kind=hip.HLL)) == (256, 480, 480)
+    assert _caps(PlainPlan.on_host(part, torch.float64, tmax=256, fcap=384)) == (256, 768, 768)
+    assert _caps(PlainPlan.on_host(part, torch.float32, tmax=256, fcap=480)) == (256, 480, 480)
+    assert _caps(PlainPlan.on_host(part, torch.float32, tmax=256)) == (256, 512, None)
+    assert _caps(PlainPlan.on_host(mesh.partition(0, 2), torch.float64, tmax=256)) == (256, 768, 768)
+
+
+def test_inherited_cap_and_patch_form_expire(monkeypatch):
+    """An adapted mesh's plan keeps the inherited cap and patch form (PlainPlan.inherited_options) while the mesh is within a
+    factor two of the size they were chosen for; outside that the rules decide again."""
+    import torch
+    from t8gpu_amd.fused import PlainPlan
+    for k in ("T8GPU_TMAX", "T8GPU_FCAP", "T8GPU_PATCH_IRREGULAR"):
+        monkeypatch.delenv(k, raising=False)
+    part = SynthMesh(3, 3, 5, band=0.05).partition()
+    N = part.N
+    assert PlainPlan.on_host(part, torch.float32).inherited_options() == {"irregular": True, "fcap_elements": N}
+    for chosen_for in (N, 2 * N, N // 2):
+        p = PlainPlan.on_host(part, torch.float32, fcap=480, irregular=False, fcap_elements=chosen_for)
+        assert (p.host.fcap, p.irregular, sum(p.host.n_irregular_class)) == (480, False, 0)
+        assert p.inherited_options() == {"fcap": 480, "irregular": False, "fcap_elements": chosen_for}
+    for chosen_for in (2 * N + 2, N // 2 - 1):            # expired: the small-mesh rule and the default form again
+        p = PlainPlan.on_host(part, torch.float32, fcap=480, irregular=False, fcap_elements=chosen_for)
+        assert (p.host.fcap, p.irregular, p.auto_fcap, p.auto_fcap_elements) == (256, True, None, N)
+    p = PlainPlan.on_host(part, torch.float32, fcap=480, irregular=False)       # asked for (no fcap_elements): never dropped
+    assert (p.host.fcap, p.irregular, p.auto_fcap_elements) == (480, False, N)
+
+
+def test_patch_switches(monkeypatch):
+    """T8GPU_PATCH=0: no patches unless an argument asks for them. T8GPU_PATCH_IRREGULAR: "0" no irregular form, "all" every
+    patch in it, anything else the form -- and set at all it counts as asked for, so fp32 on c5 keeps the form."""
+    import torch
+    from t8gpu_amd.fused import PlainPlan
+    for k in ("T8GPU_PATCH", "T8GPU_PATCH_IRREGULAR", "T8GPU_TMAX", "T8GPU_FCAP"):
+        monkeypatch.delenv(k, raising=False)
+    box = SynthMesh(3, 4, 4).partition()          # a periodic 16^3 box: every block touches a wrap
+    p = PlainPlan.on_host(box, torch.float64)
+    assert p.patches is True and sum(p.host.n_irregular_class) == p.host.n_patches == p.host.ntiles
+    monkeypatch.setenv("T8GPU_PATCH", "0")
+    assert PlainPlan.on_host(box, torch.float64).host.n_patches == 0
+    assert PlainPlan.on_host(box, torch.float64, patches=True).host.n_patches > 0
+    monkeypatch.delenv("T8GPU_PATCH")
+    for value, form in (("0", False), ("all", "all"), ("1", True), ("yes", True)):
+        monkeypatch.setenv("T8GPU_PATCH_IRREGULAR", value)
+        p = PlainPlan.on_host(box, torch.float64)
+        assert p.irregular == form and type(p.irregular) is type(form) and (sum(p.host.n_irregular_class) > 0) == bool(form)
+        assert PlainPlan.on_host(box, torch.float64, irregular=True).irregular is True
+    monkeypatch.setenv("T8GPU_PATCH_IRREGULAR", "1")
+    assert PlainPlan.on_host(SynthMesh(3, 6, 8, band=0.05).partition(), torch.float32).irregular is True
