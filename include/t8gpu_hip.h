@@ -124,6 +124,19 @@ int t8gpu_hip_subgrid_boundary_f64(int flux_kind, int rank, int num_faces, int n
                                    const int32_t* face_neighbors, const double* face_normals,
                                    const double* face_surfaces, T8gpuVars_f64 state, T8gpuVars_f64 fluxes,
                                    void* stream);
+/* The boundary faces with their kinds (t8gpu_host.h: boundary_kinds[B], device copy): walls as above; on an outflow face
+ * every sub-face evaluates the interior face flux with the outside state = the inside subcell's, on an inflow face with the
+ * outside state = the conservative state k of `inflow_table` (t8gpu_hip_plain_inflow_table_*, words 0-4 of a row; may be
+ * NULL when no face is an inflow face); outward normal, area face_surfaces / sub-faces. boundary_kinds = NULL is
+ * t8gpu_hip_subgrid_boundary_*. */
+int t8gpu_hip_subgrid_boundary_bc_f32(int flux_kind, int rank, int num_faces, int num_boundary_faces,
+                                      const int32_t* face_neighbors, const uint8_t* boundary_kinds, const float* inflow_table,
+                                      const float* face_normals, const float* face_surfaces, T8gpuVars_f32 state,
+                                      T8gpuVars_f32 fluxes, void* stream);
+int t8gpu_hip_subgrid_boundary_bc_f64(int flux_kind, int rank, int num_faces, int num_boundary_faces,
+                                      const int32_t* face_neighbors, const uint8_t* boundary_kinds, const double* inflow_table,
+                                      const double* face_normals, const double* face_surfaces, T8gpuVars_f64 state,
+                                      T8gpuVars_f64 fluxes, void* stream);
 
 /* timestepping::subgrid::SSP_3RK_step{1,2,3}<V,Subgrid><<<N, block_size>>>, ssp_runge_kutta.inl:101-221
  * (per-subcell volume = volumes[e] / Subgrid::size). */
@@ -383,6 +396,16 @@ typedef struct T8gpuSubgridPlan {
                                    4 + 4 + 4 rows (layout: subgrid_plan.cpp) */
   const int32_t* rest_rec;      /* [n_rest][32]: block_rec rows of the blocks outside every family, in block_order order */
   int32_t n_families, n_rest;
+  /* OPEN BOUNDARIES (ABI 10). A plan built with boundary_kinds (t8gpu_host.h: t8gpu_plan_subgrid_create_bc) keeps far = -1 for
+   * every boundary face and carries the face's kind in bits 23-26 of its code word: 0 reflective wall, 1 outflow (the outside
+   * state is the inside subcell's), 2 + k inflow with prescribed state k. has_open_faces = 1 selects the kernels that decode
+   * the kind; 0 (a zeroed tail) is the behaviour of earlier ABIs: every boundary face a wall. `inflow` is the table of the
+   * prescribed states filled by t8gpu_hip_plain_inflow_table_* (the Subgrid kernels read words 0-4 of a row, the conservative
+   * state); it must be given whenever has_open_faces is set (hipErrorInvalidValue otherwise) and holds an entry for every
+   * inflow code of the plan. No launch writes it. No family holds a block with an open face. */
+  const void*    inflow;        /* DEVICE float_type [K][T8GPU_INFLOW_WORDS] */
+  int32_t        has_open_faces;
+  int32_t        reserved10;
 } T8gpuSubgridPlan;
 
 /* block_begin/block_count select a range of block_order (0, num_elements = everything; [0, n_interior_blocks)

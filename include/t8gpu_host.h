@@ -140,6 +140,16 @@ void t8gpu_plan_plain_tile_desc(const void* plan, int32_t* tile_desc);
 void* t8gpu_plan_subgrid_create(int32_t N, int32_t F, int32_t B, int32_t rank, const int32_t* face_neighbors,
                                 const int32_t* face_level_difference, const int32_t* face_neighbor_offset,
                                 const double* normals);
+/* The same with the kind of every boundary face: boundary_kinds[B] (0 wall, 1 outflow, 2 + k inflow with state k, k < 8;
+ * NULL: every boundary face a wall, which is t8gpu_plan_subgrid_create). A boundary face keeps far = -1 in the records and
+ * carries its kind in bits 23-26 of its code word (face_rec, block_rec, bf_rec, rest_rec), so a wall-only plan is
+ * byte-identical to one without kinds. A block with an outflow / inflow face never joins a family (fam_rec knows walls only):
+ * it runs through rest_rec. t8gpu_plan_subgrid_open_faces tells whether the plan has open faces at all
+ * (T8gpuSubgridPlan::has_open_faces). */
+void* t8gpu_plan_subgrid_create_bc(int32_t N, int32_t F, int32_t B, int32_t rank, const int32_t* face_neighbors,
+                                   const int32_t* face_level_difference, const int32_t* face_neighbor_offset,
+                                   const double* normals, const uint8_t* boundary_kinds);
+int32_t t8gpu_plan_subgrid_open_faces(const void* plan);
 void  t8gpu_plan_subgrid_destroy(void* plan);
 /* sizes[8] = {n_entries, max faces per block, F + B, n_interior_blocks, n_deep_blocks, 1 + largest block index referred to
  * (owned and ghost blocks), n_families, n_rest} */

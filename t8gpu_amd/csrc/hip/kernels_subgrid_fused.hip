@@ -4,7 +4,9 @@
 //                      evaluated once from LDS, the far cells of the outward faces pooled over the wavefronts;
 //   k_subgrid_family2  2D: one wavefront = a 2x2 square of blocks, the same within a wavefront.
 // The launcher (subgrid_fused_stage) takes the family kernels wherever the host plan found cubes / squares and runs the
-// remaining blocks with the block algorithm in the same launch; all three give the same bits.
+// remaining blocks with the block algorithm in the same launch; all three give the same bits. Plans with outflow / inflow
+// faces (T8gpuSubgridPlan::has_open_faces) take the _open forms of the three kernels: their block algorithm decodes the kind
+// of every boundary face (sg_boundary_kind); the family bodies are the wall-only ones (no family holds an open-face block).
 //
 // Replaces, per stage, compute_inner_fluxes + compute_boundary_fluxes + compute_outer_fluxes +
 // subgrid::SSP_3RK_stepK (examples/subgrid/solver.inl:166-195) and their flux-plane round trips
@@ -85,6 +87,22 @@ T8_DEV FaceCode decode(int code) {
 }
 T8_DEV int cell_coord(int flat, int a) { return (flat >> (2 * a)) & 3; }   // flat = i + 4 j + 16 k
 
+// ---- boundary faces (open boundaries) -------------------------------------------------------------------------------
+// A boundary face has far = -1 in its record row and its kind in bits 23-26 of the code word (subgrid_plan.cpp): 0 reflective
+// wall, 1 outflow (the outside state is the inside subcell's own), 2 + k inflow with conservative state k of the plan's inflow
+// table. The one place that spells the encoding; only the OPEN instantiations of the block algorithm decode it (the others see
+// walls only, as before). An open face evaluates the ordinary face flux: left = the inside subcell, outward normal, unmirrored.
+T8_DEV int sg_boundary_kind(int code) { return (code >> 23) & 15; }
+// the conservative state of inflow kind `bc` (>= 2): words 0-4 of its T8GPU_INFLOW_WORDS row (t8gpu_hip_plain_inflow_table_*).
+// Words 5-13 hold the plain tiles' KEPES record (prim_from_state<T, sizeof(T) == 8>); the Subgrid kernels derive their own
+// with cell_from_state, as for every far cell, so they never read it.
+template <class T>
+T8_DEV void sg_inflow_state(const T8gpuSubgridPlan& P, int bc, T s[5]) {
+  const T* w = static_cast<const T*>(P.inflow) + T8GPU_INFLOW_WORDS * (bc - 2);
+#pragma unroll
+  for (int k = 0; k < 5; k++) s[k] = w[k];
+}
+
 template <class T, int KIND>
 struct CellData {  // what a flux evaluation needs from one cell: primitives (KEPES) or the raw state (HLL)
   static constexpr int words = KIND == 0 ? kPrimWords : 5;
@@ -127,8 +145,8 @@ T8_DEV void cell_flux(const CellData<T, KIND>& L, const CellData<T, KIND>& R, bo
 // What one lane needs for its (face slot, sub-face) of a generic pass; `sf` is the far cell's state.
 template <class T>
 struct FaceLane {
-  bool active, right, wall;
-  int  axis, positive, myflat;
+  bool active, right, wall;   // wall: a boundary face (OPEN: of kind bc)
+  int  axis, positive, myflat, bc;
   T    area, sf[5];
 };
 
@@ -141,7 +159,7 @@ T8_DEV FaceLane<T> face_lane_from_row(const SVars<T>& src, int4 rec, bool live_r
   FaceLane<T> L;
   L.active = live_row;
   L.right = L.wall = false;
-  L.axis = L.positive = L.myflat = 0;
+  L.axis = L.positive = L.myflat = L.bc = 0;
   L.area = T(0);
 #pragma unroll
   for (int k = 0; k < 5; k++) L.sf[k] = T(1);
@@ -164,20 +182,26 @@ T8_DEV FaceLane<T> face_lane_from_row(const SVars<T>& src, int4 rec, bool live_r
   }
   return L;
 }
-template <class T, int S, bool WIDE>
+template <class T, int S, bool WIDE, bool OPEN = false>
 T8_DEV FaceLane<T> load_face_lane(const T8gpuSubgridPlan& P, const SVars<T>& src, int first, int nbf, int idx, int si, int sj) {
   int4 rec = make_int4(0, 0, 0, 0);
   if (idx < nbf) rec = reinterpret_cast<const int4*>(P.bf_rec)[first + idx];   // {other block, code, area}
-  return face_lane_from_row<T, S, WIDE>(src, rec, idx < nbf, si, sj);
+  FaceLane<T> L = face_lane_from_row<T, S, WIDE>(src, rec, idx < nbf, si, sj);
+  if (OPEN && L.active && L.wall) {
+    L.bc = sg_boundary_kind(rec.y);
+    if (L.bc >= 2) sg_inflow_state<T>(P, L.bc, L.sf);
+  }
+  return L;
 }
 
 // The +d coarse face of a block (wave-uniform for RANK 3: these are scalar loads, which keeps the
 // dependent chain face list -> face record -> far cell short).
 template <class T>
 struct PlusFace {
-  bool on, wall;   // on: listed as ONE coarse face (faces towards finer blocks are in the generic list)
+  bool on, wall;   // on: listed as ONE coarse face (faces towards finer blocks are in the generic list); wall: a boundary face
   int  far, hf;    // far cell of sub-face (0, 0); hf: two sub-faces share a far cell (the block is the fine side)
   T    area;
+  int  bc;         // the kind of a boundary face (read by the OPEN instantiations only)
 };
 template <class T>
 T8_DEV PlusFace<T> plus_face(int4 w, bool live) {   // w = the four words of the block record for this face
@@ -192,6 +216,7 @@ T8_DEV PlusFace<T> plus_face(int4 w, bool live) {   // w = the four words of the
     f.hf   = (w.y >> 19) & 1;
     f.area = area_of(w.z, w.w, T(0));
   }
+  f.bc = f.wall ? sg_boundary_kind(w.y) : 0;
   return f;
 }
 // state of the far cell behind sub-face (ti, tj) of a + / - face with tangential strides 1 << la, 1 << lb; a wall face
@@ -227,7 +252,8 @@ T8_DEV void block_sync() {
 // One wavefront's work on its block(s): `pos_base` = the wavefront's position in the launch (RANK 3: the block record;
 // RANK 2: four records), c = lane, pe / xb = the wavefront's LDS slices ([NW][64 + BPW * PF] cells of the block(s) then
 // the far cells of their + faces; [5][64] flux exchange buffer).
-template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE, bool WAVE_ONLY, bool NT = false>
+// OPEN: the plan has outflow / inflow faces (sg_boundary_kind); OPEN = false is the wall-only block algorithm.
+template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE, bool WAVE_ONLY, bool NT = false, bool OPEN = false>
 T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_count, int pos_base, int c, const SVars<T>& prev,
                           const SVars<T>& src, const SVars<T>& out, const T* __restrict__ volumes, T dt, T* pe, T* xb) {
   // (pe / xb carry no __restrict__: other lanes write what this lane reads, and a no-alias pointer would let the
@@ -283,6 +309,10 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
   T          pfar[5];
   load_far<T, WIDE>(src, p_on, pd == 0 ? fx.wall : (pd == 1 ? fy.wall : fz.wall), pd == 0 ? fx.far : (pd == 1 ? fy.far : fz.far),
               pd == 0 ? fx.hf : (pd == 1 ? fy.hf : fz.hf), pla, plb, pti, ptj, -1, pfar);
+  if (OPEN) {   // an inflow face on the + side: its far cell is the prescribed state (outflow and walls read this cell's own)
+    const int pbc = pd == 0 ? fx.bc : (pd == 1 ? fy.bc : fz.bc);
+    if (p_on && pbc >= 2) sg_inflow_state<T>(P, pbc, pfar);
+  }
 
   // - faces: lane cl < PF owns sub-face `cl % SF` of the block's -(cl / SF) face. A wall lane fetches its OWN cell
   // again: the mirrored flux wants two copies of the same primitives, and this way no select is needed later.
@@ -296,6 +326,9 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
   T          mfar[5];
   load_far<T, WIDE>(src, m_on, m_wall, pd == 0 ? mx.far : (pd == 1 ? my.far : mz.far), pd == 0 ? mx.hf : (pd == 1 ? my.hf : mz.hf), pla, plb,
               pti, ptj, (size_t)e * S + mflat, mfar);
+  // (OPEN: an outflow lane keeps its own cell like a wall lane, an inflow lane takes the prescribed state)
+  const int m_bc = OPEN ? (pd == 0 ? mx.bc : (pd == 1 ? my.bc : mz.bc)) : 0;
+  if (OPEN && m_on && m_bc >= 2) sg_inflow_state<T>(P, m_bc, mfar);
 
   const CellData<T, KIND> mine = cell_from_state<T, KIND>(s0);
 #pragma unroll
@@ -317,9 +350,12 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
     const bool          inner = cc[d] < 3;
     // the other cell: next lane's, or (block surface) the far cell with this lane's tangential coordinates
     const int tsub = d == 0 ? cc[1] + 4 * cc[2] : (d == 1 ? cc[0] + 4 * cc[2] : cc[0] + 4 * cc[1]);
-    // (a wall mirrors this cell: kernels.inl:913-1107 / compute_boundary_fluxes)
-    const bool wall = !inner && pl.wall;
-    const int  oidx = inner ? c + str : (wall ? c : 64 + (c / S) * PF + d * SF + tsub);
+    // (a wall mirrors this cell: kernels.inl:913-1107 / compute_boundary_fluxes; OPEN: an outflow face takes this cell
+    //  unmirrored, an inflow face the prescribed state's primitives from the appended part)
+    const bool bnd  = !inner && pl.wall;
+    const bool wall = OPEN ? bnd && pl.bc == 0 : bnd;
+    const bool self = OPEN ? bnd && pl.bc < 2 : bnd;
+    const int  oidx = inner ? c + str : (self ? c : 64 + (c / S) * PF + d * SF + tsub);
     CellData<T, KIND> other;
 #pragma unroll
     for (int w = 0; w < NW; w++) other.v[w] = pe[(w) * PEL + (oidx)];
@@ -348,7 +384,17 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
 #pragma unroll
       for (int w = 0; w < NW; w++) here.v[w] = pe[(w) * PEL + (base + mflat)];
       const CellData<T, KIND> there = cell_from_state<T, KIND>(mfar);
-      cell_flux<T, KIND>(there, here, m_wall, pd, !m_wall, m_area / T(SF), g);
+      if (OPEN) {   // a boundary face: left = this cell, outward normal -e_d, right = the mirror (wall) or the outside state
+        CellData<T, KIND> L, R;
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+          L.v[w] = m_wall ? here.v[w] : there.v[w];
+          R.v[w] = m_wall ? there.v[w] : here.v[w];
+        }
+        cell_flux<T, KIND>(L, R, m_wall && m_bc == 0, pd, !m_wall, m_area / T(SF), g);
+      } else {
+        cell_flux<T, KIND>(there, here, m_wall, pd, !m_wall, m_area / T(SF), g);
+      }
       const T sgn = m_wall ? T(-1) : T(1);
 #pragma unroll
       for (int k = 0; k < 5; k++) g[k] *= sgn;
@@ -370,12 +416,13 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
   // ---- remaining coarse faces (towards finer blocks: four sub-faces per surface cell; kernels.inl:664-911) ----------
   for (int p0 = 0; p0 < npass; p0 += 4) {
     T                 g[5] = {T(0), T(0), T(0), T(0), T(0)};
-    const FaceLane<T> fl = load_face_lane<T, S, WIDE>(P, src, b0, nbf, p0 + slot, si, sj);
+    const FaceLane<T> fl = load_face_lane<T, S, WIDE, OPEN>(P, src, b0, nbf, p0 + slot, si, sj);
     if (fl.active) {
       CellData<T, KIND> here, there;
 #pragma unroll
       for (int w = 0; w < NW; w++) here.v[w] = pe[(w) * PEL + (base + fl.myflat)];
-      there = fl.wall ? here : cell_from_state<T, KIND>(fl.sf);
+      // (OPEN: an inflow face's outside state is the prescribed one, an outflow face's this cell unmirrored)
+      there = fl.wall && !(OPEN && fl.bc >= 2) ? here : cell_from_state<T, KIND>(fl.sf);
       // geometric orientation: the low-side cell is the left one (walls: this cell, outward normal)
       const bool low = fl.wall || (fl.right != (fl.positive != 0));
       CellData<T, KIND> L, R;
@@ -384,7 +431,7 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
         L.v[w] = low ? here.v[w] : there.v[w];
         R.v[w] = low ? there.v[w] : here.v[w];
       }
-      cell_flux<T, KIND>(L, R, fl.wall, fl.axis, fl.wall ? fl.positive != 0 : true, fl.area / T(SF), g);
+      cell_flux<T, KIND>(L, R, OPEN ? fl.wall && fl.bc == 0 : fl.wall, fl.axis, fl.wall ? fl.positive != 0 : true, fl.area / T(SF), g);
       // stored with the sign it has for this block's cell: leaves the left cell, enters the right one
       const T sgn = low ? T(-1) : T(1);
 #pragma unroll
@@ -460,6 +507,18 @@ __global__ __launch_bounds__(64) void k_subgrid_fused(T8gpuSubgridPlan P, int bl
   subgrid_block<T, KIND, STAGE, RANK, EARLY_PREV, WIDE, false>(P, block_begin, block_count, pos_base, threadIdx.x, prev, src, out, volumes,
                                                                dt, pe, xb);
 }
+// the same for plans with outflow / inflow faces
+template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE>
+__global__ __launch_bounds__(64) void k_subgrid_fused_open(T8gpuSubgridPlan P, int block_begin, int block_count, SVars<T> prev,
+                                                           SVars<T> src, SVars<T> out, const T* __restrict__ volumes, T dt) {
+  constexpr int NW = CellData<T, KIND>::words;
+  constexpr int PEL = 64 + (RANK == 3 ? 1 : 4) * RANK * (RANK == 3 ? 16 : 4);
+  __shared__ T pe[NW * PEL];
+  __shared__ T xb[5 * 64];
+  const int pos_base = sg_xcd_position(blockIdx.x, gridDim.x);
+  subgrid_block<T, KIND, STAGE, RANK, EARLY_PREV, WIDE, false, false, true>(P, block_begin, block_count, pos_base, threadIdx.x, prev, src,
+                                                                            out, volumes, dt, pe, xb);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Family kernel (RANK 3): one workgroup of eight wavefronts = a 2x2x2 cube of consecutive same-level blocks
@@ -477,9 +536,10 @@ T8_DEV int fam_expand(int j, int d) { return d == 0 ? j << 1 : (d == 1 ? (j & 1)
 
 // (second launch bound = wavefronts per SIMD the register allocation must allow: 3 workgroups per CU in fp32 (80 VGPRs),
 //  2 in fp64 (128 VGPRs; its 66 KB of LDS allow no more))
-template <class T, int KIND, int STAGE, bool WIDE, bool NT>
-__global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_subgrid_family(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src, SVars<T> out,
-                                                        const T* __restrict__ volumes, T dt) {
+// (the body of k_subgrid_family and k_subgrid_family_open: OPEN reaches the blocks outside every cube only)
+template <class T, int KIND, int STAGE, bool WIDE, bool NT, bool OPEN>
+T8_DEV void subgrid_family(const T8gpuSubgridPlan& P, const SVars<T>& prev, const SVars<T>& src, const SVars<T>& out,
+                           const T* __restrict__ volumes, T dt) {
   constexpr int  NW    = CellData<T, KIND>::words;
   constexpr bool EARLY = sizeof(T) == 4;   // fp32: previous-step state requested up front; fp64: fetched last (registers)
   constexpr int FAM_WORDS = NW * 704 + 3 * 5 * 64 + 5 * 512;       // this kernel's arrays
@@ -498,8 +558,8 @@ __global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_subgrid_family(
       T8gpuSubgridPlan R = P;
       R.block_rec        = P.rest_rec;
       T* const mine_lds  = lds + w * BLK_WORDS;
-      subgrid_block<T, KIND, STAGE, 3, sizeof(T) == 4, WIDE, true, NT>(R, 0, P.n_rest, pos, c, prev, src, out, volumes, dt, mine_lds,
-                                                                  mine_lds + NW * 112);
+      subgrid_block<T, KIND, STAGE, 3, sizeof(T) == 4, WIDE, true, NT, OPEN>(R, 0, P.n_rest, pos, c, prev, src, out, volumes, dt, mine_lds,
+                                                                        mine_lds + NW * 112);
     }
     return;
   }
@@ -640,6 +700,16 @@ __global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_subgrid_family(
 #pragma unroll
   for (int k = 0; k < 5; k++) stream_store<NT>(&at<WIDE>(out.p[k], o), rk_stage_update<T, STAGE>(pv[k], s0[k], scale, acc[k]));
 }
+template <class T, int KIND, int STAGE, bool WIDE, bool NT>
+__global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_subgrid_family(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src, SVars<T> out,
+                                                        const T* __restrict__ volumes, T dt) {
+  subgrid_family<T, KIND, STAGE, WIDE, NT, false>(P, prev, src, out, volumes, dt);
+}
+template <class T, int KIND, int STAGE, bool WIDE, bool NT>
+__global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_subgrid_family_open(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src,
+                                                                                     SVars<T> out, const T* __restrict__ volumes, T dt) {
+  subgrid_family<T, KIND, STAGE, WIDE, NT, true>(P, prev, src, out, volumes, dt);
+}
 
 // (Round 4, measured and dropped: a PERSISTENT form of this kernel -- a resident grid of 2 (fp64) / 3 (fp32) workgroups per CU
 // walking the cubes of their XCD's share, the next cube's record rows as scalar loads at the top of an iteration, its own state,
@@ -662,9 +732,9 @@ __global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_subgrid_family(
 // the + faces in lanes 0-15, 16 behind the - faces in lanes 16-31: one half-filled primitive round instead of the block
 // kernel's two). Same fluxes, same summation order: bitwise equal to the block kernel. The blocks outside every square run
 // behind the squares in the same launch (four per wavefront, the block algorithm).
-template <class T, int KIND, int STAGE, bool WIDE, bool NT>
-__global__ __launch_bounds__(64) void k_subgrid_family2(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src, SVars<T> out,
-                                                        const T* __restrict__ volumes, T dt) {
+template <class T, int KIND, int STAGE, bool WIDE, bool NT, bool OPEN>
+T8_DEV void subgrid_family2(const T8gpuSubgridPlan& P, const SVars<T>& prev, const SVars<T>& src, const SVars<T>& out,
+                            const T* __restrict__ volumes, T dt) {
   constexpr int  NW        = CellData<T, KIND>::words;
   constexpr bool EARLY     = sizeof(T) == 4;
   constexpr int  FAM_WORDS = NW * 80 + 5 * 64 + 2 * 5 * 8 + 5 * 16;
@@ -674,8 +744,8 @@ __global__ __launch_bounds__(64) void k_subgrid_family2(T8gpuSubgridPlan P, SVar
   if (static_cast<int>(blockIdx.x) >= P.n_families) {   // the blocks outside every square: four per wavefront
     T8gpuSubgridPlan R = P;
     R.block_rec        = P.rest_rec;
-    subgrid_block<T, KIND, STAGE, 2, EARLY, WIDE, false, NT>(R, 0, P.n_rest, static_cast<int>(blockIdx.x) - P.n_families, c, prev, src, out,
-                                                         volumes, dt, lds, lds + NW * 96);
+    subgrid_block<T, KIND, STAGE, 2, EARLY, WIDE, false, NT, OPEN>(R, 0, P.n_rest, static_cast<int>(blockIdx.x) - P.n_families, c, prev, src,
+                                                               out, volumes, dt, lds, lds + NW * 96);
     return;
   }
   // primitives [64 cells of the square, then 16 far cells behind the outward + faces ((d * 2 + j) * 4 + sub-face)];
@@ -797,6 +867,16 @@ __global__ __launch_bounds__(64) void k_subgrid_family2(T8gpuSubgridPlan P, SVar
 #pragma unroll
   for (int k = 0; k < 5; k++) stream_store<NT>(&at<WIDE>(out.p[k], o), rk_stage_update<T, STAGE>(pv[k], s0[k], scale, acc[k]));
 }
+template <class T, int KIND, int STAGE, bool WIDE, bool NT>
+__global__ __launch_bounds__(64) void k_subgrid_family2(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src, SVars<T> out,
+                                                        const T* __restrict__ volumes, T dt) {
+  subgrid_family2<T, KIND, STAGE, WIDE, NT, false>(P, prev, src, out, volumes, dt);
+}
+template <class T, int KIND, int STAGE, bool WIDE, bool NT>
+__global__ __launch_bounds__(64) void k_subgrid_family2_open(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src, SVars<T> out,
+                                                             const T* __restrict__ volumes, T dt) {
+  subgrid_family2<T, KIND, STAGE, WIDE, NT, true>(P, prev, src, out, volumes, dt);
+}
 
 template <class T, class V>
 SVars<T> smk(const V& v) {
@@ -812,6 +892,8 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
     return static_cast<int>(hipErrorInvalidValue);
   if (block_begin < 0 || block_count < 0 || block_begin + block_count > plan->num_elements) return static_cast<int>(hipErrorInvalidValue);
   if (block_count == 0) return 0;
+  const bool open = plan->has_open_faces != 0;   // outflow / inflow faces: the _open kernels
+  if (open && !plan->inflow) return static_cast<int>(hipErrorInvalidValue);
   stage_kernel_note_reset();
   hipStream_t s = static_cast<hipStream_t>(stream);
   // fp32 requests the previous-step state up front (one round trip less per wavefront); fp64 keeps fetching it last:
@@ -825,13 +907,19 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
   auto blocks = [&](const T8gpuSubgridPlan& pl, int begin, int count) {
     const dim3 grid(pl.rank == 3 ? count : (count + 3) / 4), block(64);
     return dispatch(
-        [&](auto K, auto S, auto RANK3, auto WIDE) {
+        [&](auto K, auto S, auto RANK3, auto WIDE, auto OPEN) {
           constexpr int R = RANK3 ? 3 : 2;
-          note_stage_kernel<T>(count, "k_subgrid_fused", K, S, R, early, WIDE);
-          return launch(&k_subgrid_fused<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
-                        smk<T>(out), volumes, dt);
+          if constexpr (OPEN) {
+            note_stage_kernel<T>(count, "k_subgrid_fused_open", K, S, R, early, WIDE);
+            return launch(&k_subgrid_fused_open<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
+                          smk<T>(out), volumes, dt);
+          } else {
+            note_stage_kernel<T>(count, "k_subgrid_fused", K, S, R, early, WIDE);
+            return launch(&k_subgrid_fused<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
+                          smk<T>(out), volumes, dt);
+          }
         },
-        kind, stage, pl.rank == 3, wide);
+        kind, stage, pl.rank == 3, wide, open);
   };
   // A launch that covers the whole plan of a 3D mesh: 2x2x2 cubes of same-level blocks through the family kernel, the
   // other blocks through the block kernel (T8GPU_SG_FAMILY=0: every block through the block kernel -- same bits. Measured
@@ -863,13 +951,20 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
   const int  restb = plan->rank == 3 ? (sizeof(T) == 8 ? 4 : 8) : 4;   // (k_subgrid_family: RESTB)
   const dim3 grid(plan->n_families + (n_rest_here + restb - 1) / restb), block(plan->rank == 3 ? 512 : 64);
   return dispatch(
-      [&](auto K, auto S, auto RANK3, auto WIDE, auto NT) {
-        const char* name   = RANK3 ? "k_subgrid_family" : "k_subgrid_family2";
-        const auto  kernel = RANK3 ? &k_subgrid_family<T, K, S, WIDE, NT> : &k_subgrid_family2<T, K, S, WIDE, NT>;
-        note_stage_kernel<T>(block_count, name, K, S, WIDE, NT);
-        return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
+      [&](auto K, auto S, auto RANK3, auto WIDE, auto NT, auto OPEN) {
+        if constexpr (OPEN) {   // (the cubes / squares hold no open-face block: the blocks behind them run the OPEN algorithm)
+          const char* name   = RANK3 ? "k_subgrid_family_open" : "k_subgrid_family2_open";
+          const auto  kernel = RANK3 ? &k_subgrid_family_open<T, K, S, WIDE, NT> : &k_subgrid_family2_open<T, K, S, WIDE, NT>;
+          note_stage_kernel<T>(block_count, name, K, S, WIDE, NT);
+          return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
+        } else {
+          const char* name   = RANK3 ? "k_subgrid_family" : "k_subgrid_family2";
+          const auto  kernel = RANK3 ? &k_subgrid_family<T, K, S, WIDE, NT> : &k_subgrid_family2<T, K, S, WIDE, NT>;
+          note_stage_kernel<T>(block_count, name, K, S, WIDE, NT);
+          return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
+        }
       },
-      kind, stage, plan->rank == 3, wide, nt);
+      kind, stage, plan->rank == 3, wide, nt, open);
 }
 
 }  // namespace t8gpu_hip

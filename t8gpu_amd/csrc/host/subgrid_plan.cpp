@@ -14,8 +14,10 @@
 //                            (lane = side * sub-faces + sub-face), with no face list to walk
 //   bf_off[N+1], bf_ent[]  : per owned block its remaining faces, i.e. those towards FINER blocks (four sub-faces
 //                            per surface cell), in original order; bit 31 set when the block is the face's RIGHT side
-//   face_rec[F+B][4]       : {left slot, right slot (-1: wall), code, 0} with
-//                            code = axis | positive<<2 | hanging<<3 | off0<<4 | off1<<6 | off2<<8
+//   face_rec[F+B][4]       : {left slot, right slot (-1: boundary face), code, 0} with
+//                            code = axis | positive<<2 | hanging<<3 | off0<<4 | off1<<6 | off2<<8 | bc<<23, where bc
+//                            = the boundary kind of a boundary face (0 wall, 1 outflow, 2 + k inflow state k; 0 for
+//                            every face when no kinds are given: a wall-only plan is the plan of earlier versions)
 // Normals must be exact +-unit axis vectors -- the reference's kernels require the same
 // (kernels.inl:717-750 select the face plane by comparing the normal with +-1.0).
 #include <cstdint>
@@ -29,14 +31,19 @@ struct SubgridPlan {
   std::vector<int32_t> fam_first;   // first block of every 2x2x2 family (below)
   std::vector<uint8_t> in_family;
   int32_t n_interior = 0, n_deep = 0;
+  bool    open_faces = false;   // some boundary face is an outflow / inflow face
 };
 }  // namespace
 
 extern "C" {
 
-void* t8gpu_plan_subgrid_create(int32_t N, int32_t F, int32_t B, int32_t rank, const int32_t* fn,
-                                const int32_t* level_diff, const int32_t* nb_offset, const double* normals) {
+void* t8gpu_plan_subgrid_create_bc(int32_t N, int32_t F, int32_t B, int32_t rank, const int32_t* fn,
+                                   const int32_t* level_diff, const int32_t* nb_offset, const double* normals,
+                                   const uint8_t* boundary_kinds) {
   if (N < 0 || F < 0 || B < 0 || (rank != 2 && rank != 3)) return nullptr;
+  if (boundary_kinds)
+    for (int32_t b = 0; b < B; b++)
+      if (boundary_kinds[b] > 9) return nullptr;   // 0 wall, 1 outflow, 2 + k inflow (k < 8)
   SubgridPlan* P = new SubgridPlan;
   P->N = N; P->F = F; P->B = B; P->rank = rank;
   P->face_rec.assign(4 * (static_cast<size_t>(F) + B), 0);
@@ -64,6 +71,9 @@ void* t8gpu_plan_subgrid_create(int32_t N, int32_t F, int32_t B, int32_t rank, c
       for (int d = 0; d < rank; d++) code |= (nb_offset[static_cast<size_t>(rank) * f + d] & 3) << (4 + 2 * d);
     } else {
       l = fn[2 * static_cast<size_t>(F) + (f - F)];
+      const int32_t bc = boundary_kinds ? boundary_kinds[f - F] : 0;
+      code |= bc << 23;
+      if (bc != 0 && l < N) P->open_faces = true;
     }
     int32_t* rec = &P->face_rec[4 * static_cast<size_t>(f)];
     rec[0] = l; rec[1] = r; rec[2] = code; rec[3] = 0;
@@ -133,6 +143,12 @@ void* t8gpu_plan_subgrid_create(int32_t N, int32_t F, int32_t B, int32_t rank, c
       if (ghosty[r] && !ghosty[l]) near[l] = 1;
     }
   }
+  // blocks with an outflow / inflow face: they never join a family (the family bodies know walls only) and run as rest blocks
+  std::vector<uint8_t> open_block(static_cast<size_t>(N), 0);
+  for (int32_t b = 0; b < B; b++) {
+    const int32_t l = fn[2 * static_cast<size_t>(F) + b];
+    if (l < N && boundary_kinds && boundary_kinds[b] != 0) open_block[l] = 1;
+  }
   // 2x2x2 families (RANK 3): eight CONSECUTIVE owned blocks e .. e + 7 that form a cube in Morton order -- the +x / +y /
   // +z neighbour of block e + w is block e + w + 1 / 2 / 4 at the same level wherever that bit of w is clear --, each of
   // whose 24 outward sides is one foldable coarse face (same level, coarser neighbour or wall) and none of which has a
@@ -152,6 +168,7 @@ void* t8gpu_plan_subgrid_create(int32_t N, int32_t F, int32_t B, int32_t rank, c
       for (int w = 0; w < NB; w++) {
         const int32_t b = e + w;
         if (ghosty[b] || near[b]) return false;   // cubes of DEEP blocks only: they then lie inside the first class below
+        if (open_block[b]) return false;
         if (P->bf_off[b + 1] != P->bf_off[b]) return false;
         for (int d = 0; d < rank; d++) {
           const int32_t pe = P->plus[static_cast<size_t>(b) * rank + d], me = P->minus[static_cast<size_t>(b) * rank + d];
@@ -186,6 +203,13 @@ void* t8gpu_plan_subgrid_create(int32_t N, int32_t F, int32_t B, int32_t rank, c
     if (ghosty[e]) P->block_order.push_back(e);
   return P;
 }
+
+void* t8gpu_plan_subgrid_create(int32_t N, int32_t F, int32_t B, int32_t rank, const int32_t* fn,
+                                const int32_t* level_diff, const int32_t* nb_offset, const double* normals) {
+  return t8gpu_plan_subgrid_create_bc(N, F, B, rank, fn, level_diff, nb_offset, normals, nullptr);
+}
+
+int32_t t8gpu_plan_subgrid_open_faces(const void* h) { return static_cast<const SubgridPlan*>(h)->open_faces ? 1 : 0; }
 
 void t8gpu_plan_subgrid_destroy(void* h) { delete static_cast<SubgridPlan*>(h); }
 
@@ -225,11 +249,12 @@ void t8gpu_plan_subgrid_arrays(const void* h, int32_t* bf_off, int32_t* bf_ent, 
 //     these six faces as soon as it knows its position
 //   bf_rec[n_entries][4], the generic faces of the blocks in the same position order: far, code, area (2 words)
 // far = index of the far cell of sub-face (0, 0) in the state arrays (far block * cells per block + its cell there; the
-// far block is the left block if this block is the face's right side and vice versa), -1 = wall, -2 (+ / - faces only) =
+// far block is the left block if this block is the face's right side and vice versa), -1 = boundary face (its kind in code
+// bits 23-26: 0 wall, 1 outflow, 2 + k inflow state k), -2 (+ / - faces only) =
 // not foldable (finer neighbours: those faces are in the generic list);
 // code = the face code of face_rec | 1 << 12 when this block is the face's RIGHT side | this block's cell behind
 // sub-face (0, 0) << 13 | (two sub-faces per far cell) << 19 | (two sub-faces per own cell) << 20 | (stride of the first
-// tangential axis is 4 instead of 1) << 21 | (stride of the second is 4 instead of 16) << 22, so that
+// tangential axis is 4 instead of 1) << 21 | (stride of the second is 4 instead of 16) << 22 | boundary kind << 23, so that
 //   cell(i, j) = c0 + ((i >> h) << la) + ((j >> h) << lb)
 // on either side needs no decoding of the anchor; area = face_surfaces[f] as float (word 0) or double.
 // (32-bit cell indices: a rank holds fewer than 2^31 subcells including its ghost blocks.)

@@ -269,7 +269,9 @@ class T8gpuSubgridPlan(C.Structure):
     _fields_ = [("block_rec", C.c_void_p), ("bf_rec", C.c_void_p),
                 ("num_elements", C.c_int32), ("rank", C.c_int32), ("max_faces_per_block", C.c_int32),
                 ("n_interior_blocks", C.c_int32), ("n_deep_blocks", C.c_int32), ("n_blocks_addressed", C.c_int32),
-                ("fam_rec", C.c_void_p), ("rest_rec", C.c_void_p), ("n_families", C.c_int32), ("n_rest", C.c_int32)]
+                ("fam_rec", C.c_void_p), ("rest_rec", C.c_void_p), ("n_families", C.c_int32), ("n_rest", C.c_int32),
+                # ABI 10: open boundaries -- the inflow table (device, [K][16]) and "the plan has outflow / inflow faces"
+                ("inflow", C.c_void_p), ("has_open_faces", C.c_int32), ("reserved10", C.c_int32)]
 
 
 class SubgridPlan:
@@ -292,7 +294,13 @@ class SubgridPlan:
         c.n_interior_blocks = self.host.n_interior
         c.n_deep_blocks = self.host.n_deep
         c.n_blocks_addressed = self.host.n_addressed
+        c.has_open_faces = int(self.host.has_open_faces)
         self.c = c
+
+    def attach_inflow(self, table):
+        """the device inflow table (t8gpu_hip_plain_inflow_table_*) the _open kernels read: set once, before any launch"""
+        self._keep["inflow"] = table
+        self.c.inflow = table.data_ptr()
 
     def stage(self, solver, stage, src, dst, dt, stream, block_begin=0, block_count=None):
         from .solver import _timer_begin, _timer_end

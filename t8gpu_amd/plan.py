@@ -132,11 +132,18 @@ class HostPlainPlan:
 class HostSubgridPlan:
     """Host arrays of the per-block face lists (see include/t8gpu_hip.h, T8gpuSubgridPlan)."""
 
-    def __init__(self, part):
+    def __init__(self, part, boundary_kinds=None):
+        """boundary_kinds[B] (0 wall, 1 outflow, 2 + k inflow k; default: part.boundary_kinds, None = all walls): a boundary
+        face carries its kind in bits 23-26 of its code word, and a block with an open face never joins a family
+        (t8gpu_host.h: t8gpu_plan_subgrid_create_bc)."""
         assert part.subgrid
         lib = _synth.lib()
         lib.t8gpu_plan_subgrid_create.restype = C.c_void_p
         lib.t8gpu_plan_subgrid_create.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 4
+        lib.t8gpu_plan_subgrid_create_bc.restype = C.c_void_p
+        lib.t8gpu_plan_subgrid_create_bc.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 5
+        lib.t8gpu_plan_subgrid_open_faces.restype = C.c_int32
+        lib.t8gpu_plan_subgrid_open_faces.argtypes = [C.c_void_p]
         lib.t8gpu_plan_subgrid_destroy.argtypes = [C.c_void_p]
         lib.t8gpu_plan_subgrid_sizes.argtypes = [C.c_void_p, C.c_void_p]
         lib.t8gpu_plan_subgrid_arrays.argtypes = [C.c_void_p] * 5
@@ -144,10 +151,19 @@ class HostSubgridPlan:
         rank = part.mesh.dim
         fn = np.ascontiguousarray(part.face_neighbors, np.int32)
         nr = np.ascontiguousarray(part.normals, np.float64)
-        h = lib.t8gpu_plan_subgrid_create(part.N, part.F, part.B, rank, p(fn), p(part.level_diff), p(part.nb_offset), p(nr))
+        if boundary_kinds is None:
+            boundary_kinds = getattr(part, "boundary_kinds", None)
+        if boundary_kinds is None:
+            h = lib.t8gpu_plan_subgrid_create(part.N, part.F, part.B, rank, p(fn), p(part.level_diff), p(part.nb_offset), p(nr))
+        else:
+            kinds = np.ascontiguousarray(boundary_kinds, np.uint8)
+            assert kinds.size == part.B
+            h = lib.t8gpu_plan_subgrid_create_bc(part.N, part.F, part.B, rank, p(fn), p(part.level_diff), p(part.nb_offset),
+                                                 p(nr), p(kinds))
         if not h:
             raise ValueError("subgrid plan needs axis-aligned unit normals (as the reference's subgrid kernels do)")
         self._h = h
+        self.has_open_faces = bool(lib.t8gpu_plan_subgrid_open_faces(h))   # some boundary face is an outflow / inflow face
         sz = np.zeros(8, np.int64)
         lib.t8gpu_plan_subgrid_sizes(h, p(sz))
         self.N, self.rank, self.max_bf, self.n_interior, self.n_deep = part.N, rank, int(sz[1]), int(sz[3]), int(sz[4])

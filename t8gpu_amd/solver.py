@@ -86,6 +86,20 @@ class _Solver:
         self.next, self.prev = STEP0, STEP3  # solver.h:100-101
         self.plan = self.stepper = None
 
+    def _upload_open_boundaries(self, kinds, inflow_states):
+        """device copies of the boundary kinds (compat kernels) and the inflow table (t8gpu_hip_plain_inflow_table_*), made once
+        when self.open_boundaries is set (launches never allocate or copy); None otherwise"""
+        self.inflow_states = inflow_states
+        self.kinds = self.inflow_table = None
+        if self.open_boundaries:
+            self.kinds = _dev(kinds) if kinds is not None and bool(np.any(kinds != 0)) else None   # (all walls: the wall kernel)
+            states = inflow_states if inflow_states is not None else np.zeros((1, 5))   # (an outflow-only plan: never read)
+            st = torch.from_numpy(np.ascontiguousarray(states)).to(self.dtype).cuda()
+            self.inflow_table = torch.zeros((states.shape[0], 16), dtype=self.dtype, device="cuda")
+            hip.call("t8gpu_hip_plain_inflow_table", self.dtype, hip.ptr(st), int(states.shape[0]), hip.ptr(self.inflow_table),
+                     hip.stream_ptr())
+            torch.cuda.current_stream().synchronize()     # (`st` is released on return)
+
     # -- accessors named after the reference API ------------------------------------------------
     def get_own_variables(self, step):
         return hip.vars_of(self.planes, step)
@@ -192,16 +206,7 @@ class PlainSolver(_Solver):
         # open boundaries: the kinds (compat kernels) and the inflow table, uploaded once here (launches never allocate or copy)
         kinds = boundary_kinds_of(part)
         self.open_boundaries = kinds is not None and bool(np.any(kinds != 0))
-        self.inflow_states = inflow_states
-        self.kinds = self.inflow_table = None
-        if self.open_boundaries:
-            self.kinds = _dev(kinds)
-            states = inflow_states if inflow_states is not None else np.zeros((1, 5))   # (an outflow-only plan: never read)
-            st = torch.from_numpy(np.ascontiguousarray(states)).to(dtype).cuda()
-            self.inflow_table = torch.zeros((states.shape[0], 16), dtype=dtype, device="cuda")
-            hip.call("t8gpu_hip_plain_inflow_table", dtype, hip.ptr(st), int(states.shape[0]), hip.ptr(self.inflow_table),
-                     hip.stream_ptr())
-            torch.cuda.current_stream().synchronize()     # (`st` is released on return)
+        self._upload_open_boundaries(kinds, inflow_states)
         if mode == "fused":
             from . import fused
             import time
@@ -282,16 +287,26 @@ class PlainSolver(_Solver):
 
 
 class SubgridSolver(_Solver):
-    """Subgrid<4,4> / Subgrid<4,4,4>: planes[25, (N+G)*S] in subcells + per-block volumes."""
+    """Subgrid<4,4> / Subgrid<4,4,4>: planes[25, (N+G)*S] in subcells + per-block volumes.
+    open_boundaries=True: boundary faces follow part.boundary_kinds (0 wall, 1 outflow, 2 + k inflow with state k; absent:
+    walls), every subcell on an open face with its own sub-face flux; inflow_states = (K, 5) conservative states, required iff
+    some face is an inflow face. A partition without open faces takes it too (a rank that owns no boundary, an adapted mesh).
+    By default a partition with open faces is refused."""
     _native_stepper = native.NativeSubgridStepper
 
-    def __init__(self, part, dtype=torch.float32, flux_kind=hip.KEPES, mode="compat", state=None):
+    def __init__(self, part, dtype=torch.float32, flux_kind=hip.KEPES, mode="compat", state=None, open_boundaries=False,
+                 inflow_states=None):
         kinds = boundary_kinds_of(part)
-        if kinds is not None and np.any(kinds != 0):
-            raise ValueError("SubgridSolver supports reflective walls only: the partition has outflow / inflow boundary faces "
-                             "(open boundaries are implemented for plain elements, PlainSolver)")
+        if not open_boundaries and kinds is not None and np.any(kinds != 0):
+            raise ValueError("SubgridSolver without open_boundaries=True takes walls only: the partition has outflow / inflow "
+                             "boundary faces (pass open_boundaries=True and, for inflow faces, inflow_states)")
+        if not open_boundaries and inflow_states is not None:
+            raise ValueError("inflow_states needs open_boundaries=True")
+        inflow_states = check_inflow_states(part, inflow_states) if open_boundaries else None
         assert part.subgrid
         super().__init__(part, dtype, flux_kind, mode)
+        self.open_boundaries = bool(open_boundaries)
+        self._upload_open_boundaries(kinds, inflow_states)
         self.rank = part.mesh.dim
         self.S = 4 ** self.rank
         tot = part.N + part.G
@@ -308,6 +323,8 @@ class SubgridSolver(_Solver):
         if mode == "fused":
             from . import fused
             self.plan = fused.SubgridPlan(part, dtype)
+            if self.plan.c.has_open_faces:
+                self.plan.attach_inflow(self.inflow_table)
 
     def _stage_compat(self, stage, src, dst, dt, stream):
         st, fl = self.get_own_variables(src), self.get_own_variables(FLUXES)
@@ -315,7 +332,10 @@ class SubgridSolver(_Solver):
         hip.call("t8gpu_hip_subgrid_inner", self.dtype, self.kind, self.rank, self.N, st, fl, hip.ptr(self.volumes),
                  stream)
         _timer_end(self, ev)
-        if self.B > 0:
+        if self.B > 0 and self.kinds is not None:
+            hip.call("t8gpu_hip_subgrid_boundary_bc", self.dtype, self.kind, self.rank, self.F, self.B, hip.ptr(self.fn),
+                     hip.ptr(self.kinds), hip.ptr(self.inflow_table), hip.ptr(self.normals), hip.ptr(self.areas), st, fl, stream)
+        elif self.B > 0:
             hip.call("t8gpu_hip_subgrid_boundary", self.dtype, self.kind, self.rank, self.F, self.B,
                      hip.ptr(self.fn), hip.ptr(self.normals), hip.ptr(self.areas), st, fl, stream)
         hip.call("t8gpu_hip_subgrid_outer", self.dtype, self.kind, self.rank, self.F, hip.ptr(self.fn), None,
