@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Adaptive 2D acoustic pulse on [0, 1]^2 with far-field boundaries on all four sides (one MI355X): the structure of
+riemann2d_amr.py on a mesh whose sides hold the ambient state through the characteristic far-field condition
+(SynthMesh(..., sides=(("farfield", 0),) * 4)).
+
+Initial state: the ambient state (rho = 1, at rest, p = 1) with a Gaussian pressure pulse (amplitude 0.1, width 0.05) at
+the centre, isentropic in density. The ring it sends out leaves through the sides; what it leaves behind is the residual
+max |p - p_inf| printed at the end -- a reflective wall, or a prescribed-state inflow of the ambient state, leaves more.
+
+    python examples/acoustic_pulse_farfield.py --t-end 1.0 --min-level 5 --max-level 8 --out out/pulse
+    python examples/acoustic_pulse_farfield.py --sides inflow      # the same with a prescribed-state inflow of the ambient state
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from t8gpu_amd import amr, hip, vtk  # noqa: E402
+from t8gpu_amd.solver import PlainSolver  # noqa: E402
+from t8gpu_amd.synth import SynthMesh  # noqa: E402
+
+GAMMA = 1.4
+AMBIENT = (1.0, 1.0)   # rho, p
+SIDES = {"farfield": ("farfield", 0), "inflow": 0, "outflow": "outflow", "wall": "wall"}
+FLUXES = {"kepes": hip.KEPES, "hll": hip.HLL, "hllc": hip.HLLC}
+
+
+def ambient_state():
+    rho, p = AMBIENT
+    return np.array([[rho, 0.0, 0.0, 0.0, p / (GAMMA - 1)]])
+
+
+def initial_state(part, amplitude=0.1, width=0.05):
+    x, y = part.centres[:, 0], part.centres[:, 1]
+    r2 = (x - 0.5) ** 2 + (y - 0.5) ** 2
+    p = AMBIENT[1] * (1 + amplitude * np.exp(-r2 / (width * width)))
+    rho = AMBIENT[0] * (p / AMBIENT[1]) ** (1 / GAMMA)
+    return np.stack([rho, 0 * rho, 0 * rho, 0 * rho, p / (GAMMA - 1)])
+
+
+def pressure(solver):
+    u = solver.state().double().cpu().numpy()
+    return (GAMMA - 1) * (u[4] - 0.5 * (u[1] ** 2 + u[2] ** 2 + u[3] ** 2) / u[0])
+
+
+def cfl_step(solver, cfl):
+    """cfl * finest cell size / max(|v| + c) of the current state (the same rule for every kind of side)"""
+    u = solver.state().double().cpu().numpy()
+    rho = u[0]
+    v = np.sqrt(u[1] ** 2 + u[2] ** 2 + u[3] ** 2) / rho
+    c = np.sqrt(GAMMA * pressure(solver) / rho)
+    return cfl * 0.5 ** solver.part.mesh.finest_level / float((v + c).max())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--t-end", type=float, default=1.0)
+    ap.add_argument("--adapt-every", type=int, default=20)
+    ap.add_argument("--min-level", type=int, default=5)
+    ap.add_argument("--max-level", type=int, default=8)
+    ap.add_argument("--threshold", type=float, default=2.0)
+    ap.add_argument("--cfl", type=float, default=0.35)
+    ap.add_argument("--sides", choices=list(SIDES), default="farfield", help="the kind of all four sides")
+    ap.add_argument("--flux", choices=list(FLUXES), default="kepes")
+    ap.add_argument("--out", default=None, help="directory of the .vtu written at the end (density, energy, momentum)")
+    ap.add_argument("--toy", action="store_true", help="levels 3-5, t_end 0.05 (a quick check)")
+    args = ap.parse_args()
+    if args.toy:
+        args.min_level, args.max_level, args.t_end, args.adapt_every = 3, 5, 0.05, 5
+
+    mesh = SynthMesh(2, args.min_level, args.min_level, sides=(SIDES[args.sides],) * 4)
+    part = mesh.partition()
+    states = ambient_state() if args.sides in ("farfield", "inflow") else None
+    solver = PlainSolver(part, torch.float64, flux_kind=FLUXES[args.flux], mode="fused", state=initial_state(part), inflow_states=states)
+
+    def adapt(s):
+        return amr.adapt(s, args.threshold, args.min_level, args.max_level)[0]
+
+    for _ in range(args.max_level - args.min_level):      # refine around the pulse, then re-evaluate the state
+        solver = adapt(solver)
+        ic = torch.from_numpy(initial_state(solver.part)).to(solver.dtype).cuda()
+        solver.planes[5 * solver.next:5 * solver.next + 5] = ic
+    solver.use_native_stepper()
+    t, it, cells, t_iter = 0.0, 0, 0, 0.0
+    while t < args.t_end - 1e-12:
+        if it % args.adapt_every == 0:
+            if it > 0:
+                solver = adapt(solver)
+                solver.use_native_stepper()
+            dt_cycle = cfl_step(solver, args.cfl)
+        dt = min(dt_cycle, args.t_end - t)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        solver.iterate(dt)
+        torch.cuda.synchronize()
+        t_iter += time.perf_counter() - t0
+        t += dt
+        it += 1
+        cells += solver.N
+        if it % 50 == 0:
+            print(f"it {it:5d}  t {t:.4f}  elements {solver.N:8d}  finest level {solver.part.mesh.finest_level}  dt {dt:.3e}",
+                  flush=True)
+    assert bool(torch.isfinite(solver.state()).all())
+    residual = float(np.abs(pressure(solver) - AMBIENT[1]).max())
+    print(f"t = {t:.4f} after {it} steps, {solver.N} elements; {cells / t_iter / 1e6:.1f} M cell-updates/s (host-synchronised)")
+    print(f"sides {args.sides}, flux {args.flux}: residual max |p - p_inf| = {residual:.3e}")
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        fields = [vtk.get_host_scalar_variable(solver, solver.next, 0, "density"),
+                  vtk.get_host_scalar_variable(solver, solver.next, 4, "energy"),
+                  vtk.get_host_vector_variable(solver, solver.next, (1, 2, 3), "momentum")]
+        print("wrote", vtk.save_variables_to_vtk(solver, fields, os.path.join(args.out, "acoustic_pulse")))
+
+
+if __name__ == "__main__":
+    main()

@@ -77,7 +77,8 @@ int t8gpu_hip_flux_boundary_f64(int flux_kind, int num_faces, int num_boundary_f
                                 double* speed_estimates, void* stream);
 /* The boundary faces with their kinds (t8gpu_host.h: boundary_kinds[B], device copy): walls as above; outflow faces evaluate
  * the interior face flux with the outside state = the inside one; inflow faces with the outside state = the conservative
- * state k of `inflow_table` (t8gpu_hip_plain_inflow_table_*; may be NULL when no face is an inflow face).
+ * state k of `inflow_table` (t8gpu_hip_plain_inflow_table_*; may be NULL when no face is an inflow or far-field face);
+ * far-field faces (ABI 11) with the outside state of the characteristic condition against state k.
  * boundary_kinds = NULL is t8gpu_hip_flux_boundary_*. */
 int t8gpu_hip_flux_boundary_bc_f32(int flux_kind, int num_faces, int num_boundary_faces, int normal_dim,
                                    const int32_t* face_neighbors, const uint8_t* boundary_kinds, const float* inflow_table,
@@ -230,7 +231,11 @@ typedef struct T8gpuPlainPlan {
    * their launches run the one-tile kernels, which give the same bits. */
   const void*    inflow;      /* DEVICE float_type [K][T8GPU_INFLOW_WORDS]                                  */
   int32_t        has_open_faces;
-  int32_t        reserved9;
+  /* FAR-FIELD FACES (ABI 11): 0xFFF8 + k in face_lr is a far-field face against state k of `inflow` (k < 6; the inflow codes are
+   * then 0xFFF0 .. 0xFFF7). has_farfield_faces = 1 (with has_open_faces = 1) selects the _far kernels, which build the outside
+   * state of such a face from the inside state, the face normal and the table row (Riemann invariants); the
+   * table must then hold an entry for every far-field code too. 0 (a zeroed tail): no far-field faces, as before ABI 11. */
+  int32_t        has_farfield_faces;
 } T8gpuPlainPlan;
 
 /* One inflow-table entry: the conservative state (5 values), the 9 per-element KEPES quantities the tile kernels derive from a

@@ -21,16 +21,21 @@ extern "C" {
 /* ---- boundary kinds --------------------------------------------------------------------------
  * boundary_kinds[B] (uint8, one entry per boundary face, in the order of the boundary entries of face_neighbors):
  * 0 reflective wall, 1 outflow (zero gradient: the outside state is the inside one), 2 + k inflow with prescribed
- * conservative state k (k < T8GPU_MAX_INFLOW_STATES). An absent array (NULL) means every boundary face is a wall. */
+ * conservative state k (k < T8GPU_MAX_INFLOW_STATES), 10 + k far field with state k (k < T8GPU_MAX_FARFIELD_STATES: the
+ * Riemann-invariant characteristic condition against inflow state k). An absent array (NULL) means every
+ * boundary face is a wall. Codes of 16 and above are refused. */
 #define T8GPU_BOUNDARY_WALL 0
 #define T8GPU_BOUNDARY_OUTFLOW 1
 #define T8GPU_BOUNDARY_INFLOW 2
 #define T8GPU_MAX_INFLOW_STATES 8
+#define T8GPU_BOUNDARY_FARFIELD 10
+#define T8GPU_MAX_FARFIELD_STATES 6
 
 /* ---- synthetic mesh -------------------------------------------------------------------------- */
 /* periodic != 0: every side periodic, else every side a wall */
 void*   t8gpu_synth_mesh_create(int dim, int base_level, int max_level, double band, double shrink, int periodic);
-/* sides[2 * dim] in the order -x, +x, -y, +y, -z, +z: -1 periodic, 0 wall, 1 outflow, 2 + k inflow state k. A periodic
+/* sides[2 * dim] in the order -x, +x, -y, +y, -z, +z: -1 periodic, 0 wall, 1 outflow, 2 + k inflow state k, 10 + k far field
+ * with state k. A periodic
  * side must be paired with the opposite side of its axis. NULL on invalid parameters (t8gpu_synth_check_sides: 0 valid,
  * 1 a code out of range, 2 an unpaired periodic side). adapt / adapt_by_rounds / partitions keep the sides. */
 void*   t8gpu_synth_mesh_create_sides(int dim, int base_level, int max_level, double band, double shrink, const int* sides);
@@ -95,13 +100,16 @@ void* t8gpu_plan_plain_create(int32_t N, int32_t G, int32_t F, int32_t B, int32_
 void* t8gpu_plan_plain_create_ex(int32_t N, int32_t G, int32_t F, int32_t B, int32_t ndim, const int32_t* face_neighbors,
                                  const double* normals, const double* areas, int32_t tmax, int32_t fcap, int32_t flags);
 /* The same with boundary_kinds[B] (NULL: every boundary face a wall -- what _ex does). An open boundary face (outflow /
- * inflow) is encoded in face_lr as r = 0xFFFE (outflow) or 0xFFF0 + k (inflow k); walls keep 0xFFFF, so tile-local
- * indices stay below 0xFFF0. A cell with an open face never goes into a patch (2D or 3D): it runs through the generic
- * tiles. t8gpu_plan_plain_open_faces tells whether the plan has open faces at all (T8gpuPlainPlan::has_open_faces). */
+ * inflow / far field) is encoded in face_lr as r = 0xFFFE (outflow), 0xFFF0 + k (inflow k) or 0xFFF8 + k (far field k);
+ * walls keep 0xFFFF, so tile-local indices stay below 0xFFF0. A cell with an open face never goes into a patch (2D or 3D):
+ * it runs through the generic tiles. t8gpu_plan_plain_open_faces tells whether the plan has open faces at all
+ * (T8gpuPlainPlan::has_open_faces), t8gpu_plan_plain_farfield_faces whether some of them are far-field faces
+ * (T8gpuPlainPlan::has_farfield_faces). NULL for a kind of 16 or above. */
 void* t8gpu_plan_plain_create_bc(int32_t N, int32_t G, int32_t F, int32_t B, int32_t ndim, const int32_t* face_neighbors,
                                  const double* normals, const double* areas, const uint8_t* boundary_kinds, int32_t tmax,
                                  int32_t fcap, int32_t flags);
 int32_t t8gpu_plan_plain_open_faces(const void* plan);
+int32_t t8gpu_plan_plain_farfield_faces(const void* plan);
 void  t8gpu_plan_plain_destroy(void* plan);
 /* counts[4] = leading patch tiles of the deep / near-boundary / ghost-reading class of tile_order, total */
 void  t8gpu_plan_plain_patch_counts(const void* plan, int32_t* counts);

@@ -58,7 +58,7 @@ def build_hip(force=False):
     """One object per .hip file (compiled in parallel, rebuilt only when the file or a header changed), then one link."""
     from concurrent.futures import ThreadPoolExecutor
     srcs = _glob(os.path.join(CSRC, "hip"), (".hip", ".cpp"))
-    hdrs = _glob(os.path.join(CSRC, "hip"), (".h", ".hpp")) + _glob(os.path.join(ROOT, "include"), (".h",))
+    hdrs = _glob(os.path.join(CSRC, "hip"), (".h", ".hpp", ".inc")) + _glob(os.path.join(ROOT, "include"), (".h",))
     objdir = os.path.join(LIB, "obj")
     os.makedirs(objdir, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

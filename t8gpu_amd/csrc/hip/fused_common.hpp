@@ -163,19 +163,102 @@ T8_DEV void ghost_window_send(const T8gpuPlainPlan& P, int e, const T v[5]) {
 // The r half of a face_lr entry (tile_plan.cpp: boundary_code): a tile-local slot below 0xFFF0, else 0xFFFF reflective wall,
 // 0xFFFE outflow, 0xFFF0 + k inflow state k. The one place that spells the codes; only the OPEN instantiations of the tile
 // kernels decode the open ones (the others see walls only, as before ABI 9).
+// FAR (ABI 11): the plan also has far-field faces, 0xFFF8 + k far-field state k (k < 6); inflow codes are then 0xFFF0..0xFFF7.
+// FAR = false decodes exactly as before ABI 11 (those plans have no far-field codes).
 struct FaceSide {
   int  r;        // slot of the right state in LDS: the neighbour, or l itself at a boundary face
   bool wall;     // reflective wall: the right state is the mirror image of the left one
-  bool open;     // outflow or inflow: no right element to update
+  bool open;     // outflow, inflow or far field: no right element to update
   int  inflow;   // inflow state index, -1 otherwise
+  int  far;      // far-field state index, -1 otherwise (FAR only)
 };
+template <bool FAR = false>
 T8_DEV FaceSide decode_face_side(int l, unsigned r16) {
   FaceSide f;
   f.wall   = r16 == 0xFFFFu;
   f.open   = r16 >= 0xFFF0u && r16 < 0xFFFFu;
-  f.inflow = r16 >= 0xFFF0u && r16 < 0xFFFEu ? static_cast<int>(r16 - 0xFFF0u) : -1;
+  if constexpr (FAR) {
+    f.inflow = r16 >= 0xFFF0u && r16 < 0xFFF8u ? static_cast<int>(r16 - 0xFFF0u) : -1;
+    f.far    = r16 >= 0xFFF8u && r16 < 0xFFFEu ? static_cast<int>(r16 - 0xFFF8u) : -1;
+  } else {
+    f.inflow = r16 >= 0xFFF0u && r16 < 0xFFFEu ? static_cast<int>(r16 - 0xFFF0u) : -1;
+    f.far    = -1;
+  }
   f.r      = r16 >= 0xFFF0u ? l : static_cast<int>(r16);
   return f;
+}
+
+// ---- far-field faces (ABI 11): the Riemann-invariant condition ----------------------------------------
+// The outside state of a far-field face from the inside primitives (ri, vi, pi), the face's outward unit normal n and the
+// far-field state of inflow-table row `row` (its primitives rho, v, p: words 5-9). gamma = 1.4, 2 / (gamma - 1) = 5.
+// Returns what the face takes as its outside state:
+//   kFarTable   supersonic inflow (qi <= -ci): the table row itself -- the bits of an inflow face with that state;
+//   kFarInside  supersonic outflow (qi >= ci), or the guard cb <= 0: the inside state itself -- the bits of an outflow face;
+//   kFarBuilt   subsonic: (rb, vb, pb) from the outgoing invariant qi + 5 ci and the incoming one qf - 5 cf, with the
+//               entropy and tangential velocity of the side the flow comes from (inside if qb > 0, else the far field).
+// Shared by the fused tiers (kernels_fused.hip, fused_tile_body.hpp) and the compat tier (kernels_compat.hip).
+enum FarSide { kFarTable = 0, kFarInside = 1, kFarBuilt = 2 };
+template <class T>
+T8_DEV int farfield_outside(T ri, const T vi[3], T pi, const T n[3], const T* __restrict__ row, T& rb, T vb[3], T& pb) {
+  const T* w  = row + 5;
+  const T  rf = w[0], pf = w[4];
+  const T  vf[3] = {w[1], w[2], w[3]};
+  const T  ci = sqrt(T(1.4) * pi / ri);
+  const T  qi = vi[0] * n[0] + vi[1] * n[1] + vi[2] * n[2];
+  if (qi <= -ci) return kFarTable;
+  if (qi >= ci) return kFarInside;
+  const T cf = sqrt(T(1.4) * pf / rf);
+  const T qf = vf[0] * n[0] + vf[1] * n[1] + vf[2] * n[2];
+  const T rp = qi + T(5) * ci, rm = qf - T(5) * cf;
+  const T qb = T(0.5) * (rp + rm), cb = (rp - rm) / T(10);
+  if (!(cb > T(0))) return kFarInside;
+  const bool in = qb > T(0);
+  const T    rr = in ? ri : rf, cr = in ? ci : cf, dq = qb - (in ? qi : qf);
+  const T    x = cb / cr, x2 = x * x;
+  rb = rr * (x2 * x2 * x);   // isentropic with the reference side's entropy: rho_r (cb / cr)^5
+  pb = rb * cb * cb / T(1.4);
+#pragma unroll
+  for (int k = 0; k < 3; k++) vb[k] = (in ? vi[k] : vf[k]) + dq * n[k];
+  return kFarBuilt;
+}
+// conservative state of the primitives (rho, v, p)
+template <class T>
+T8_DEV void state_from_prim(T rho, const T v[3], T p, T s[5]) {
+  s[0] = rho;
+  s[1] = rho * v[0];
+  s[2] = rho * v[1];
+  s[3] = rho * v[2];
+  s[4] = p / T(0.4) + T(0.5) * rho * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+}
+// The KEPES side: R holds the inside record on entry (a boundary face's right slot is its left one) and the outside record on
+// return -- the table's record, the inside one, or the built state's record by the routine cells use (prim_from_state).
+template <class T, bool TAB>
+T8_DEV void farfield_prim(const T* __restrict__ row, const T n[3], const double* logtab, Prim<T>& R) {
+  const T   vi[3] = {R.vx, R.vy, R.vz};
+  T         rb, vb[3], pb;
+  const int side = farfield_outside<T>(R.rho, vi, R.p, n, row, rb, vb, pb);
+  if (side == kFarTable) {
+    const T* w = row + 5;
+    R.rho = w[0]; R.vx = w[1]; R.vy = w[2]; R.vz = w[3]; R.p = w[4]; R.beta = w[5]; R.lrho = w[6]; R.lbeta = w[7]; R.v0 = w[8];
+  } else if (side == kFarBuilt) {
+    T s[5];
+    state_from_prim<T>(rb, vb, pb, s);
+    R = prim_from_state<T, TAB>(s, logtab);
+  }
+}
+// The conservative side (HLL / HLLC, compat tier): s holds the inside state on entry and the outside state on return.
+template <class T>
+T8_DEV void farfield_state(const T* __restrict__ row, const T n[3], T s[5]) {
+  const Prim<T> q     = prim_from_state<T>(s);   // (only rho, v, p are used)
+  const T       vi[3] = {q.vx, q.vy, q.vz};
+  T             rb, vb[3], pb;
+  const int     side = farfield_outside<T>(q.rho, vi, q.p, n, row, rb, vb, pb);
+  if (side == kFarTable) {
+#pragma unroll
+    for (int k = 0; k < 5; k++) s[k] = row[k];
+  } else if (side == kFarBuilt) {
+    state_from_prim<T>(rb, vb, pb, s);
+  }
 }
 // the conservative state (words 0-4) and the KEPES per-element record (words 5-13) of inflow state k
 template <class T>

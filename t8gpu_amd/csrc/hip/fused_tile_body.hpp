@@ -67,7 +67,9 @@ T8_DEV void load_prim(const T* pe, int LE, int i, Prim<T>& q) {
 // table from global memory instead of an LDS copy (c2: +1 %).
 // OPEN: the plan has outflow / inflow faces (T8gpuPlainPlan::has_open_faces): their codes are decoded (decode_face_side);
 // OPEN = false is the wall-only body, unchanged.
-template <class T, int KIND, int STAGE, bool DICT, int MAXP, bool DENSE = false, bool OPEN = false>
+// FAR (with OPEN): the plan has far-field faces too (T8gpuPlainPlan::has_farfield_faces): their outside state is built by
+// fused_common.hpp: farfield_prim / farfield_state; FAR = false is the body of the OPEN kernels, unchanged.
+template <class T, int KIND, int STAGE, bool DICT, int MAXP, bool DENSE = false, bool OPEN = false, bool FAR = false>
 T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& prev, const FVars<T>& src, const FVars<T>& out,
                             const T* __restrict__ vol, T dt, T* __restrict__ speed) {
   extern __shared__ __attribute__((aligned(16))) double lds_raw[];
@@ -174,12 +176,13 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
     if (fi.valid) {
       const int  l = fi.lr & 0xFFFFu, r16 = fi.lr >> 16;
       bool       wall;
-      int        r, inflow = -1;
+      int        r, inflow = -1, far = -1;
       if constexpr (OPEN) {
-        const FaceSide fs = decode_face_side(l, r16);
+        const FaceSide fs = decode_face_side<FAR>(l, r16);
         wall   = fs.wall;
         r      = fs.r;
         inflow = fs.inflow;
+        far    = fs.far;
       } else {
         wall = r16 == 0xFFFFu;
         r    = wall ? l : r16;
@@ -199,6 +202,11 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
           inflow_prim<T>(P, inflow, R);
         else
           load_prim<T>(pe, LE, r, R);
+        if (FAR && far >= 0) {   // the outside state in xyz, before the component routing below (n = sg * e_axis)
+          const int ax   = wcode >> 1;
+          const T   n[3] = {ax == 0 ? sg : T(0), ax == 1 ? sg : T(0), ax == 2 ? sg : T(0)};
+          farfield_prim<T, kTab>(inflow_entry<T>(P, far), n, lt, R);
+        }
         T uL, vL, wL, uR, vR, wR;
         if ((wcode >> 1) == 0) {
           asm volatile("");
@@ -251,6 +259,7 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
           inflow_prim<T>(P, inflow, R);
         else
           load_prim<T>(pe, LE, r, R);
+        if (FAR && far >= 0) farfield_prim<T, kTab>(inflow_entry<T>(P, far), n, lt, R);
         kepes_prim<T>(L, R, wall, n, t1, t2, gm.w, g, spd);
       } else {
         T sl[5], sr[5];
@@ -264,6 +273,7 @@ T8_DEV void plain_tile_body(const T8gpuPlainPlan& P, int pos, const FVars<T>& pr
 #pragma unroll
           for (int k = 0; k < 5; k++) sr[k] = q[k];
         }
+        if (FAR && far >= 0) farfield_state<T>(inflow_entry<T>(P, far), n, sr);
         hll_face<T>(sl, sr, wall, n, t1, t2, gm.w, g, spd, KIND == 2);
       }
       }
@@ -311,6 +321,16 @@ __global__ __launch_bounds__(256, DENSE ? (sizeof(T) == 8 ? 4 : 5) : 1) void k_p
                                                        T* __restrict__ speed) {
   const int pos = tile_begin + xcd_position(blockIdx.x, gridDim.x);
   plain_tile_body<T, KIND, STAGE, DICT, MAXP, DENSE, OPEN>(P, pos, prev, src, out, vol, dt, speed);
+}
+
+// the same for plans with far-field faces (T8gpuPlainPlan::has_farfield_faces): the OPEN body with far-field faces decoded, under
+// the default register budget (not DENSE: the far-field state would spill there). A kernel of its own name, so that the
+// instantiations of k_plain_fused_p keep their symbols.
+template <class T, int KIND, int STAGE, bool DICT, int MAXP>
+__global__ __launch_bounds__(256, 1) void k_plain_fused_p_far(T8gpuPlainPlan P, int tile_begin, FVars<T> prev, FVars<T> src,
+                                                              FVars<T> out, const T* __restrict__ vol, T dt, T* __restrict__ speed) {
+  const int pos = tile_begin + xcd_position(blockIdx.x, gridDim.x);
+  plain_tile_body<T, KIND, STAGE, DICT, MAXP, false, true, true>(P, pos, prev, src, out, vol, dt, speed);
 }
 
 }  // namespace t8gpu_hip

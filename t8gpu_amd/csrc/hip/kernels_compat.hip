@@ -11,8 +11,10 @@
 #pragma clang fp contract(off)
 
 #include "flux_math.hpp"
+#include "fused_common.hpp"
 #include "stage_kernel_note.hpp"
 #include "t8gpu_hip.h"
+#include "t8gpu_host.h"
 
 namespace t8gpu_hip {
 
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(256) void k_flux_boundary(int F, int B, int ndim, c
 
 // ---- boundary faces with their kinds (open boundaries; not in the reference) ----------------------
 // The wall flux above with a different outside state: outflow = the inside state unmirrored, inflow k = the conservative
-// state of inflow table entry k (t8gpu_hip.h: T8GPU_INFLOW_WORDS).
+// state of inflow table entry k (t8gpu_hip.h: T8GPU_INFLOW_WORDS), far field k = the characteristic state against entry k.
 template <class T, int KIND>
 __global__ __launch_bounds__(256) void k_flux_boundary_bc(int F, int B, int ndim, const int32_t* __restrict__ fn,
                                                           const uint8_t* __restrict__ kinds, const T* __restrict__ inflow,
@@ -108,7 +110,11 @@ __global__ __launch_bounds__(256) void k_flux_boundary_bc(int F, int B, int ndim
   for (int k = 0; k < ndim; k++) n[k] = normals[(size_t)ndim * (F + i) + k];
   T s[5], o[5];
   load5(st, e, s);
-  if (kind >= 2) {
+  if (kind >= T8GPU_BOUNDARY_FARFIELD) {   // far field k: the characteristic condition (fused_common.hpp: farfield_outside)
+#pragma unroll
+    for (int k = 0; k < 5; k++) o[k] = s[k];
+    farfield_state<T>(inflow + T8GPU_INFLOW_WORDS * (kind - T8GPU_BOUNDARY_FARFIELD), n, o);
+  } else if (kind >= 2) {
 #pragma unroll
     for (int k = 0; k < 5; k++) o[k] = inflow[T8GPU_INFLOW_WORDS * (kind - 2) + k];
   } else {
@@ -476,7 +482,7 @@ using namespace t8gpu_hip;
 extern "C" {
 
 const char* t8gpu_hip_last_stage_kernel(void) { return stage_kernel_note().name; }
-int t8gpu_hip_abi_version(void) { return 10; }   // 2: T8gpuPlainPlan.tile_desc; 3: T8gpuSubgridPlan row format (far-cell recipes), n_blocks_addressed, family records; 4: T8gpuPlainPlan.n_patch_tiles; 5: T8gpuPlainPlan.ell holds rows for generic tiles only (tile_desc word 6), patch_dim; 6: T8gpuPlainPlan.n_irregular_tiles; 7: T8gpuPlainPlan ghost window (ghost_buf, send_map, send_list, send_buf, n_owned); 8: t8gpu_hip_plain_geo_frames_* (plan builders must call it); 9: T8gpuPlainPlan open boundaries (inflow, has_open_faces), t8gpu_hip_flux_boundary_bc_*, t8gpu_hip_plain_inflow_table_*; 10: T8gpuSubgridPlan open boundaries (inflow, has_open_faces), t8gpu_hip_subgrid_boundary_bc_*
+int t8gpu_hip_abi_version(void) { return 11; }   // 2: T8gpuPlainPlan.tile_desc; 3: T8gpuSubgridPlan row format (far-cell recipes), n_blocks_addressed, family records; 4: T8gpuPlainPlan.n_patch_tiles; 5: T8gpuPlainPlan.ell holds rows for generic tiles only (tile_desc word 6), patch_dim; 6: T8gpuPlainPlan.n_irregular_tiles; 7: T8gpuPlainPlan ghost window (ghost_buf, send_map, send_list, send_buf, n_owned); 8: t8gpu_hip_plain_geo_frames_* (plan builders must call it); 9: T8gpuPlainPlan open boundaries (inflow, has_open_faces), t8gpu_hip_flux_boundary_bc_*, t8gpu_hip_plain_inflow_table_*; 10: T8gpuSubgridPlan open boundaries (inflow, has_open_faces), t8gpu_hip_subgrid_boundary_bc_*; 11: far-field boundary kinds (T8gpuPlainPlan.has_farfield_faces, face_lr codes 0xFFF8 + k, t8gpu_hip_flux_boundary_bc_* kinds 10..15)
 int t8gpu_hip_device_count(int* count) { return static_cast<int>(hipGetDeviceCount(count)); }
 int t8gpu_hip_set_device(int device) { return static_cast<int>(hipSetDevice(device)); }
 const char* t8gpu_hip_error_string(int code) {

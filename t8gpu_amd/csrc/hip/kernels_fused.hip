@@ -19,138 +19,22 @@
 
 namespace t8gpu_hip {
 
-// OPEN: the plan has outflow / inflow faces (fused_common.hpp: decode_face_side); OPEN = false is the wall-only kernel
 template <class T, int KIND, int STAGE, bool OPEN = false>
 __global__ __launch_bounds__(256) void k_plain_fused(T8gpuPlainPlan P, int tile_begin, FVars<T> prev, FVars<T> src,
                                                      FVars<T> out, const T* __restrict__ vol, T dt,
                                                      T* __restrict__ speed) {
-  extern __shared__ double lds_raw[];
-  T* const      lds = reinterpret_cast<T*>(lds_raw);
-  constexpr int NW  = KIND == 0 ? kPrimWords : 5;  // words per element kept in LDS
-  const int     LE  = plan_slots(P);                 // element slots per LDS plane
-  const int     LF  = P.max_faces;
-  T* const      pe  = lds;                         // [NW][LE]
-  T* const      ff  = lds + (size_t)NW * LE;       // [5][LF]
-  constexpr bool kTab = sizeof(T) == 8 && KIND == 0;   // fp64 KEPES: table-driven logarithms (flux_math.hpp: t8_log_tab)
-  double* const lt  = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(ff + (size_t)5 * LF) + 15) & ~uintptr_t(15));   // 16-byte rows
-  if (kTab) {
-    lt[threadIdx.x] = kLogTab[threadIdx.x];
-    __syncthreads();
-  }
-
-  const int tile = P.tile_order[tile_begin + xcd_position(blockIdx.x, gridDim.x)];
-  const int e0 = P.elem_off[tile], ne = P.elem_off[tile + 1] - e0;
-  const int h0 = P.halo_off[tile], nh = P.halo_off[tile + 1] - h0;
-  const int f0 = P.face_off[tile], nf = P.face_off[tile + 1] - f0;
-  const int tid = threadIdx.x;
-
-  // ---- phase 1: elements -> LDS --------------------------------------------------------------
-  for (int i = tid; i < ne + nh; i += 256) {
-    const int slot = i < ne ? e0 + i : P.halo_ids[h0 + (i - ne)];
-    T         s[5];
-    if (P.ghost_buf) {
-#pragma unroll
-      for (int k = 0; k < 5; k++) s[k] = ghost_window_load<T>(P, src, slot, k);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 5; k++) s[k] = src.p[k][slot];
-    }
-    if (KIND == 0) {
-      const Prim<T> q = prim_from_state<T, kTab>(s, lt);
-      pe[0 * LE + i]  = q.rho;
-      pe[1 * LE + i]  = q.vx;
-      pe[2 * LE + i]  = q.vy;
-      pe[3 * LE + i]  = q.vz;
-      pe[4 * LE + i]  = q.p;
-      pe[5 * LE + i]  = q.beta;
-      pe[6 * LE + i]  = q.lrho;
-      pe[7 * LE + i]  = q.lbeta;
-      pe[8 * LE + i]  = q.v0;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 5; k++) pe[k * LE + i] = s[k];
-    }
-  }
-  __syncthreads();
-
-  // ---- phase 2: faces -----------------------------------------------------------------------
-  using V4 = typename vec4<T>::type;
-  const V4* __restrict__ geo = reinterpret_cast<const V4*>(P.face_geo) + f0;
-  for (int f = tid; f < nf; f += 256) {
-    const uint32_t lr = P.face_lr[f0 + f];
-    const V4       gm = geo[f];
-    const int      l = lr & 0xFFFFu, r16 = lr >> 16;
-    bool           wall;
-    int            r, inflow = -1;
-    if constexpr (OPEN) {
-      const FaceSide fs = decode_face_side(l, r16);
-      wall   = fs.wall;
-      r      = fs.r;
-      inflow = fs.inflow;
-    } else {
-      wall = r16 == 0xFFFFu;
-      r    = wall ? l : r16;
-    }
-    const T        n[3] = {gm.x, gm.y, gm.z};
-    T              t1[3], t2[3], g[5], spd = T(0);
-    face_basis_fast<T>(n, t1, t2);
-    if (KIND == 0) {
-      Prim<T> L, R;
-      L.rho = pe[0 * LE + l]; L.vx = pe[1 * LE + l]; L.vy = pe[2 * LE + l]; L.vz = pe[3 * LE + l]; L.p = pe[4 * LE + l];
-      L.beta = pe[5 * LE + l]; L.lrho = pe[6 * LE + l]; L.lbeta = pe[7 * LE + l]; L.v0 = pe[8 * LE + l];
-      R.rho = pe[0 * LE + r]; R.vx = pe[1 * LE + r]; R.vy = pe[2 * LE + r]; R.vz = pe[3 * LE + r]; R.p = pe[4 * LE + r];
-      R.beta = pe[5 * LE + r]; R.lrho = pe[6 * LE + r]; R.lbeta = pe[7 * LE + r]; R.v0 = pe[8 * LE + r];
-      if (OPEN && inflow >= 0) inflow_prim<T>(P, inflow, R);
-      kepes_prim<T>(L, R, wall, n, t1, t2, gm.w, g, spd);
-    } else {
-      T sl[5], sr[5];
-#pragma unroll
-      for (int k = 0; k < 5; k++) {
-        sl[k] = pe[k * LE + l];
-        sr[k] = pe[k * LE + r];
-      }
-      if (OPEN && inflow >= 0) {
-        const T* q = inflow_entry<T>(P, inflow);
-#pragma unroll
-        for (int k = 0; k < 5; k++) sr[k] = q[k];
-      }
-      hll_face<T>(sl, sr, wall, n, t1, t2, gm.w, g, spd, KIND == 2);
-    }
-    if (speed) {
-      const int orig = P.face_orig[f0 + f];
-      if (orig >= 0) speed[orig] = spd;
-    }
-#pragma unroll
-    for (int k = 0; k < 5; k++) ff[k * LF + f] = g[k];
-  }
-  __syncthreads();
-
-  // ---- phase 3: per-element sum + RK stage (ssp_runge_kutta.inl:30-99) ---------------------------
-  for (int i = tid; i < ne; i += 256) {
-    const int e  = e0 + i;
-    const int c0 = P.csr_off[e], c1 = P.csr_off[e + 1];
-    T         acc[5] = {T(0), T(0), T(0), T(0), T(0)};
-    for (int c = c0; c < c1; c++) {
-      const unsigned ent = P.csr_ent[c];
-      const int      f   = ent & 0x7FFFu;
-      if (ent & 0x8000u) {
-#pragma unroll
-        for (int k = 0; k < 5; k++) acc[k] += ff[k * LF + f];
-      } else {
-#pragma unroll
-        for (int k = 0; k < 5; k++) acc[k] -= ff[k * LF + f];
-      }
-    }
-    const T scale = dt / vol[e];
-    T       res[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-      // (stage 1: prev is the stage's source state, plain_fused_stage() checks it)
-      res[k] = rk_stage_update<T, STAGE>(prev.p[k][e], STAGE == 1 ? prev.p[k][e] : src.p[k][e], scale, acc[k]);
-      out.p[k][e] = res[k];
-    }
-    if (P.send_map) ghost_window_send<T>(P, e, res);
-  }
+  // OPEN: the plan has outflow / inflow faces (fused_common.hpp: decode_face_side); OPEN = false is the wall-only kernel
+  constexpr bool FAR = false;
+#include "plain_fused_body.inc"
+}
+// plans with far-field faces (T8gpuPlainPlan::has_farfield_faces): the OPEN body with far-field faces decoded. A kernel of its own
+// name, so that the instantiations of k_plain_fused keep their symbols.
+template <class T, int KIND, int STAGE>
+__global__ __launch_bounds__(256) void k_plain_fused_far(T8gpuPlainPlan P, int tile_begin, FVars<T> prev, FVars<T> src,
+                                                         FVars<T> out, const T* __restrict__ vol, T dt,
+                                                         T* __restrict__ speed) {
+  constexpr bool OPEN = true, FAR = true;
+#include "plain_fused_body.inc"
 }
 
 }  // namespace t8gpu_hip
@@ -176,6 +60,7 @@ int plain_generic_stage(int kind, int stage, const T8gpuPlainPlan* plan, int til
   //  upload them -- t8gpu_amd/fused.py does not)
   if (!pipelined && (!plan->csr_off || !plan->csr_ent)) return static_cast<int>(hipErrorInvalidValue);
   const bool  open = plan->has_open_faces != 0;   // outflow / inflow faces: the OPEN instantiations
+  const bool  far  = open && plan->has_farfield_faces != 0;   // far-field faces too: the _far kernels
   if (open && !plan->inflow) return static_cast<int>(hipErrorInvalidValue);
   // The persistent, software-pipelined kernel (kernels_fused_persistent.hip) for launches that cover the whole plan.
   // A multi-rank stage is split into tile classes on three streams beside the pack / RCCL / unpack kernels
@@ -195,14 +80,26 @@ int plain_generic_stage(int kind, int stage, const T8gpuPlainPlan* plan, int til
   if (lds > 160 * 1024) return static_cast<int>(hipErrorInvalidValue);
   const bool  dict  = pipelined && plan->geo_idx && plan->geo_table && plan->n_geo > 0;
   // the DENSE register budget (fused_tile_body.hpp) for fp64 KEPES tiles of <= 36 KB with a dictionary and <= 512 faces
-  const bool  dense = dict && !four && kind == 0 && sizeof(T) == 8 && lds - lds_table <= static_cast<size_t>(36) * 1024;
+  // (not for far-field plans: the _far body would spill under that budget -- their tiles take the default one)
+  const bool  dense = !far && dict && !four && kind == 0 && sizeof(T) == 8 && lds - lds_table <= static_cast<size_t>(36) * 1024;
   if (dense) lds -= lds_table;   // (the DENSE kernel reads the logarithm table from global memory)
   return dispatch(
-      [&](auto K, auto S, auto OPEN, auto PIPELINED, auto DICT, auto FOUR, auto DENSE) {
-        if constexpr (!PIPELINED) {
+      [&](auto K, auto S, auto OPEN, auto FAR, auto PIPELINED, auto DICT, auto FOUR, auto DENSE) {
+        if constexpr (FAR && !OPEN) {
+          return static_cast<int>(hipErrorInvalidValue);   // (never: `far` implies `open`)
+        } else if constexpr (!PIPELINED && FAR) {
+          note_stage_kernel<T>(tile_count, "k_plain_fused_far", K, S);
+          return launch(&k_plain_fused_far<T, K, S>, grid, block, lds, s, *plan, tile_begin, fmk<T>(prev), fmk<T>(mid), fmk<T>(out),
+                        volume, dt, speed);
+        } else if constexpr (!PIPELINED) {
           note_stage_kernel<T>(tile_count, "k_plain_fused", K, S, OPEN);
           return launch(&k_plain_fused<T, K, S, OPEN>, grid, block, lds, s, *plan, tile_begin, fmk<T>(prev), fmk<T>(mid), fmk<T>(out),
                         volume, dt, speed);
+        } else if constexpr (FAR) {
+          constexpr int  MAXP = FOUR ? 4 : 2;
+          note_stage_kernel<T>(tile_count, "k_plain_fused_p_far", K, S, DICT, MAXP);
+          return launch(&k_plain_fused_p_far<T, K, S, DICT, MAXP>, grid, block, lds, s, *plan, tile_begin, fmk<T>(prev), fmk<T>(mid),
+                        fmk<T>(out), volume, dt, speed);
         } else {
           constexpr int  MAXP = FOUR ? 4 : 2;
           constexpr bool D    = DENSE && DICT && !FOUR && K == 0 && sizeof(T) == 8;   // (`dense` is never set otherwise)
@@ -211,7 +108,7 @@ int plain_generic_stage(int kind, int stage, const T8gpuPlainPlan* plan, int til
                         fmk<T>(out), volume, dt, speed);
         }
       },
-      kind, stage, open, pipelined, dict, four, dense);
+      kind, stage, open, far, pipelined, dict, four, dense);
 }
 
 // The C-ABI entry: splits the range of tile_order into its patch tiles (kernels_fused_patch.hip) and its generic tiles

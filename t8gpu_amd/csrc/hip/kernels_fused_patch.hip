@@ -283,6 +283,9 @@ int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch
   if (!plan->tile_desc) return static_cast<int>(hipErrorInvalidValue);
   if (!plan_planes_fit_32bit<T>(plan)) return static_cast<int>(hipErrorInvalidValue);
   size_t lds = record_lds<T>(kind, static_cast<size_t>(5) * kPatchFF, 320);
+  // (far-field faces: the generic tiles run k_plain_fused_p_far in a launch of their own -- under the mixed kernel's register
+  //  budget of 3 / 5 workgroups per CU their far-field state spills)
+  if (tile_count > 0 && plan->has_farfield_faces) return -1;
   if (tile_count > 0) {
     // what plain_tile_body<T, K, S, true, 2> takes (kernels_fused.hip: the pipelined kernel with a geometry dictionary, two
     // passes of 256 faces), and its LDS window

@@ -35,7 +35,7 @@ struct Leaf {
 
 struct Mesh {
   int    dim = 2, base = 1, lmax = 1, periodic = 1;
-  // per side (-x, +x, -y, +y, -z, +z): -1 periodic, 0 wall, 1 outflow, 2 + k inflow state k. A periodic side is always
+  // per side (-x, +x, -y, +y, -z, +z): -1 periodic, 0 wall, 1 outflow, 2 + k inflow state k, 10 + k far field k. A periodic side is always
   // paired with the opposite side of its axis (t8gpu_synth_mesh_create_sides checks it); `periodic` = every side periodic.
   int    side[6] = {-1, -1, -1, -1, -1, -1};
   double band = 0, shrink = 1;
@@ -169,7 +169,7 @@ struct Part {
   uvector<int32_t> fn;       // 2F + B      (uvector: sized, then written completely by parallel loops)
   uvector<double>  normals;  // ndim * (F + B)
   uvector<double>  areas;    // F + B
-  std::vector<uint8_t> kinds;  // B: boundary kind of every boundary face (0 wall, 1 outflow, 2 + k inflow k)
+  std::vector<uint8_t> kinds;  // B: boundary kind of every boundary face (0 wall, 1 outflow, 2 + k inflow k, 10 + k far field k)
   std::vector<int32_t> level_diff, nb_offset;
   std::vector<int64_t> ghost_global;
   std::vector<int32_t> ghost_owner;
@@ -372,7 +372,7 @@ void* t8gpu_synth_mesh_create(int dim, int base_level, int max_level, double ban
 int t8gpu_synth_check_sides(int dim, const int* sides) {
   if (dim < 2 || dim > 3 || !sides) return 1;
   for (int f = 0; f < 2 * dim; f++) {
-    if (sides[f] < -1 || sides[f] >= 2 + T8GPU_MAX_INFLOW_STATES) return 1;
+    if (sides[f] < -1 || sides[f] >= T8GPU_BOUNDARY_FARFIELD + T8GPU_MAX_FARFIELD_STATES) return 1;
     if ((sides[f] == -1) != (sides[f ^ 1] == -1)) return 2;   // a periodic side without its opposite side
   }
   return 0;

@@ -97,6 +97,7 @@ struct TilePlan {
   bool    two_classes = false;                         // no deep / near-boundary split of the interior tiles (flag 32)
   const uint8_t* kinds = nullptr;                      // boundary_kinds[B] (null: all walls), read during build() only
   bool    open_faces = false;                          // some boundary face is not a wall
+  bool    farfield_faces = false;                      // some boundary face is a far-field face
   std::vector<Patch>   patches;                        // in element order
   std::vector<int32_t> tile_patch;                     // [ntiles] index into patches, or -1 (generic tile)
   int32_t n_patch_class[3] = {0, 0, 0};                // leading patch tiles of the deep / near / ghost-reading class
@@ -116,10 +117,11 @@ inline int direction_code(const double* n, int ndim) {
   return axis < 0 ? 6 : 2 * axis + (n[axis] > 0.0 ? 1 : 0);
 }
 
-// face_lr code of boundary face b (the r half): 0xFFFF wall, 0xFFFE outflow, 0xFFF0 + k inflow state k. The kernels decode it
+// face_lr code of boundary face b (the r half): 0xFFFF wall, 0xFFFE outflow, 0xFFF0 + k inflow state k, 0xFFF8 + k far field k. The kernels decode it
 // in one place (fused_common.hpp: boundary_side).
 inline uint32_t boundary_code(const TilePlan& P, int32_t b) {
   const int k = P.kinds ? P.kinds[b] : 0;
+  if (k >= T8GPU_BOUNDARY_FARFIELD) return 0xFFF8u + static_cast<uint32_t>(k - T8GPU_BOUNDARY_FARFIELD);   // far field k
   return k == 0 ? 0xFFFFu : (k == 1 ? 0xFFFEu : 0xFFF0u + static_cast<uint32_t>(k - 2));
 }
 
@@ -954,14 +956,16 @@ void* t8gpu_plan_plain_create_bc(int32_t N, int32_t G, int32_t F, int32_t B, int
                                  const double* normals, const double* areas, const uint8_t* kinds, int32_t tmax, int32_t fcap,
                                  int32_t flags) {
   if (N < 0 || F < 0 || B < 0 || ndim < 2 || ndim > 3 || tmax < 1 || tmax > 1024 || fcap < 1) return nullptr;
-  bool open_faces = false;
+  bool open_faces = false, farfield_faces = false;
   for (int32_t b = 0; kinds && b < B; b++) {
-    if (kinds[b] >= 2 + T8GPU_MAX_INFLOW_STATES) return nullptr;
-    open_faces = open_faces || kinds[b] != 0;
+    if (kinds[b] >= T8GPU_BOUNDARY_FARFIELD + T8GPU_MAX_FARFIELD_STATES) return nullptr;
+    open_faces     = open_faces || kinds[b] != 0;
+    farfield_faces = farfield_faces || kinds[b] >= T8GPU_BOUNDARY_FARFIELD;
   }
   TilePlan* P = new TilePlan;
-  P->kinds      = open_faces ? kinds : nullptr;
-  P->open_faces = open_faces;
+  P->kinds          = open_faces ? kinds : nullptr;
+  P->open_faces     = open_faces;
+  P->farfield_faces = farfield_faces;
   P->N = N; P->G = G; P->F = F; P->B = B; P->ndim = ndim; P->tmax = tmax; P->fcap = fcap;
   P->want_patches  = flags & 27;   // bit 0: 2D patches (16 x 16), bit 1: 3D patches (8 x 8 x 4), bit 3: irregular 3D patches too, bit 4: no regular 3D ones
   P->skip_face_geo = (flags & 4) != 0;   // bit 2: no face_geo rows if the plan has a geometry dictionary
@@ -981,6 +985,7 @@ void* t8gpu_plan_plain_create_ex(int32_t N, int32_t G, int32_t F, int32_t B, int
   return t8gpu_plan_plain_create_bc(N, G, F, B, ndim, fn, normals, areas, nullptr, tmax, fcap, flags);
 }
 int32_t t8gpu_plan_plain_open_faces(const void* h) { return static_cast<const TilePlan*>(h)->open_faces ? 1 : 0; }
+int32_t t8gpu_plan_plain_farfield_faces(const void* h) { return static_cast<const TilePlan*>(h)->farfield_faces ? 1 : 0; }
 void* t8gpu_plan_plain_create(int32_t N, int32_t G, int32_t F, int32_t B, int32_t ndim, const int32_t* fn,
                               const double* normals, const double* areas, int32_t tmax, int32_t fcap) {
   return t8gpu_plan_plain_create_ex(N, G, F, B, ndim, fn, normals, areas, tmax, fcap, 0);

@@ -19,8 +19,9 @@ class T8gpuPlainPlan(C.Structure):
         # ABI 7: the ghost window, attached by the multi-rank step driver only (stepper.hip); NULL / 0 here
         ("ghost_buf", C.c_void_p), ("send_map", C.c_void_p), ("send_list", C.c_void_p), ("send_buf", C.c_void_p),
         ("n_owned", C.c_int32), ("reserved7", C.c_int32),
-        # ABI 9: open boundaries -- the inflow table (device, [K][16]) and "the plan has outflow / inflow faces"
-        ("inflow", C.c_void_p), ("has_open_faces", C.c_int32), ("reserved9", C.c_int32)]
+        # ABI 9: open boundaries -- the inflow table (device, [K][16]) and "the plan has outflow / inflow faces";
+        # ABI 11: "... and far-field faces" (the _far kernels)
+        ("inflow", C.c_void_p), ("has_open_faces", C.c_int32), ("has_farfield_faces", C.c_int32)]
 
 
 class PlainPlan:
@@ -197,6 +198,7 @@ class PlainPlan:
         c.patch_dim = self.host.patch_dim
         c.n_slots_addressed = part.N + part.G
         c.has_open_faces = int(self.host.open_faces)
+        c.has_farfield_faces = int(self.host.farfield_faces)
         self.c = c
 
     def attach_inflow(self, table):
@@ -216,6 +218,7 @@ class PlainPlan:
         c.n_geo, c.ell_width = h.geo_table.shape[0], h.ell_width
         c.ntiles, c.max_elems, c.max_halo, c.max_faces, c.max_slots = h.ntiles, h.max_elems, h.max_halo, h.max_faces, h.max_slots
         c.has_open_faces = int(h.open_faces)
+        c.has_farfield_faces = int(h.farfield_faces)
         return c
 
     @staticmethod

@@ -20,6 +20,8 @@ def _lib():
         lib.t8gpu_plan_plain_create_bc.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 4 + [C.c_int32] * 3
         lib.t8gpu_plan_plain_open_faces.restype = C.c_int32
         lib.t8gpu_plan_plain_open_faces.argtypes = [C.c_void_p]
+        lib.t8gpu_plan_plain_farfield_faces.restype = C.c_int32
+        lib.t8gpu_plan_plain_farfield_faces.argtypes = [C.c_void_p]
         lib.t8gpu_plan_plain_patch_counts.argtypes = [C.c_void_p] * 2
         lib.t8gpu_plan_plain_irregular_counts.argtypes = [C.c_void_p] * 2
         lib.t8gpu_plan_plain_patch_dim.argtypes = [C.c_void_p]
@@ -48,7 +50,7 @@ class HostPlainPlan:
         tiles without face records (`tile_patch[t]` = 1), first inside every class of `tile_order` (`n_patch_class`).
         want_face_geo=False: leave `face_geo` (32 bytes per tile face, only read by the kernels that have no geometry
         dictionary) empty when the plan has a dictionary -- at c4 size that is 700 MB of host copying per plan.
-        boundary_kinds[B] (0 wall, 1 outflow, 2 + k inflow k; None: all walls): open faces get their codes in face_lr and keep
+        boundary_kinds[B] (0 wall, 1 outflow, 2 + k inflow k, 10 + k far field k; None: all walls): open faces get their codes in face_lr and keep
         their cells out of patches (t8gpu_host.h: t8gpu_plan_plain_create_bc)."""
         lib = _lib()
         fn = np.ascontiguousarray(face_neighbors, np.int32)
@@ -80,7 +82,8 @@ class HostPlainPlan:
         (self.ntiles, n_halo, n_faces, n_csr, self.max_elems, self.max_halo, self.max_faces,
          self.n_interior) = (int(x) for x in sz[:8])
         self.N, self.F, self.B, self.tmax, self.fcap = N, F, B, tmax, fcap
-        self.open_faces = bool(lib.t8gpu_plan_plain_open_faces(h))     # some boundary face is an outflow / inflow face
+        self.open_faces = bool(lib.t8gpu_plan_plain_open_faces(h))     # some boundary face is an outflow / inflow / far-field face
+        self.farfield_faces = bool(lib.t8gpu_plan_plain_farfield_faces(h))   # ... some of them far-field faces
         self.ell_width, n_geo, self.max_slots, self.n_deep = int(sz[10]), int(sz[11]), int(sz[12]), int(sz[13])
         self.n_ell_rows = int(sz[15])                  # rows exist for the elements of generic tiles only (tile_desc word 6)
         ptrs = (C.c_void_p * 13)()

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import hip, native
+from .synth import FARFIELD
 
 STEP0, STEP1, STEP2, STEP3, FLUXES = range(5)
 
@@ -47,20 +48,26 @@ def boundary_kinds_of(part):
 
 def check_inflow_states(part, inflow_states):
     """The (K, 5) conservative inflow states as float64, or None. Required iff part.boundary_kinds holds an inflow code
-    (2 + k); then K <= 8, every code has its state, and every state is a physical one (rho > 0, p > 0, finite). A partition
-    without inflow faces takes them too (a rank of a partitioned mesh, an adapted mesh: the states travel with the run)."""
-    from .synth import INFLOW, MAX_INFLOW_STATES
+    (2 + k) or a far-field code (10 + k: the far-field state is inflow state k); then K <= 8, every code has its state, and
+    every state is a physical one (rho > 0, p > 0, finite). A partition without inflow or far-field faces takes them too (a
+    rank of a partitioned mesh, an adapted mesh: the states travel with the run)."""
+    from .synth import FARFIELD, INFLOW, MAX_INFLOW_STATES
     kinds = boundary_kinds_of(part)
-    need = 0 if kinds is None or kinds.size == 0 else max(0, int(kinds.max()) - INFLOW + 1)
+    kinds = np.zeros(0, np.uint8) if kinds is None else kinds.astype(np.int64)
+    inflow_k = kinds[(kinds >= INFLOW) & (kinds < FARFIELD)] - INFLOW
+    far_k = kinds[kinds >= FARFIELD] - FARFIELD
+    need = max(int(inflow_k.max()) + 1 if inflow_k.size else 0, int(far_k.max()) + 1 if far_k.size else 0)
     if inflow_states is None:
-        if need:
+        if inflow_k.size:
             raise ValueError(f"the partition has inflow faces (states 0..{need - 1}): inflow_states is required")
+        if far_k.size:
+            raise ValueError(f"the partition has far-field faces (states 0..{need - 1}): inflow_states is required")
         return None
     s = np.array(inflow_states, np.float64, copy=True)
     if s.ndim != 2 or s.shape[1] != 5 or not 1 <= s.shape[0] <= MAX_INFLOW_STATES:
         raise ValueError(f"inflow_states must be a (K, 5) array of conservative states, 1 <= K <= {MAX_INFLOW_STATES}")
     if s.shape[0] < need:
-        raise ValueError(f"the partition uses inflow state {need - 1}, inflow_states has {s.shape[0]}")
+        raise ValueError(f"the partition uses inflow / far-field state {need - 1}, inflow_states has {s.shape[0]}")
     if not np.all(np.isfinite(s)):
         raise ValueError("inflow_states must be finite")
     p = 0.4 * (s[:, 4] - 0.5 * (s[:, 1] ** 2 + s[:, 2] ** 2 + s[:, 3] ** 2) / np.where(s[:, 0] > 0, s[:, 0], 1.0))
@@ -184,8 +191,10 @@ class _Solver:
 class PlainSolver(_Solver):
     """Plain elements. mode = "compat": reference data flow (face kernel + atomics, RK kernel);
     mode = "fused": tile kernels (flux + RK in one pass, no flux planes in HBM).
-    Boundary faces follow part.boundary_kinds (0 wall, 1 outflow, 2 + k inflow with state k; absent: walls);
-    inflow_states = (K, 5) conservative states, required iff some face is an inflow face."""
+    Boundary faces follow part.boundary_kinds (0 wall, 1 outflow, 2 + k inflow with state k, 10 + k far field against state k;
+    absent: walls). A far-field face takes its outside state from the Riemann invariants: the outgoing one from the inside
+    cell, the incoming one from state k; it switches by itself between inflow and outflow, subsonic and supersonic
+    (DESIGN.md §4). inflow_states = (K, 5) conservative states, required iff some face is an inflow or far-field face."""
     _native_stepper = native.NativeStepper
 
     def __init__(self, part, dtype=torch.float64, flux_kind=hip.KEPES, mode="compat", capacity=None, state=None,
@@ -291,12 +300,15 @@ class SubgridSolver(_Solver):
     open_boundaries=True: boundary faces follow part.boundary_kinds (0 wall, 1 outflow, 2 + k inflow with state k; absent:
     walls), every subcell on an open face with its own sub-face flux; inflow_states = (K, 5) conservative states, required iff
     some face is an inflow face. A partition without open faces takes it too (a rank that owns no boundary, an adapted mesh).
-    By default a partition with open faces is refused."""
+    By default a partition with open faces is refused. Far-field faces (10 + k) are not supported for Subgrid blocks."""
     _native_stepper = native.NativeSubgridStepper
 
     def __init__(self, part, dtype=torch.float32, flux_kind=hip.KEPES, mode="compat", state=None, open_boundaries=False,
                  inflow_states=None):
         kinds = boundary_kinds_of(part)
+        if kinds is not None and np.any(kinds >= FARFIELD):
+            raise ValueError("SubgridSolver does not support far-field boundary faces: far-field kinds (10 + k) are not supported "
+                             "for Subgrid blocks (use outflow or inflow sides, or a PlainSolver)")
         if not open_boundaries and kinds is not None and np.any(kinds != 0):
             raise ValueError("SubgridSolver without open_boundaries=True takes walls only: the partition has outflow / inflow "
                              "boundary faces (pass open_boundaries=True and, for inflow faces, inflow_states)")

@@ -78,23 +78,41 @@ def _p(a):
 
 WALL, OUTFLOW, INFLOW = 0, 1, 2          # boundary_kinds codes (t8gpu_host.h); inflow state k has code INFLOW + k
 MAX_INFLOW_STATES = 8
+FARFIELD, MAX_FARFIELD_STATES = 10, 6    # far field against state k has code FARFIELD + k
 _SIDE_CODES = {"periodic": -1, "wall": WALL, "outflow": OUTFLOW}
+_SIDE_SPELLINGS = ("'periodic', 'wall', 'outflow', an inflow state index 0..7 or ('farfield', k) with k in 0..5")
+
+
+def boundary_code(s):
+    """The boundary kind of one open or walled side spec: "wall" 0, "outflow" 1, int k -> inflow state k (2 + k),
+    ("farfield", k) -> far field against state k (10 + k); None for anything else ("periodic" included)."""
+    if isinstance(s, str):
+        return _SIDE_CODES.get(s) if s != "periodic" else None
+    if isinstance(s, (int, np.integer)) and not isinstance(s, bool):
+        return INFLOW + int(s) if 0 <= int(s) < MAX_INFLOW_STATES else None
+    if isinstance(s, tuple) and len(s) == 2 and isinstance(s[0], str) and s[0] == "farfield":
+        k = s[1]
+        if isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 0 <= int(k) < MAX_FARFIELD_STATES:
+            return FARFIELD + int(k)
+    return None
 
 
 def side_codes(dim, sides):
     """sides[2 * dim] (order -x, +x, -y, +y, -z, +z) as provider codes: "periodic" -1, "wall" 0, "outflow" 1, int k -> inflow
-    state k (2 + k). Raises ValueError on anything else and on a periodic side whose opposite side is not periodic."""
+    state k (2 + k), ("farfield", k) -> far field against state k (10 + k, k < 6). Raises ValueError on anything else and on
+    a periodic side whose opposite side is not periodic."""
     sides = tuple(sides)
     if len(sides) != 2 * dim:
         raise ValueError(f"sides needs {2 * dim} entries (-x, +x, -y, +y{', -z, +z' if dim == 3 else ''}), got {len(sides)}")
     codes = []
     for s in sides:
-        if isinstance(s, str) and s in _SIDE_CODES:
-            codes.append(_SIDE_CODES[s])
-        elif isinstance(s, (int, np.integer)) and not isinstance(s, bool) and 0 <= int(s) < MAX_INFLOW_STATES:
-            codes.append(INFLOW + int(s))
-        else:
-            raise ValueError(f"invalid side {s!r}: 'periodic', 'wall', 'outflow' or an inflow state index 0..{MAX_INFLOW_STATES - 1}")
+        if isinstance(s, str) and s == "periodic":
+            codes.append(-1)
+            continue
+        c = boundary_code(s)
+        if c is None:
+            raise ValueError(f"invalid side {s!r}: {_SIDE_SPELLINGS}")
+        codes.append(c)
     for a in range(dim):
         if (codes[2 * a] == -1) != (codes[2 * a + 1] == -1):
             raise ValueError(f"side {'xyz'[a]}: a periodic side must be paired with the opposite side of its axis")
@@ -128,7 +146,7 @@ class SynthMesh:
 
     @property
     def sides(self):
-        """provider codes of the 2 * dim sides (-1 periodic, 0 wall, 1 outflow, 2 + k inflow k)"""
+        """provider codes of the 2 * dim sides (-1 periodic, 0 wall, 1 outflow, 2 + k inflow k, 10 + k far field k)"""
         out = np.zeros(6, np.int32)
         n = lib().t8gpu_synth_mesh_sides(self._h, _p(out))
         return out[:n]
@@ -206,7 +224,8 @@ class Partition:
         self.areas = _view(ptrs[2], self.F + self.B, np.float64, owner)
         self.level_diff = _view(ptrs[3], self.F, np.int32, owner) if subgrid else None
         self.nb_offset = _view(ptrs[4], dim * self.F, np.int32, owner) if subgrid else None
-        # boundary_kinds[B]: 0 wall, 1 outflow, 2 + k inflow state k (t8gpu_host.h), in the order of the boundary faces
+        # boundary_kinds[B]: 0 wall, 1 outflow, 2 + k inflow state k, 10 + k far field k (t8gpu_host.h), in the order of the
+        # boundary faces
         self.boundary_kinds = _view(lib().t8gpu_synth_part_boundary_kinds(h), self.B, np.uint8, owner)
         tot = self.N + self.G
         self.levels = np.empty(tot, np.int32)                # (np.empty: the provider overwrites every entry)

@@ -16,6 +16,27 @@ numbered along the Morton curve of their cells.
 """
 import numpy as np
 
+from .synth import boundary_code
+
+SIDE_NAMES = ("-x (inner radius)", "+x (outer radius)", "-y", "+y", "-z", "+z")
+
+
+def side_kinds(sides):
+    """sides[6] in reference-cube order (-x, +x, -y, +y, -z, +z; under shell_map -x is the inner radius and +x the outer) as
+    boundary_kinds codes: "wall" 0, "outflow" 1, int k -> inflow state k (2 + k), ("farfield", k) -> far field against
+    state k (10 + k). Raises ValueError on anything else."""
+    sides = tuple(sides)
+    if len(sides) != 6:
+        raise ValueError(f"sides needs 6 entries (-x, +x, -y, +y, -z, +z), got {len(sides)}")
+    codes = []
+    for name, spec in zip(SIDE_NAMES, sides):
+        c = boundary_code(spec)
+        if c is None:
+            raise ValueError(f"invalid side {spec!r} at {name}: 'wall', 'outflow', an inflow state index 0..7 or ('farfield', k) "
+                             "with k in 0..5")
+        codes.append(c)
+    return np.array(codes, np.uint8)
+
 
 def _morton3(i, j, k, bits):
     m = np.zeros_like(i, dtype=np.int64)
@@ -40,9 +61,14 @@ def wavy_map(x, y, z):
 
 
 class PrismHexMesh:
-    """Global mesh. split: "all" | "none" | "checker" | float (fraction of columns, seeded)."""
+    """Global mesh. split: "all" | "none" | "checker" | float (fraction of columns, seeded).
+    sides: None (every boundary face a wall: boundary_kinds = None) or one entry per side of the reference cube, see
+    side_kinds; `boundary_side[B]` is the side (0 -x .. 5 +z) of every boundary face, `boundary_kinds[B]` its kind."""
 
-    def __init__(self, n, split="checker", mapping=shell_map, periodic=False, seed=12345):
+    def __init__(self, n, split="checker", mapping=shell_map, periodic=False, seed=12345, sides=None):
+        kinds_of_side = None if sides is None else side_kinds(sides)
+        if kinds_of_side is not None and periodic:
+            raise ValueError("a periodic mesh has no boundary sides")
         nx, ny, nz = (n, n, n) if np.isscalar(n) else n
         self.n, self.periodic, self.dim = (nx, ny, nz), bool(periodic), 3
         bits = int(np.ceil(np.log2(max(nx, ny, nz))))
@@ -84,13 +110,14 @@ class PrismHexMesh:
         def tri(v0, v1, v2):
             return 0.5 * np.cross(v1 - v0, v2 - v0), (v0 + v1 + v2) / 3.0
 
-        faces_l, faces_r, avec, cen = [], [], [], []
+        faces_l, faces_r, avec, cen, fside = [], [], [], [], []
 
-        def add(mask, left, right, a, c):
+        def add(mask, left, right, a, c, side=-1):   # side: of the reference cube, for boundary faces (right None)
             faces_l.append(left[mask])
             faces_r.append(right[mask] if right is not None else np.full(int(mask.sum()), -1, np.int64))
             avec.append(a[mask])
             cen.append(c[mask])
+            fside.append(np.full(int(mask.sum()), side, np.int8))
 
         full = np.ones_like(S)
         # +x faces (area vector along +x), owner: hi of this cell; neighbour: lo of cell i+1
@@ -98,41 +125,42 @@ class PrismHexMesh:
         nb = lo[(I + 1) % nx, J, K]
         inner = full if periodic else (I + 1 < nx)
         add(inner, hi, nb, a, c)
-        add(~inner, hi, None, a, c)
+        add(~inner, hi, None, a, c, 1)
         # +y faces (loop chosen so that the area vector points along +y)
         a, c = quad(V(I, J + 1, K), V(I, J + 1, K + 1), V(I + 1, J + 1, K + 1), V(I + 1, J + 1, K))
         nb = lo[I, (J + 1) % ny, K]
         inner = full if periodic else (J + 1 < ny)
         add(inner, hi, nb, a, c)
-        add(~inner, hi, None, a, c)
+        add(~inner, hi, None, a, c, 3)
         # +z faces: one quad for a hexahedron, two triangles for a split cell
         inner = full if periodic else (K + 1 < nz)
         Kp = (K + 1) % nz
         a, c = quad(V(I, J, K + 1), V(I + 1, J, K + 1), V(I + 1, J + 1, K + 1), V(I, J + 1, K + 1))
         add(inner & ~S, lo, lo[I, J, Kp], a, c)
-        add(~inner & ~S, lo, None, a, c)
+        add(~inner & ~S, lo, None, a, c, 5)
         a, c = tri(V(I, J, K + 1), V(I + 1, J, K + 1), V(I, J + 1, K + 1))
         add(inner & S, lo, lo[I, J, Kp], a, c)
-        add(~inner & S, lo, None, a, c)
+        add(~inner & S, lo, None, a, c, 5)
         a, c = tri(V(I + 1, J + 1, K + 1), V(I, J + 1, K + 1), V(I + 1, J, K + 1))
         add(inner & S, hi, hi[I, J, Kp], a, c)
-        add(~inner & S, hi, None, a, c)
+        add(~inner & S, hi, None, a, c, 5)
         # the diagonal of a split cell: from T0 to T1
         a, c = quad(V(I + 1, J, K), V(I, J + 1, K), V(I, J + 1, K + 1), V(I + 1, J, K + 1))
         add(S, lo, hi, a, c)
         if not periodic:  # the three low walls; area vectors of the same loops as above, pointing outward (-)
             a, c = quad(V(I, J, K), V(I, J + 1, K), V(I, J + 1, K + 1), V(I, J, K + 1))
-            add(I == 0, lo, None, -a, c)
+            add(I == 0, lo, None, -a, c, 0)
             a, c = quad(V(I, J, K), V(I, J, K + 1), V(I + 1, J, K + 1), V(I + 1, J, K))
-            add(J == 0, lo, None, -a, c)
+            add(J == 0, lo, None, -a, c, 2)
             a, c = quad(V(I, J, K), V(I + 1, J, K), V(I + 1, J + 1, K), V(I, J + 1, K))
-            add((K == 0) & ~S, lo, None, -a, c)
+            add((K == 0) & ~S, lo, None, -a, c, 4)
             a, c = tri(V(I, J, K), V(I + 1, J, K), V(I, J + 1, K))
-            add((K == 0) & S, lo, None, -a, c)
+            add((K == 0) & S, lo, None, -a, c, 4)
             a, c = tri(V(I + 1, J + 1, K), V(I, J + 1, K), V(I + 1, J, K))
-            add((K == 0) & S, hi, None, -a, c)
+            add((K == 0) & S, hi, None, -a, c, 4)
         L, R = np.concatenate(faces_l), np.concatenate(faces_r)
         A, C = np.concatenate(avec), np.concatenate(cen)
+        Sd = np.concatenate(fside)
         # the reference lists an interior face by the lower index, with that element's outward normal
         swap = (R >= 0) & (R < L)
         L, R = np.where(swap, R, L), np.where(swap, L, R)
@@ -141,6 +169,9 @@ class PrismHexMesh:
         key = np.argsort(np.where(interior, L, L + self.num_elements), kind="stable")   # interior by left element, then walls
         L, R, A, C = L[key], R[key], A[key], C[key]
         self.F, self.B = int(interior.sum()), int((~interior).sum())
+        self.boundary_side = Sd[key][self.F:].astype(np.uint8)
+        assert self.B == 0 or self.boundary_side.max() < 6
+        self.boundary_kinds = None if kinds_of_side is None else kinds_of_side[self.boundary_side]
         self.face_left, self.face_right = L, R
         self.area_vec, self.face_centroid = A, C
         # volumes and centres from the divergence theorem over each element's faces
@@ -225,7 +256,9 @@ class UnstructuredPartition:
         fn[0: 2 * self.F: 2], fn[1: 2 * self.F: 2] = local(li), local(ri)
         fn[2 * self.F:] = local(L[F:][keep_b])
         self.face_neighbors = fn
-        self.boundary_kinds = None             # (no boundary kinds from this provider: every boundary face is a wall)
+        # boundary_kinds[B]: the mesh's kinds of this rank's boundary faces (None: the mesh has no sides -- every face a wall)
+        mk = getattr(mesh, "boundary_kinds", None)
+        self.boundary_kinds = None if mk is None else np.ascontiguousarray(mk[keep_b])
         A = np.concatenate([mesh.area_vec[:F][keep_i], mesh.area_vec[F:][keep_b]])
         area = np.linalg.norm(A, axis=1)
         self.areas = area
@@ -278,12 +311,14 @@ class TetHexMesh:
     tets: "blocks" (2x2x2 blocks of cells alternate between the two kinds: many interfaces), "half" (x < 1/2),
     "all", "none", or a boolean array [nx, ny, nz]. Faces are matched through their vertex sets, area vectors come
     from the vertex loops of the mapped geometry (every element closed to rounding), volumes and the listing order as
-    in PrismHexMesh. Elements are numbered along the Morton curve of their cells."""
+    in PrismHexMesh. Elements are numbered along the Morton curve of their cells. sides, boundary_side and boundary_kinds
+    as in PrismHexMesh."""
 
     # Kuhn tetrahedra: one per permutation of the axes, vertices p0 = (0,0,0), p0 + e_a, p0 + e_a + e_b, (1,1,1)
     _PERMS = [(0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)]
 
-    def __init__(self, n, tets="blocks", mapping=shell_map):
+    def __init__(self, n, tets="blocks", mapping=shell_map, sides=None):
+        kinds_of_side = None if sides is None else side_kinds(sides)
         nx, ny, nz = (n, n, n) if np.isscalar(n) else n
         self.n, self.periodic, self.dim = (nx, ny, nz), False, 3
         bits = int(np.ceil(np.log2(max(nx, ny, nz))))
@@ -368,9 +403,20 @@ class TetHexMesh:
         R = np.concatenate([np.where(lo_first, b, a), np.full(int(single.sum()), -1, np.int64)])
         Avec = np.concatenate([np.where(lo_first[:, None], As[i0], As[i0 + 1]), As[single]])   # outward from the listed element
         Cen = np.concatenate([Cs[i0], Cs[single]])
+        Kb = ks[single][:, :3]            # three vertices of every boundary face (a triangle's fourth key is a pad)
         self.F, self.B = int(i0.size), int(single.sum())
         srt = np.argsort(np.where(R >= 0, L, L + self.num_elements), kind="stable")           # interior by left element, then walls
         self.face_left, self.face_right, self.area_vec, self.face_centroid = L[srt], R[srt], Avec[srt], Cen[srt]
+        # the side of the unit cube every boundary face lies on, from its vertices in index space (boundary faces are the last
+        # B entries before and after the sort)
+        Kb = Kb[srt[self.F:] - self.F]
+        vi, vj, vk = Kb // ((ny + 1) * (nz + 1)), (Kb // (nz + 1)) % (ny + 1), Kb % (nz + 1)
+        side = np.full(self.B, 255, np.uint8)
+        for sd, (ax, val) in enumerate(((vi, 0), (vi, nx), (vj, 0), (vj, ny), (vk, 0), (vk, nz))):
+            side[np.all(ax == val, axis=1)] = sd
+        assert self.B == 0 or side.max() < 6
+        self.boundary_side = side
+        self.boundary_kinds = None if kinds_of_side is None else kinds_of_side[side]
         L, R, Avec, Cen = self.face_left, self.face_right, self.area_vec, self.face_centroid
         # every wall face lies on the boundary of the unit cube (checked in index space through its vertices)
         vol = np.zeros(self.num_elements)
