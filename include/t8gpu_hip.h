@@ -138,6 +138,17 @@ int t8gpu_hip_subgrid_boundary_bc_f64(int flux_kind, int rank, int num_faces, in
                                       const int32_t* face_neighbors, const uint8_t* boundary_kinds, const double* inflow_table,
                                       const double* face_normals, const double* face_surfaces, T8gpuVars_f64 state,
                                       T8gpuVars_f64 fluxes, void* stream);
+/* The same with far-field faces as well (ABI 12): kinds 10 + k take the outside state of the characteristic condition against
+ * state k of `inflow_table`, per sub-face from the inside subcell and the block face's outward normal. Kinds of 9
+ * and below as t8gpu_hip_subgrid_boundary_bc_*, which keeps its kernel for plans without far-field faces. */
+int t8gpu_hip_subgrid_boundary_far_f32(int flux_kind, int rank, int num_faces, int num_boundary_faces,
+                                       const int32_t* face_neighbors, const uint8_t* boundary_kinds, const float* inflow_table,
+                                       const float* face_normals, const float* face_surfaces, T8gpuVars_f32 state,
+                                       T8gpuVars_f32 fluxes, void* stream);
+int t8gpu_hip_subgrid_boundary_far_f64(int flux_kind, int rank, int num_faces, int num_boundary_faces,
+                                       const int32_t* face_neighbors, const uint8_t* boundary_kinds, const double* inflow_table,
+                                       const double* face_normals, const double* face_surfaces, T8gpuVars_f64 state,
+                                       T8gpuVars_f64 fluxes, void* stream);
 
 /* timestepping::subgrid::SSP_3RK_step{1,2,3}<V,Subgrid><<<N, block_size>>>, ssp_runge_kutta.inl:101-221
  * (per-subcell volume = volumes[e] / Subgrid::size). */
@@ -410,7 +421,12 @@ typedef struct T8gpuSubgridPlan {
    * inflow code of the plan. No launch writes it. No family holds a block with an open face. */
   const void*    inflow;        /* DEVICE float_type [K][T8GPU_INFLOW_WORDS] */
   int32_t        has_open_faces;
-  int32_t        reserved10;
+  /* FAR-FIELD FACES (ABI 12): a plan built by t8gpu_plan_subgrid_create_far may hold kinds 10 + k in the same bits: a far-field
+   * face against state k of `inflow` (k < 6). has_farfield_faces = 1 (with has_open_faces = 1) selects the _far kernels, whose
+   * block algorithm builds the outside state of every such sub-face from the inside subcell, the outward normal +-e_axis and
+   * the table row (Riemann invariants); the table must then hold an entry for every far-field code too. 0 (a
+   * zeroed tail): no far-field faces, as before ABI 12. */
+  int32_t        has_farfield_faces;
 } T8gpuSubgridPlan;
 
 /* block_begin/block_count select a range of block_order (0, num_elements = everything; [0, n_interior_blocks)

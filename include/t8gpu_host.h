@@ -158,6 +158,15 @@ void* t8gpu_plan_subgrid_create_bc(int32_t N, int32_t F, int32_t B, int32_t rank
                                    const int32_t* face_level_difference, const int32_t* face_neighbor_offset,
                                    const double* normals, const uint8_t* boundary_kinds);
 int32_t t8gpu_plan_subgrid_open_faces(const void* plan);
+/* The same with far-field kinds as well: boundary_kinds[B] in 0 .. 15, 10 + k = far field against state k
+ * (k < T8GPU_MAX_FARFIELD_STATES), in the same bits 23-26 of the same records; 16 and above are refused (NULL). With kinds
+ * of 9 and below the plan is byte for byte the plan of t8gpu_plan_subgrid_create_bc, which keeps refusing kinds above 9. A
+ * block with a far-field face never joins a family either. t8gpu_plan_subgrid_farfield_faces tells whether some owned block
+ * has a far-field face (T8gpuSubgridPlan::has_farfield_faces). */
+void* t8gpu_plan_subgrid_create_far(int32_t N, int32_t F, int32_t B, int32_t rank, const int32_t* face_neighbors,
+                                    const int32_t* face_level_difference, const int32_t* face_neighbor_offset,
+                                    const double* normals, const uint8_t* boundary_kinds);
+int32_t t8gpu_plan_subgrid_farfield_faces(const void* plan);
 void  t8gpu_plan_subgrid_destroy(void* plan);
 /* sizes[8] = {n_entries, max faces per block, F + B, n_interior_blocks, n_deep_blocks, 1 + largest block index referred to
  * (owned and ghost blocks), n_families, n_rest} */

@@ -228,7 +228,8 @@ def adapt_subgrid(solver, threshold=0.02, min_level=1, max_level=6, family_membe
     new_part = new_mesh.partition(0, 1, subgrid=True)
     S = solver.S
     new = SubgridSolver(new_part, solver.dtype, flux_kind=solver.kind, mode=solver.mode, state=np.zeros((5, new_part.N * S)),
-                        open_boundaries=solver.open_boundaries, inflow_states=solver.inflow_states)
+                        open_boundaries=solver.open_boundaries, inflow_states=solver.inflow_states,
+                        farfield=solver.farfield)
     new.next, new.prev = solver.next, solver.prev
     ad = torch.from_numpy(adapt_data).cuda()
     hip.call("t8gpu_hip_subgrid_adapt_variables_and_volume", solver.dtype, solver.rank, new_part.N, hip.ptr(ad),
@@ -260,7 +261,8 @@ class PartitionedSubgridAdapt(_Repartition):
         self.new_part = self.new_mesh.partition(self.rank, self.world, subgrid=True)
         tot = self.new_part.N + self.new_part.G
         self.new_solver = SubgridSolver(self.new_part, dtype, flux_kind=solver.kind, mode=solver.mode, state=np.zeros((5, tot * S)),
-                                        open_boundaries=solver.open_boundaries, inflow_states=solver.inflow_states)
+                                        open_boundaries=solver.open_boundaries, inflow_states=solver.inflow_states,
+                                        farfield=solver.farfield)
         self.new_solver.next, self.new_solver.prev = solver.next, solver.prev
         w = 5 * S + 1
         self.sendbufs, self.recvbufs = {}, {}

@@ -246,9 +246,10 @@ T8_DEV void farfield_prim(const T* __restrict__ row, const T n[3], const double*
     R = prim_from_state<T, TAB>(s, logtab);
   }
 }
-// The conservative side (HLL / HLLC, compat tier): s holds the inside state on entry and the outside state on return.
+// The conservative side (HLL / HLLC, compat tier, Subgrid blocks): s holds the inside state on entry and the outside state on
+// return. Returns the FarSide (kFarInside: s is untouched -- a caller that holds the inside cell's record keeps that).
 template <class T>
-T8_DEV void farfield_state(const T* __restrict__ row, const T n[3], T s[5]) {
+T8_DEV int farfield_state(const T* __restrict__ row, const T n[3], T s[5]) {
   const Prim<T> q     = prim_from_state<T>(s);   // (only rho, v, p are used)
   const T       vi[3] = {q.vx, q.vy, q.vz};
   T             rb, vb[3], pb;
@@ -259,6 +260,7 @@ T8_DEV void farfield_state(const T* __restrict__ row, const T n[3], T s[5]) {
   } else if (side == kFarBuilt) {
     state_from_prim<T>(rb, vb, pb, s);
   }
+  return side;
 }
 // the conservative state (words 0-4) and the KEPES per-element record (words 5-13) of inflow state k
 template <class T>

@@ -332,6 +332,48 @@ __global__ __launch_bounds__(64) void k_subgrid_boundary_bc(int F, int B, const 
   for (int k = 0; k < 5; k++) gadd(&fl.p[k][li], -g[k] * surface);
 }
 
+// The same with far-field faces (kinds 10 + k) as well: the outside state of every sub-face from the characteristic condition
+// against table entry k, the inside subcell and the block face's outward normal (fused_common.hpp: farfield_state, the routine
+// of k_flux_boundary_bc). A kernel of its own: k_subgrid_boundary_bc keeps its code for plans without far-field faces.
+template <class T, int KIND, int RANK>
+__global__ __launch_bounds__(64) void k_subgrid_boundary_far(int F, int B, const int32_t* __restrict__ fn,
+                                                             const uint8_t* __restrict__ kinds, const T* __restrict__ inflow,
+                                                             const T* __restrict__ normals, const T* __restrict__ areas,
+                                                             Vars<T> st, Vars<T> fl) {
+  constexpr int S  = RANK == 3 ? 64 : 16;
+  constexpr int SF = RANK == 3 ? 16 : 4;
+  const int     f  = blockIdx.x * (64 / SF) + threadIdx.x / SF;
+  if (f >= B) return;
+  const int    t    = threadIdx.x % SF;
+  const int    i    = t % 4, j = t / 4;
+  const size_t slot = (size_t)F + f;
+  const int    l    = fn[2 * (size_t)F + f];
+  const int    kind = kinds[f];
+  const int    off[3] = {0, 0, 0};
+  T n[3] = {T(0), T(0), T(0.0)};
+  for (int d = 0; d < RANK; d++) n[d] = normals[(size_t)RANK * slot + d];
+  T t1[3], t2[3];
+  face_basis<T>(n, t1, t2);
+  int lflat, rflat;
+  sg_face_cells<T, RANK>(n, off, 2, i, j, lflat, rflat);
+  const size_t li = (size_t)l * S + lflat;
+  T            sl[5], so[5], Ff[5], g[5], spd;
+  load5(st, li, sl);
+#pragma unroll
+  for (int k = 0; k < 5; k++) so[k] = sl[k];
+  if (kind >= T8GPU_BOUNDARY_FARFIELD) {
+    farfield_state<T>(inflow + T8GPU_INFLOW_WORDS * (kind - T8GPU_BOUNDARY_FARFIELD), n, so);
+  } else if (kind >= 2) {
+#pragma unroll
+    for (int k = 0; k < 5; k++) so[k] = inflow[T8GPU_INFLOW_WORDS * (kind - 2) + k];
+  }
+  face_frame_flux_ref<T, KIND>(n, t1, t2, sl, so, kind == 0, Ff, spd);
+  from_face_frame<T>(n, t1, t2, Ff, g);
+  const T surface = areas[slot] / static_cast<T>(SF);
+#pragma unroll
+  for (int k = 0; k < 5; k++) gadd(&fl.p[k][li], -g[k] * surface);
+}
+
 // ---- launchers ------------------------------------------------------------------------------------
 template <class T, class V>
 Vars<T> mk(const V& v) {
@@ -466,6 +508,27 @@ int subgrid_boundary_bc(int kind, int rank, int F, int B, const int32_t* fn, con
   return launch_status();
 }
 
+// kinds 0 .. 15 (far-field faces too): k_subgrid_boundary_far
+template <class T, class V>
+int subgrid_boundary_far(int kind, int rank, int F, int B, const int32_t* fn, const uint8_t* kinds, const T* inflow, const T* normals,
+                         const T* areas, V st, V fl, void* stream) {
+  if (!kinds) return subgrid_faces<T, true, V>(kind, rank, F, B, fn, nullptr, nullptr, nullptr, normals, areas, st, fl, stream);
+  if (B <= 0) return 0;
+  if ((rank != 2 && rank != 3) || (kind < 0 || kind > 2)) return static_cast<int>(hipErrorInvalidValue);
+  hipStream_t s   = static_cast<hipStream_t>(stream);
+  const int   fpb = rank == 3 ? 4 : 16;
+  const dim3  block(64), grid((B + fpb - 1) / fpb);
+#define T8_FAR(K, R) \
+  hipLaunchKernelGGL((k_subgrid_boundary_far<T, K, R>), grid, block, 0, s, F, B, fn, kinds, inflow, normals, areas, mk<T>(st), mk<T>(fl))
+  if (rank == 3) {
+    if (kind == 0) T8_FAR(0, 3); else if (kind == 1) T8_FAR(1, 3); else T8_FAR(2, 3);
+  } else {
+    if (kind == 0) T8_FAR(0, 2); else if (kind == 1) T8_FAR(1, 2); else T8_FAR(2, 2);
+  }
+#undef T8_FAR
+  return launch_status();
+}
+
 }  // namespace t8gpu_hip
 
 namespace t8gpu_hip {
@@ -482,7 +545,7 @@ using namespace t8gpu_hip;
 extern "C" {
 
 const char* t8gpu_hip_last_stage_kernel(void) { return stage_kernel_note().name; }
-int t8gpu_hip_abi_version(void) { return 11; }   // 2: T8gpuPlainPlan.tile_desc; 3: T8gpuSubgridPlan row format (far-cell recipes), n_blocks_addressed, family records; 4: T8gpuPlainPlan.n_patch_tiles; 5: T8gpuPlainPlan.ell holds rows for generic tiles only (tile_desc word 6), patch_dim; 6: T8gpuPlainPlan.n_irregular_tiles; 7: T8gpuPlainPlan ghost window (ghost_buf, send_map, send_list, send_buf, n_owned); 8: t8gpu_hip_plain_geo_frames_* (plan builders must call it); 9: T8gpuPlainPlan open boundaries (inflow, has_open_faces), t8gpu_hip_flux_boundary_bc_*, t8gpu_hip_plain_inflow_table_*; 10: T8gpuSubgridPlan open boundaries (inflow, has_open_faces), t8gpu_hip_subgrid_boundary_bc_*; 11: far-field boundary kinds (T8gpuPlainPlan.has_farfield_faces, face_lr codes 0xFFF8 + k, t8gpu_hip_flux_boundary_bc_* kinds 10..15)
+int t8gpu_hip_abi_version(void) { return 12; }   // 2: T8gpuPlainPlan.tile_desc; 3: T8gpuSubgridPlan row format (far-cell recipes), n_blocks_addressed, family records; 4: T8gpuPlainPlan.n_patch_tiles; 5: T8gpuPlainPlan.ell holds rows for generic tiles only (tile_desc word 6), patch_dim; 6: T8gpuPlainPlan.n_irregular_tiles; 7: T8gpuPlainPlan ghost window (ghost_buf, send_map, send_list, send_buf, n_owned); 8: t8gpu_hip_plain_geo_frames_* (plan builders must call it); 9: T8gpuPlainPlan open boundaries (inflow, has_open_faces), t8gpu_hip_flux_boundary_bc_*, t8gpu_hip_plain_inflow_table_*; 10: T8gpuSubgridPlan open boundaries (inflow, has_open_faces), t8gpu_hip_subgrid_boundary_bc_*; 11: far-field boundary kinds (T8gpuPlainPlan.has_farfield_faces, face_lr codes 0xFFF8 + k, t8gpu_hip_flux_boundary_bc_* kinds 10..15); 12: far-field kinds on Subgrid blocks (T8gpuSubgridPlan.has_farfield_faces, code bits 23-26 hold 10 + k, t8gpu_hip_subgrid_boundary_far_*)
 int t8gpu_hip_device_count(int* count) { return static_cast<int>(hipGetDeviceCount(count)); }
 int t8gpu_hip_set_device(int device) { return static_cast<int>(hipSetDevice(device)); }
 const char* t8gpu_hip_error_string(int code) {
@@ -524,6 +587,11 @@ const char* t8gpu_hip_error_string(int code) {
                                           const T* inflow, const T* normals, const T* areas, V st, V fl,             \
                                           void* stream) {                                                            \
     return subgrid_boundary_bc<T, V>(kind, rank, F, B, fn, kinds, inflow, normals, areas, st, fl, stream);           \
+  }                                                                                                                  \
+  int t8gpu_hip_subgrid_boundary_far_##SUF(int kind, int rank, int F, int B, const int32_t* fn, const uint8_t* kinds, \
+                                           const T* inflow, const T* normals, const T* areas, V st, V fl,            \
+                                           void* stream) {                                                           \
+    return subgrid_boundary_far<T, V>(kind, rank, F, B, fn, kinds, inflow, normals, areas, st, fl, stream);          \
   }                                                                                                                  \
   int t8gpu_hip_subgrid_rk3_stage_##SUF(int stage, int rank, int N, V prev, V mid, V out, V fl, const T* volumes,    \
                                         T dt, void* stream) {                                                        \

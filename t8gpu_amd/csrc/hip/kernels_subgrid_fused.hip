@@ -7,6 +7,8 @@
 // remaining blocks with the block algorithm in the same launch; all three give the same bits. Plans with outflow / inflow
 // faces (T8gpuSubgridPlan::has_open_faces) take the _open forms of the three kernels: their block algorithm decodes the kind
 // of every boundary face (sg_boundary_kind); the family bodies are the wall-only ones (no family holds an open-face block).
+// Plans that also have far-field faces (has_farfield_faces) take the _far forms: the block algorithm with OPEN + FAR, which
+// builds the outside state of a far-field sub-face from the inside subcell (sg_farfield_state); family bodies as before.
 //
 // Replaces, per stage, compute_inner_fluxes + compute_boundary_fluxes + compute_outer_fluxes +
 // subgrid::SSP_3RK_stepK (examples/subgrid/solver.inl:166-195) and their flux-plane round trips
@@ -90,7 +92,8 @@ T8_DEV int cell_coord(int flat, int a) { return (flat >> (2 * a)) & 3; }   // fl
 // ---- boundary faces (open boundaries) -------------------------------------------------------------------------------
 // A boundary face has far = -1 in its record row and its kind in bits 23-26 of the code word (subgrid_plan.cpp): 0 reflective
 // wall, 1 outflow (the outside state is the inside subcell's own), 2 + k inflow with conservative state k of the plan's inflow
-// table. The one place that spells the encoding; only the OPEN instantiations of the block algorithm decode it (the others see
+// table, 10 + k far field against state k (plans of t8gpu_plan_subgrid_create_far; decoded by the FAR instantiations, below).
+// The one place that spells the encoding; only the OPEN instantiations of the block algorithm decode it (the others see
 // walls only, as before). An open face evaluates the ordinary face flux: left = the inside subcell, outward normal, unmirrored.
 T8_DEV int sg_boundary_kind(int code) { return (code >> 23) & 15; }
 // the conservative state of inflow kind `bc` (>= 2): words 0-4 of its T8GPU_INFLOW_WORDS row (t8gpu_hip_plain_inflow_table_*).
@@ -101,6 +104,21 @@ T8_DEV void sg_inflow_state(const T8gpuSubgridPlan& P, int bc, T s[5]) {
   const T* w = static_cast<const T*>(P.inflow) + T8GPU_INFLOW_WORDS * (bc - 2);
 #pragma unroll
   for (int k = 0; k < 5; k++) s[k] = w[k];
+}
+
+// ---- far-field faces (ABI 12) -----------------------------------------------------------------------------------------
+// Kind 10 + k: the characteristic condition (fused_common.hpp: farfield_outside) against row k of the inflow table,
+// per sub-face, with the inside subcell on the left and the outward normal +-e_axis. Only the FAR instantiations decode these
+// kinds (a plan without has_farfield_faces holds none). `s` holds the inside subcell's conservative state on entry and the
+// outside state on return: the table row's words 0-4 (supersonic inflow: what sg_inflow_state gives an inflow face), untouched
+// (supersonic outflow, the guard: the caller keeps what an outflow face takes) or the built state. Returns the FarSide.
+constexpr int kSgFarfield = 10;   // T8GPU_BOUNDARY_FARFIELD (t8gpu_host.h)
+template <class T>
+T8_DEV int sg_farfield_state(const T8gpuSubgridPlan& P, int bc, int axis, bool positive, T s[5]) {
+  const T* row = static_cast<const T*>(P.inflow) + T8GPU_INFLOW_WORDS * (bc - kSgFarfield);
+  const T  sg  = positive ? T(1) : T(-1);
+  const T  n[3] = {axis == 0 ? sg : T(0), axis == 1 ? sg : T(0), axis == 2 ? sg : T(0)};
+  return farfield_state<T>(row, n, s);
 }
 
 template <class T, int KIND>
@@ -182,14 +200,23 @@ T8_DEV FaceLane<T> face_lane_from_row(const SVars<T>& src, int4 rec, bool live_r
   }
   return L;
 }
-template <class T, int S, bool WIDE, bool OPEN = false>
-T8_DEV FaceLane<T> load_face_lane(const T8gpuSubgridPlan& P, const SVars<T>& src, int first, int nbf, int idx, int si, int sj) {
+// (FAR: `own0` = the first cell of the lane's block. A far-field face leaves as an outflow face (bc 1: the outside state is the
+//  inside subcell's own record) or as an inflow face whose state `sf` is the table row or the built state)
+template <class T, int S, bool WIDE, bool OPEN = false, bool FAR = false>
+T8_DEV FaceLane<T> load_face_lane(const T8gpuSubgridPlan& P, const SVars<T>& src, int first, int nbf, int idx, int si, int sj,
+                                  size_t own0 = 0) {
   int4 rec = make_int4(0, 0, 0, 0);
   if (idx < nbf) rec = reinterpret_cast<const int4*>(P.bf_rec)[first + idx];   // {other block, code, area}
   FaceLane<T> L = face_lane_from_row<T, S, WIDE>(src, rec, idx < nbf, si, sj);
   if (OPEN && L.active && L.wall) {
     L.bc = sg_boundary_kind(rec.y);
-    if (L.bc >= 2) sg_inflow_state<T>(P, L.bc, L.sf);
+    if (FAR && L.bc >= kSgFarfield) {
+#pragma unroll
+      for (int k = 0; k < 5; k++) L.sf[k] = at<WIDE>(src.p[k], own0 + L.myflat);
+      L.bc = sg_farfield_state<T>(P, L.bc, L.axis, L.positive != 0, L.sf) == kFarInside ? 1 : 2;
+    } else if (L.bc >= 2) {
+      sg_inflow_state<T>(P, L.bc, L.sf);
+    }
   }
   return L;
 }
@@ -253,7 +280,10 @@ T8_DEV void block_sync() {
 // RANK 2: four records), c = lane, pe / xb = the wavefront's LDS slices ([NW][64 + BPW * PF] cells of the block(s) then
 // the far cells of their + faces; [5][64] flux exchange buffer).
 // OPEN: the plan has outflow / inflow faces (sg_boundary_kind); OPEN = false is the wall-only block algorithm.
-template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE, bool WAVE_ONLY, bool NT = false, bool OPEN = false>
+// FAR (with OPEN): ... and far-field faces. The outside state of such a sub-face is built by the lane that evaluates it, right
+// before its flux (it is not live across the passes); the kind test diverges only in wavefronts that hold boundary sub-faces.
+template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE, bool WAVE_ONLY, bool NT = false, bool OPEN = false,
+          bool FAR = false>
 T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_count, int pos_base, int c, const SVars<T>& prev,
                           const SVars<T>& src, const SVars<T>& out, const T* __restrict__ volumes, T dt, T* pe, T* xb) {
   // (pe / xb carry no __restrict__: other lanes write what this lane reads, and a no-alias pointer would let the
@@ -310,8 +340,9 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
   load_far<T, WIDE>(src, p_on, pd == 0 ? fx.wall : (pd == 1 ? fy.wall : fz.wall), pd == 0 ? fx.far : (pd == 1 ? fy.far : fz.far),
               pd == 0 ? fx.hf : (pd == 1 ? fy.hf : fz.hf), pla, plb, pti, ptj, -1, pfar);
   if (OPEN) {   // an inflow face on the + side: its far cell is the prescribed state (outflow and walls read this cell's own)
+    // (FAR: a far-field face against state k appends state k like inflow face 2 + k: what its supersonic-inflow lanes take)
     const int pbc = pd == 0 ? fx.bc : (pd == 1 ? fy.bc : fz.bc);
-    if (p_on && pbc >= 2) sg_inflow_state<T>(P, pbc, pfar);
+    if (p_on && pbc >= 2) sg_inflow_state<T>(P, FAR && pbc >= kSgFarfield ? pbc - kSgFarfield + 2 : pbc, pfar);
   }
 
   // - faces: lane cl < PF owns sub-face `cl % SF` of the block's -(cl / SF) face. A wall lane fetches its OWN cell
@@ -328,7 +359,8 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
               pti, ptj, (size_t)e * S + mflat, mfar);
   // (OPEN: an outflow lane keeps its own cell like a wall lane, an inflow lane takes the prescribed state)
   const int m_bc = OPEN ? (pd == 0 ? mx.bc : (pd == 1 ? my.bc : mz.bc)) : 0;
-  if (OPEN && m_on && m_bc >= 2) sg_inflow_state<T>(P, m_bc, mfar);
+  // (FAR: a far-field lane keeps its own cell until the - pass, which builds the outside state from it)
+  if (OPEN && m_on && m_bc >= 2 && !(FAR && m_bc >= kSgFarfield)) sg_inflow_state<T>(P, m_bc, mfar);
 
   const CellData<T, KIND> mine = cell_from_state<T, KIND>(s0);
 #pragma unroll
@@ -355,10 +387,26 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
     const bool bnd  = !inner && pl.wall;
     const bool wall = OPEN ? bnd && pl.bc == 0 : bnd;
     const bool self = OPEN ? bnd && pl.bc < 2 : bnd;
-    const int  oidx = inner ? c + str : (self ? c : 64 + (c / S) * PF + d * SF + tsub);
+    int        oidx = inner ? c + str : (self ? c : 64 + (c / S) * PF + d * SF + tsub);
+    // FAR, a far-field face: supersonic inflow reads the appended state like an inflow face, supersonic outflow this cell like
+    // an outflow face, a subsonic sub-face the record of the state built here
+    const bool farf = FAR && bnd && pl.bc >= kSgFarfield;
+    int        fside = kFarTable;
+    T          so[5];
+    if (FAR) {
+#pragma unroll
+      for (int k = 0; k < 5; k++) so[k] = s0[k];
+      if (farf) {
+        fside = sg_farfield_state<T>(P, pl.bc, d, true, so);
+        if (fside == kFarInside) oidx = c;
+      }
+    }
     CellData<T, KIND> other;
 #pragma unroll
     for (int w = 0; w < NW; w++) other.v[w] = pe[(w) * PEL + (oidx)];
+    if (FAR) {
+      if (farf && fside == kFarBuilt) other = cell_from_state<T, KIND>(so);
+    }
     const T    ar   = inner ? surface : pl.area / T(SF);
     T g[5] = {T(0), T(0), T(0), T(0), T(0)};
     if (inner || pl.on) cell_flux<T, KIND>(mine, other, wall, d, true, ar, g);   // left = this cell, normal +e_d
@@ -383,6 +431,8 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
       CellData<T, KIND> here;
 #pragma unroll
       for (int w = 0; w < NW; w++) here.v[w] = pe[(w) * PEL + (base + mflat)];
+      // (FAR: mfar is this cell's own state, as on an outflow lane; it stays, or becomes the table row or the built state)
+      if (FAR && m_bc >= kSgFarfield) sg_farfield_state<T>(P, m_bc, pd, false, mfar);
       const CellData<T, KIND> there = cell_from_state<T, KIND>(mfar);
       if (OPEN) {   // a boundary face: left = this cell, outward normal -e_d, right = the mirror (wall) or the outside state
         CellData<T, KIND> L, R;
@@ -416,7 +466,7 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
   // ---- remaining coarse faces (towards finer blocks: four sub-faces per surface cell; kernels.inl:664-911) ----------
   for (int p0 = 0; p0 < npass; p0 += 4) {
     T                 g[5] = {T(0), T(0), T(0), T(0), T(0)};
-    const FaceLane<T> fl = load_face_lane<T, S, WIDE, OPEN>(P, src, b0, nbf, p0 + slot, si, sj);
+    const FaceLane<T> fl = load_face_lane<T, S, WIDE, OPEN, FAR>(P, src, b0, nbf, p0 + slot, si, sj, (size_t)e * S);
     if (fl.active) {
       CellData<T, KIND> here, there;
 #pragma unroll
@@ -519,6 +569,18 @@ __global__ __launch_bounds__(64) void k_subgrid_fused_open(T8gpuSubgridPlan P, i
   subgrid_block<T, KIND, STAGE, RANK, EARLY_PREV, WIDE, false, false, true>(P, block_begin, block_count, pos_base, threadIdx.x, prev, src,
                                                                             out, volumes, dt, pe, xb);
 }
+// ... and far-field faces
+template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE>
+__global__ __launch_bounds__(64) void k_subgrid_fused_far(T8gpuSubgridPlan P, int block_begin, int block_count, SVars<T> prev,
+                                                          SVars<T> src, SVars<T> out, const T* __restrict__ volumes, T dt) {
+  constexpr int NW = CellData<T, KIND>::words;
+  constexpr int PEL = 64 + (RANK == 3 ? 1 : 4) * RANK * (RANK == 3 ? 16 : 4);
+  __shared__ T pe[NW * PEL];
+  __shared__ T xb[5 * 64];
+  const int pos_base = sg_xcd_position(blockIdx.x, gridDim.x);
+  subgrid_block<T, KIND, STAGE, RANK, EARLY_PREV, WIDE, false, false, true, true>(P, block_begin, block_count, pos_base, threadIdx.x, prev,
+                                                                                  src, out, volumes, dt, pe, xb);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Family kernel (RANK 3): one workgroup of eight wavefronts = a 2x2x2 cube of consecutive same-level blocks
@@ -536,8 +598,8 @@ T8_DEV int fam_expand(int j, int d) { return d == 0 ? j << 1 : (d == 1 ? (j & 1)
 
 // (second launch bound = wavefronts per SIMD the register allocation must allow: 3 workgroups per CU in fp32 (80 VGPRs),
 //  2 in fp64 (128 VGPRs; its 66 KB of LDS allow no more))
-// (the body of k_subgrid_family and k_subgrid_family_open: OPEN reaches the blocks outside every cube only)
-template <class T, int KIND, int STAGE, bool WIDE, bool NT, bool OPEN>
+// (the body of k_subgrid_family, k_subgrid_family_open and k_subgrid_family_far: OPEN / FAR reach the blocks outside every cube only)
+template <class T, int KIND, int STAGE, bool WIDE, bool NT, bool OPEN, bool FAR = false>
 T8_DEV void subgrid_family(const T8gpuSubgridPlan& P, const SVars<T>& prev, const SVars<T>& src, const SVars<T>& out,
                            const T* __restrict__ volumes, T dt) {
   constexpr int  NW    = CellData<T, KIND>::words;
@@ -558,8 +620,8 @@ T8_DEV void subgrid_family(const T8gpuSubgridPlan& P, const SVars<T>& prev, cons
       T8gpuSubgridPlan R = P;
       R.block_rec        = P.rest_rec;
       T* const mine_lds  = lds + w * BLK_WORDS;
-      subgrid_block<T, KIND, STAGE, 3, sizeof(T) == 4, WIDE, true, NT, OPEN>(R, 0, P.n_rest, pos, c, prev, src, out, volumes, dt, mine_lds,
-                                                                        mine_lds + NW * 112);
+      subgrid_block<T, KIND, STAGE, 3, sizeof(T) == 4, WIDE, true, NT, OPEN, FAR>(R, 0, P.n_rest, pos, c, prev, src, out, volumes, dt,
+                                                                             mine_lds, mine_lds + NW * 112);
     }
     return;
   }
@@ -710,6 +772,14 @@ __global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_subgrid_family_
                                                                                      SVars<T> out, const T* __restrict__ volumes, T dt) {
   subgrid_family<T, KIND, STAGE, WIDE, NT, true>(P, prev, src, out, volumes, dt);
 }
+// (fp64 KEPES stages 2 and 3 with 64-bit addressing: the rest blocks' far-field state does not fit 128 VGPRs beside the 64-bit
+//  plane addresses -- 4 VGPRs spilled in a trial build --, so these four instantiations are bounded to 3 waves per SIMD, which
+//  is one workgroup per CU instead of two; planes of 4 GiB and more only)
+template <class T, int KIND, int STAGE, bool WIDE, bool NT>
+__global__ __launch_bounds__(512, sizeof(T) == 8 ? (KIND == 0 && STAGE > 1 && WIDE ? 3 : 4) : 6) void k_subgrid_family_far(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src,
+                                                                                    SVars<T> out, const T* __restrict__ volumes, T dt) {
+  subgrid_family<T, KIND, STAGE, WIDE, NT, true, true>(P, prev, src, out, volumes, dt);
+}
 
 // (Round 4, measured and dropped: a PERSISTENT form of this kernel -- a resident grid of 2 (fp64) / 3 (fp32) workgroups per CU
 // walking the cubes of their XCD's share, the next cube's record rows as scalar loads at the top of an iteration, its own state,
@@ -732,7 +802,7 @@ __global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_subgrid_family_
 // the + faces in lanes 0-15, 16 behind the - faces in lanes 16-31: one half-filled primitive round instead of the block
 // kernel's two). Same fluxes, same summation order: bitwise equal to the block kernel. The blocks outside every square run
 // behind the squares in the same launch (four per wavefront, the block algorithm).
-template <class T, int KIND, int STAGE, bool WIDE, bool NT, bool OPEN>
+template <class T, int KIND, int STAGE, bool WIDE, bool NT, bool OPEN, bool FAR = false>
 T8_DEV void subgrid_family2(const T8gpuSubgridPlan& P, const SVars<T>& prev, const SVars<T>& src, const SVars<T>& out,
                             const T* __restrict__ volumes, T dt) {
   constexpr int  NW        = CellData<T, KIND>::words;
@@ -744,8 +814,8 @@ T8_DEV void subgrid_family2(const T8gpuSubgridPlan& P, const SVars<T>& prev, con
   if (static_cast<int>(blockIdx.x) >= P.n_families) {   // the blocks outside every square: four per wavefront
     T8gpuSubgridPlan R = P;
     R.block_rec        = P.rest_rec;
-    subgrid_block<T, KIND, STAGE, 2, EARLY, WIDE, false, NT, OPEN>(R, 0, P.n_rest, static_cast<int>(blockIdx.x) - P.n_families, c, prev, src,
-                                                               out, volumes, dt, lds, lds + NW * 96);
+    subgrid_block<T, KIND, STAGE, 2, EARLY, WIDE, false, NT, OPEN, FAR>(R, 0, P.n_rest, static_cast<int>(blockIdx.x) - P.n_families, c, prev,
+                                                                    src, out, volumes, dt, lds, lds + NW * 96);
     return;
   }
   // primitives [64 cells of the square, then 16 far cells behind the outward + faces ((d * 2 + j) * 4 + sub-face)];
@@ -877,6 +947,11 @@ __global__ __launch_bounds__(64) void k_subgrid_family2_open(T8gpuSubgridPlan P,
                                                              const T* __restrict__ volumes, T dt) {
   subgrid_family2<T, KIND, STAGE, WIDE, NT, true>(P, prev, src, out, volumes, dt);
 }
+template <class T, int KIND, int STAGE, bool WIDE, bool NT>
+__global__ __launch_bounds__(64) void k_subgrid_family2_far(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src, SVars<T> out,
+                                                            const T* __restrict__ volumes, T dt) {
+  subgrid_family2<T, KIND, STAGE, WIDE, NT, true, true>(P, prev, src, out, volumes, dt);
+}
 
 template <class T, class V>
 SVars<T> smk(const V& v) {
@@ -893,6 +968,7 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
   if (block_begin < 0 || block_count < 0 || block_begin + block_count > plan->num_elements) return static_cast<int>(hipErrorInvalidValue);
   if (block_count == 0) return 0;
   const bool open = plan->has_open_faces != 0;   // outflow / inflow faces: the _open kernels
+  const bool far  = open && plan->has_farfield_faces != 0;   // ... and far-field faces: the _far kernels
   if (open && !plan->inflow) return static_cast<int>(hipErrorInvalidValue);
   stage_kernel_note_reset();
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -907,9 +983,13 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
   auto blocks = [&](const T8gpuSubgridPlan& pl, int begin, int count) {
     const dim3 grid(pl.rank == 3 ? count : (count + 3) / 4), block(64);
     return dispatch(
-        [&](auto K, auto S, auto RANK3, auto WIDE, auto OPEN) {
+        [&](auto K, auto S, auto RANK3, auto WIDE, auto OPEN, auto FAR) {
           constexpr int R = RANK3 ? 3 : 2;
-          if constexpr (OPEN) {
+          if constexpr (OPEN && FAR) {
+            note_stage_kernel<T>(count, "k_subgrid_fused_far", K, S, R, early, WIDE);
+            return launch(&k_subgrid_fused_far<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
+                          smk<T>(out), volumes, dt);
+          } else if constexpr (OPEN) {
             note_stage_kernel<T>(count, "k_subgrid_fused_open", K, S, R, early, WIDE);
             return launch(&k_subgrid_fused_open<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
                           smk<T>(out), volumes, dt);
@@ -919,7 +999,7 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
                           smk<T>(out), volumes, dt);
           }
         },
-        kind, stage, pl.rank == 3, wide, open);
+        kind, stage, pl.rank == 3, wide, open, far);
   };
   // A launch that covers the whole plan of a 3D mesh: 2x2x2 cubes of same-level blocks through the family kernel, the
   // other blocks through the block kernel (T8GPU_SG_FAMILY=0: every block through the block kernel -- same bits. Measured
@@ -951,8 +1031,13 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
   const int  restb = plan->rank == 3 ? (sizeof(T) == 8 ? 4 : 8) : 4;   // (k_subgrid_family: RESTB)
   const dim3 grid(plan->n_families + (n_rest_here + restb - 1) / restb), block(plan->rank == 3 ? 512 : 64);
   return dispatch(
-      [&](auto K, auto S, auto RANK3, auto WIDE, auto NT, auto OPEN) {
-        if constexpr (OPEN) {   // (the cubes / squares hold no open-face block: the blocks behind them run the OPEN algorithm)
+      [&](auto K, auto S, auto RANK3, auto WIDE, auto NT, auto OPEN, auto FAR) {
+        if constexpr (OPEN && FAR) {
+          const char* name   = RANK3 ? "k_subgrid_family_far" : "k_subgrid_family2_far";
+          const auto  kernel = RANK3 ? &k_subgrid_family_far<T, K, S, WIDE, NT> : &k_subgrid_family2_far<T, K, S, WIDE, NT>;
+          note_stage_kernel<T>(block_count, name, K, S, WIDE, NT);
+          return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
+        } else if constexpr (OPEN) {   // (the cubes / squares hold no open-face block: the blocks behind them run the OPEN algorithm)
           const char* name   = RANK3 ? "k_subgrid_family_open" : "k_subgrid_family2_open";
           const auto  kernel = RANK3 ? &k_subgrid_family_open<T, K, S, WIDE, NT> : &k_subgrid_family2_open<T, K, S, WIDE, NT>;
           note_stage_kernel<T>(block_count, name, K, S, WIDE, NT);
@@ -964,7 +1049,7 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
           return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
         }
       },
-      kind, stage, plan->rank == 3, wide, nt, open);
+      kind, stage, plan->rank == 3, wide, nt, open, far);
 }
 
 }  // namespace t8gpu_hip

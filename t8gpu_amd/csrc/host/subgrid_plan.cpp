@@ -16,7 +16,8 @@
 //                            per surface cell), in original order; bit 31 set when the block is the face's RIGHT side
 //   face_rec[F+B][4]       : {left slot, right slot (-1: boundary face), code, 0} with
 //                            code = axis | positive<<2 | hanging<<3 | off0<<4 | off1<<6 | off2<<8 | bc<<23, where bc
-//                            = the boundary kind of a boundary face (0 wall, 1 outflow, 2 + k inflow state k; 0 for
+//                            = the boundary kind of a boundary face (0 wall, 1 outflow, 2 + k inflow state k, 10 + k far field
+//                            against state k -- t8gpu_plan_subgrid_create_far only; 0 for
 //                            every face when no kinds are given: a wall-only plan is the plan of earlier versions)
 // Normals must be exact +-unit axis vectors -- the reference's kernels require the same
 // (kernels.inl:717-750 select the face plane by comparing the normal with +-1.0).
@@ -31,19 +32,17 @@ struct SubgridPlan {
   std::vector<int32_t> fam_first;   // first block of every 2x2x2 family (below)
   std::vector<uint8_t> in_family;
   int32_t n_interior = 0, n_deep = 0;
-  bool    open_faces = false;   // some boundary face is an outflow / inflow face
+  bool    open_faces = false;   // some boundary face is an outflow / inflow / far-field face
+  bool    farfield_faces = false;   // some boundary face is a far-field face
 };
-}  // namespace
 
-extern "C" {
-
-void* t8gpu_plan_subgrid_create_bc(int32_t N, int32_t F, int32_t B, int32_t rank, const int32_t* fn,
-                                   const int32_t* level_diff, const int32_t* nb_offset, const double* normals,
-                                   const uint8_t* boundary_kinds) {
+// the plan of t8gpu_plan_subgrid_create_bc / _far: kinds above `max_kind` are refused
+SubgridPlan* create_plan(int32_t N, int32_t F, int32_t B, int32_t rank, const int32_t* fn, const int32_t* level_diff,
+                         const int32_t* nb_offset, const double* normals, const uint8_t* boundary_kinds, int max_kind) {
   if (N < 0 || F < 0 || B < 0 || (rank != 2 && rank != 3)) return nullptr;
   if (boundary_kinds)
     for (int32_t b = 0; b < B; b++)
-      if (boundary_kinds[b] > 9) return nullptr;   // 0 wall, 1 outflow, 2 + k inflow (k < 8)
+      if (boundary_kinds[b] > max_kind) return nullptr;
   SubgridPlan* P = new SubgridPlan;
   P->N = N; P->F = F; P->B = B; P->rank = rank;
   P->face_rec.assign(4 * (static_cast<size_t>(F) + B), 0);
@@ -74,6 +73,7 @@ void* t8gpu_plan_subgrid_create_bc(int32_t N, int32_t F, int32_t B, int32_t rank
       const int32_t bc = boundary_kinds ? boundary_kinds[f - F] : 0;
       code |= bc << 23;
       if (bc != 0 && l < N) P->open_faces = true;
+      if (bc >= 10 && l < N) P->farfield_faces = true;
     }
     int32_t* rec = &P->face_rec[4 * static_cast<size_t>(f)];
     rec[0] = l; rec[1] = r; rec[2] = code; rec[3] = 0;
@@ -143,7 +143,7 @@ void* t8gpu_plan_subgrid_create_bc(int32_t N, int32_t F, int32_t B, int32_t rank
       if (ghosty[r] && !ghosty[l]) near[l] = 1;
     }
   }
-  // blocks with an outflow / inflow face: they never join a family (the family bodies know walls only) and run as rest blocks
+  // blocks with an outflow / inflow / far-field face: they never join a family (the family bodies know walls only) and run as rest blocks
   std::vector<uint8_t> open_block(static_cast<size_t>(N), 0);
   for (int32_t b = 0; b < B; b++) {
     const int32_t l = fn[2 * static_cast<size_t>(F) + b];
@@ -203,6 +203,22 @@ void* t8gpu_plan_subgrid_create_bc(int32_t N, int32_t F, int32_t B, int32_t rank
     if (ghosty[e]) P->block_order.push_back(e);
   return P;
 }
+}  // namespace
+
+extern "C" {
+
+void* t8gpu_plan_subgrid_create_bc(int32_t N, int32_t F, int32_t B, int32_t rank, const int32_t* fn,
+                                   const int32_t* level_diff, const int32_t* nb_offset, const double* normals,
+                                   const uint8_t* boundary_kinds) {
+  return create_plan(N, F, B, rank, fn, level_diff, nb_offset, normals, boundary_kinds, 9);   // 0 wall, 1 outflow, 2 + k inflow (k < 8)
+}
+
+// ... and 10 + k far field against state k (k < 6): the same plan with the kind in the same bits
+void* t8gpu_plan_subgrid_create_far(int32_t N, int32_t F, int32_t B, int32_t rank, const int32_t* fn,
+                                    const int32_t* level_diff, const int32_t* nb_offset, const double* normals,
+                                    const uint8_t* boundary_kinds) {
+  return create_plan(N, F, B, rank, fn, level_diff, nb_offset, normals, boundary_kinds, 15);
+}
 
 void* t8gpu_plan_subgrid_create(int32_t N, int32_t F, int32_t B, int32_t rank, const int32_t* fn,
                                 const int32_t* level_diff, const int32_t* nb_offset, const double* normals) {
@@ -210,6 +226,7 @@ void* t8gpu_plan_subgrid_create(int32_t N, int32_t F, int32_t B, int32_t rank, c
 }
 
 int32_t t8gpu_plan_subgrid_open_faces(const void* h) { return static_cast<const SubgridPlan*>(h)->open_faces ? 1 : 0; }
+int32_t t8gpu_plan_subgrid_farfield_faces(const void* h) { return static_cast<const SubgridPlan*>(h)->farfield_faces ? 1 : 0; }
 
 void t8gpu_plan_subgrid_destroy(void* h) { delete static_cast<SubgridPlan*>(h); }
 
@@ -250,7 +267,7 @@ void t8gpu_plan_subgrid_arrays(const void* h, int32_t* bf_off, int32_t* bf_ent, 
 //   bf_rec[n_entries][4], the generic faces of the blocks in the same position order: far, code, area (2 words)
 // far = index of the far cell of sub-face (0, 0) in the state arrays (far block * cells per block + its cell there; the
 // far block is the left block if this block is the face's right side and vice versa), -1 = boundary face (its kind in code
-// bits 23-26: 0 wall, 1 outflow, 2 + k inflow state k), -2 (+ / - faces only) =
+// bits 23-26: 0 wall, 1 outflow, 2 + k inflow state k, 10 + k far field k), -2 (+ / - faces only) =
 // not foldable (finer neighbours: those faces are in the generic list);
 // code = the face code of face_rec | 1 << 12 when this block is the face's RIGHT side | this block's cell behind
 // sub-face (0, 0) << 13 | (two sub-faces per far cell) << 19 | (two sub-faces per own cell) << 20 | (stride of the first

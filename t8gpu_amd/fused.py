@@ -274,15 +274,17 @@ class T8gpuSubgridPlan(C.Structure):
                 ("n_interior_blocks", C.c_int32), ("n_deep_blocks", C.c_int32), ("n_blocks_addressed", C.c_int32),
                 ("fam_rec", C.c_void_p), ("rest_rec", C.c_void_p), ("n_families", C.c_int32), ("n_rest", C.c_int32),
                 # ABI 10: open boundaries -- the inflow table (device, [K][16]) and "the plan has outflow / inflow faces"
-                ("inflow", C.c_void_p), ("has_open_faces", C.c_int32), ("reserved10", C.c_int32)]
+                # ABI 12: "... and far-field faces" (the _far kernels)
+                ("inflow", C.c_void_p), ("has_open_faces", C.c_int32), ("has_farfield_faces", C.c_int32)]
 
 
 class SubgridPlan:
     """Device copy of the joined per-block face records for the fused Subgrid<4,4> / Subgrid<4,4,4> kernels."""
 
-    def __init__(self, part, dtype):
+    def __init__(self, part, dtype, farfield=False):
+        """farfield=True: the plan takes far-field kinds (10 + k) through the planner's _far entry"""
         from .plan import HostSubgridPlan
-        self.host = HostSubgridPlan(part)
+        self.host = HostSubgridPlan(part, farfield=farfield)
         self.dtype = dtype
         block_rec, bf_rec = self.host.records(part.areas, 4 if dtype == torch.float32 else 8)
         self._keep = {"block_rec": torch.from_numpy(block_rec).cuda(), "bf_rec": torch.from_numpy(bf_rec).cuda()}
@@ -298,10 +300,11 @@ class SubgridPlan:
         c.n_deep_blocks = self.host.n_deep
         c.n_blocks_addressed = self.host.n_addressed
         c.has_open_faces = int(self.host.has_open_faces)
+        c.has_farfield_faces = int(self.host.has_farfield_faces)
         self.c = c
 
     def attach_inflow(self, table):
-        """the device inflow table (t8gpu_hip_plain_inflow_table_*) the _open kernels read: set once, before any launch"""
+        """the device inflow table (t8gpu_hip_plain_inflow_table_*) the _open / _far kernels read: set once, before any launch"""
         self._keep["inflow"] = table
         self.c.inflow = table.data_ptr()
 

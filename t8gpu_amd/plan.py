@@ -135,18 +135,23 @@ class HostPlainPlan:
 class HostSubgridPlan:
     """Host arrays of the per-block face lists (see include/t8gpu_hip.h, T8gpuSubgridPlan)."""
 
-    def __init__(self, part, boundary_kinds=None):
+    def __init__(self, part, boundary_kinds=None, farfield=False):
         """boundary_kinds[B] (0 wall, 1 outflow, 2 + k inflow k; default: part.boundary_kinds, None = all walls): a boundary
         face carries its kind in bits 23-26 of its code word, and a block with an open face never joins a family
-        (t8gpu_host.h: t8gpu_plan_subgrid_create_bc)."""
+        (t8gpu_host.h: t8gpu_plan_subgrid_create_bc). farfield=True: kinds 10 + k (far field against state k) are taken too
+        (t8gpu_plan_subgrid_create_far); with kinds of 9 and below the plan is the same byte for byte."""
         assert part.subgrid
         lib = _synth.lib()
         lib.t8gpu_plan_subgrid_create.restype = C.c_void_p
         lib.t8gpu_plan_subgrid_create.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 4
         lib.t8gpu_plan_subgrid_create_bc.restype = C.c_void_p
         lib.t8gpu_plan_subgrid_create_bc.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 5
+        lib.t8gpu_plan_subgrid_create_far.restype = C.c_void_p
+        lib.t8gpu_plan_subgrid_create_far.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 5
         lib.t8gpu_plan_subgrid_open_faces.restype = C.c_int32
         lib.t8gpu_plan_subgrid_open_faces.argtypes = [C.c_void_p]
+        lib.t8gpu_plan_subgrid_farfield_faces.restype = C.c_int32
+        lib.t8gpu_plan_subgrid_farfield_faces.argtypes = [C.c_void_p]
         lib.t8gpu_plan_subgrid_destroy.argtypes = [C.c_void_p]
         lib.t8gpu_plan_subgrid_sizes.argtypes = [C.c_void_p, C.c_void_p]
         lib.t8gpu_plan_subgrid_arrays.argtypes = [C.c_void_p] * 5
@@ -161,12 +166,14 @@ class HostSubgridPlan:
         else:
             kinds = np.ascontiguousarray(boundary_kinds, np.uint8)
             assert kinds.size == part.B
-            h = lib.t8gpu_plan_subgrid_create_bc(part.N, part.F, part.B, rank, p(fn), p(part.level_diff), p(part.nb_offset),
-                                                 p(nr), p(kinds))
+            create = lib.t8gpu_plan_subgrid_create_far if farfield else lib.t8gpu_plan_subgrid_create_bc
+            h = create(part.N, part.F, part.B, rank, p(fn), p(part.level_diff), p(part.nb_offset), p(nr), p(kinds))
         if not h:
-            raise ValueError("subgrid plan needs axis-aligned unit normals (as the reference's subgrid kernels do)")
+            raise ValueError("subgrid plan needs axis-aligned unit normals (as the reference's subgrid kernels do) and boundary "
+                             f"kinds of at most {15 if farfield else 9}")
         self._h = h
-        self.has_open_faces = bool(lib.t8gpu_plan_subgrid_open_faces(h))   # some boundary face is an outflow / inflow face
+        self.has_open_faces = bool(lib.t8gpu_plan_subgrid_open_faces(h))   # some boundary face is an outflow / inflow / far-field face
+        self.has_farfield_faces = bool(lib.t8gpu_plan_subgrid_farfield_faces(h))   # ... some of them far-field faces
         sz = np.zeros(8, np.int64)
         lib.t8gpu_plan_subgrid_sizes(h, p(sz))
         self.N, self.rank, self.max_bf, self.n_interior, self.n_deep = part.N, rank, int(sz[1]), int(sz[3]), int(sz[4])

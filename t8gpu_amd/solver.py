@@ -93,19 +93,52 @@ class _Solver:
         self.next, self.prev = STEP0, STEP3  # solver.h:100-101
         self.plan = self.stepper = None
 
+    _STATE_SLOTS = 4    # pinned host copies of the states that may be on their way to the device at once (set_inflow_states)
+
     def _upload_open_boundaries(self, kinds, inflow_states):
         """device copies of the boundary kinds (compat kernels) and the inflow table (t8gpu_hip_plain_inflow_table_*), made once
-        when self.open_boundaries is set (launches never allocate or copy); None otherwise"""
+        when self.open_boundaries is set (launches never allocate or copy); None otherwise. With them the staging buffers of
+        set_inflow_states: a device block of (K, 5) states and a few pinned host copies of it."""
         self.inflow_states = inflow_states
-        self.kinds = self.inflow_table = None
+        self.kinds = self.inflow_table = self._states_dev = None
         if self.open_boundaries:
             self.kinds = _dev(kinds) if kinds is not None and bool(np.any(kinds != 0)) else None   # (all walls: the wall kernel)
             states = inflow_states if inflow_states is not None else np.zeros((1, 5))   # (an outflow-only plan: never read)
-            st = torch.from_numpy(np.ascontiguousarray(states)).to(self.dtype).cuda()
-            self.inflow_table = torch.zeros((states.shape[0], 16), dtype=self.dtype, device="cuda")
-            hip.call("t8gpu_hip_plain_inflow_table", self.dtype, hip.ptr(st), int(states.shape[0]), hip.ptr(self.inflow_table),
+            K = int(states.shape[0])
+            self._states_dev = torch.from_numpy(np.ascontiguousarray(states)).to(self.dtype).cuda()
+            self._states_host = torch.zeros((self._STATE_SLOTS, K, 5), dtype=self.dtype).pin_memory()
+            self._states_sent = [torch.cuda.Event() for _ in range(self._STATE_SLOTS)]
+            self._states_slot = 0
+            self.inflow_table = torch.zeros((K, 16), dtype=self.dtype, device="cuda")
+            hip.call("t8gpu_hip_plain_inflow_table", self.dtype, hip.ptr(self._states_dev), K, hip.ptr(self.inflow_table),
                      hip.stream_ptr())
-            torch.cuda.current_stream().synchronize()     # (`st` is released on return)
+            torch.cuda.current_stream().synchronize()
+
+    def set_inflow_states(self, states, stream=None):
+        """New inflow / far-field states for a running solver: a (K, 5) array of conservative states with the K of the
+        constructor (check_inflow_states). The device table is refilled in place (t8gpu_hip_plain_inflow_table_*), ordered on
+        `stream` (default: the current stream), so its address never changes and every later launch on that stream reads the
+        new values: compat and fused stages, the native step driver, a replayed graph. Nothing is allocated and the host does
+        not wait for the device (the states travel through a pinned host copy and a device staging block made with the solver;
+        only a caller more than a few updates ahead of the device waits for the oldest copy). A rank of a partitioned run calls
+        it like every other rank."""
+        if self.inflow_table is None or self.inflow_states is None:
+            raise ValueError("set_inflow_states needs a solver built with open boundaries and inflow_states")
+        new = check_inflow_states(self.part, states)
+        if new is None or new.shape != self.inflow_states.shape:
+            raise ValueError(f"inflow_states must keep the shape {self.inflow_states.shape} of the states the solver was built with "
+                             "(the device table's size and address are fixed)")
+        stream = torch.cuda.current_stream() if stream is None else stream
+        slot = self._states_slot
+        self._states_slot = (slot + 1) % self._STATE_SLOTS
+        self._states_sent[slot].synchronize()          # (a no-op unless this slot's last copy is still queued)
+        self._states_host[slot].copy_(torch.from_numpy(new))
+        with torch.cuda.stream(stream):
+            self._states_dev.copy_(self._states_host[slot], non_blocking=True)
+            self._states_sent[slot].record(stream)
+        hip.call("t8gpu_hip_plain_inflow_table", self.dtype, hip.ptr(self._states_dev), int(new.shape[0]), hip.ptr(self.inflow_table),
+                 hip.stream_ptr(stream))
+        self.inflow_states = new
 
     # -- accessors named after the reference API ------------------------------------------------
     def get_own_variables(self, step):
@@ -299,16 +332,21 @@ class SubgridSolver(_Solver):
     """Subgrid<4,4> / Subgrid<4,4,4>: planes[25, (N+G)*S] in subcells + per-block volumes.
     open_boundaries=True: boundary faces follow part.boundary_kinds (0 wall, 1 outflow, 2 + k inflow with state k; absent:
     walls), every subcell on an open face with its own sub-face flux; inflow_states = (K, 5) conservative states, required iff
-    some face is an inflow face. A partition without open faces takes it too (a rank that owns no boundary, an adapted mesh).
-    By default a partition with open faces is refused. Far-field faces (10 + k) are not supported for Subgrid blocks."""
+    some face is an inflow or far-field face. A partition without open faces takes it too (a rank that owns no boundary, an
+    adapted mesh). By default a partition with open faces is refused.
+    farfield=True (needs open_boundaries=True): far-field faces (10 + k, the characteristic condition against state k,
+    DESIGN.md §4) are taken too, per sub-face with the outward normal of the block face; without it a partition with far-field
+    faces is refused. A partition without far-field faces takes the flag too."""
     _native_stepper = native.NativeSubgridStepper
 
     def __init__(self, part, dtype=torch.float32, flux_kind=hip.KEPES, mode="compat", state=None, open_boundaries=False,
-                 inflow_states=None):
+                 inflow_states=None, farfield=False):
         kinds = boundary_kinds_of(part)
-        if kinds is not None and np.any(kinds >= FARFIELD):
-            raise ValueError("SubgridSolver does not support far-field boundary faces: far-field kinds (10 + k) are not supported "
-                             "for Subgrid blocks (use outflow or inflow sides, or a PlainSolver)")
+        if farfield and not open_boundaries:
+            raise ValueError("farfield=True needs open_boundaries=True")
+        if not farfield and kinds is not None and np.any(kinds >= FARFIELD):
+            raise ValueError("SubgridSolver without farfield=True takes no far-field boundary faces: the partition has far-field "
+                             "kinds (10 + k) (pass open_boundaries=True, farfield=True and inflow_states)")
         if not open_boundaries and kinds is not None and np.any(kinds != 0):
             raise ValueError("SubgridSolver without open_boundaries=True takes walls only: the partition has outflow / inflow "
                              "boundary faces (pass open_boundaries=True and, for inflow faces, inflow_states)")
@@ -317,7 +355,8 @@ class SubgridSolver(_Solver):
         inflow_states = check_inflow_states(part, inflow_states) if open_boundaries else None
         assert part.subgrid
         super().__init__(part, dtype, flux_kind, mode)
-        self.open_boundaries = bool(open_boundaries)
+        self.open_boundaries, self.farfield = bool(open_boundaries), bool(farfield)
+        self._far_kinds = self.farfield and kinds is not None and bool(np.any(kinds >= FARFIELD))
         self._upload_open_boundaries(kinds, inflow_states)
         self.rank = part.mesh.dim
         self.S = 4 ** self.rank
@@ -334,7 +373,7 @@ class SubgridSolver(_Solver):
         self.areas = _dev(part.areas, dtype)
         if mode == "fused":
             from . import fused
-            self.plan = fused.SubgridPlan(part, dtype)
+            self.plan = fused.SubgridPlan(part, dtype, farfield=self.farfield)
             if self.plan.c.has_open_faces:
                 self.plan.attach_inflow(self.inflow_table)
 
@@ -345,7 +384,8 @@ class SubgridSolver(_Solver):
                  stream)
         _timer_end(self, ev)
         if self.B > 0 and self.kinds is not None:
-            hip.call("t8gpu_hip_subgrid_boundary_bc", self.dtype, self.kind, self.rank, self.F, self.B, hip.ptr(self.fn),
+            # (far-field kinds: the kernel that decodes them; plans without them keep the _bc kernel)
+            hip.call("t8gpu_hip_subgrid_boundary_far" if self._far_kinds else "t8gpu_hip_subgrid_boundary_bc", self.dtype, self.kind, self.rank, self.F, self.B, hip.ptr(self.fn),
                      hip.ptr(self.kinds), hip.ptr(self.inflow_table), hip.ptr(self.normals), hip.ptr(self.areas), st, fl, stream)
         elif self.B > 0:
             hip.call("t8gpu_hip_subgrid_boundary", self.dtype, self.kind, self.rank, self.F, self.B,
