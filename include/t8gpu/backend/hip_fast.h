@@ -25,26 +25,7 @@
 
 namespace t8gpu::hip {
 
-  template<typename ft>
-  using vars_t = std::conditional_t<std::is_same_v<ft, float>, T8gpuVars_f32, T8gpuVars_f64>;
-
-  template<typename VariableType>
-  auto to_vars(MemoryAccessorOwn<VariableType> acc) {
-    using ft = typename variable_traits<VariableType>::float_type;
-    static_assert(variable_traits<VariableType>::nb_variables == 5, "the Euler kernels expect Rho, Rho_v1..3, Rho_e");
-    vars_t<ft> v;
-    for (int k = 0; k < 5; k++) v.p[k] = acc.get(k);
-    return v;
-  }
-
-#define T8GPU_DISPATCH(ft, name, ...)                                \
-  do {                                                               \
-    if constexpr (std::is_same_v<ft, float>) {                       \
-      T8GPU_HIP_CHECK_ABI(name##_f32(__VA_ARGS__));                  \
-    } else {                                                         \
-      T8GPU_HIP_CHECK_ABI(name##_f64(__VA_ARGS__));                  \
-    }                                                                \
-  } while (0)
+  // vars_t<ft>, to_vars(accessor) and T8GPU_DISPATCH: t8gpu/mesh/forest_core.h (the managers use them too)
 
   /// replaces kepes_compute_fluxes<<<>>> (kernels.cu:135-309)
   template<typename VariableType, size_t dim>
@@ -85,22 +66,10 @@ namespace t8gpu::hip {
   inline HostMeshArrays host_mesh_arrays_from_query(T8gpuForestQuery const& q, int rank = 0, HostHaloArrays* halo = nullptr) {
     void* h = t8gpu_host_connectivity_create(&q);
     if (!h) T8GPU_ABORT("t8gpu_host_connectivity_create failed (malformed forest query)");
-    int64_t c[6];
-    t8gpu_host_connectivity_counts(h, c);
     HostMeshArrays m;
-    m.num_local_elements = static_cast<int32_t>(c[0]); m.num_ghost_elements = static_cast<int32_t>(c[1]);
-    m.num_local_faces = static_cast<int32_t>(c[2]); m.num_local_boundary_faces = static_cast<int32_t>(c[3]);
+    read_host_connectivity(h, m, halo);
     m.rank = rank;
-    m.face_neighbors.resize(2 * c[2] + c[3]);
-    m.face_normals.resize(3 * (c[2] + c[3]));
-    m.face_surfaces.resize(c[2] + c[3]);
-    m.volumes.resize(c[0] + c[1]);
-    HostHaloArrays hh;
-    hh.peers.resize(c[4]); hh.recv_off.resize(c[4] + 1); hh.send_off.resize(c[4] + 1); hh.send_idx.resize(c[5]);
-    t8gpu_host_connectivity_arrays(h, m.face_neighbors.data(), m.face_normals.data(), m.face_surfaces.data(), m.volumes.data(),
-                                   hh.peers.data(), hh.recv_off.data(), hh.send_off.data(), hh.send_idx.data());
     t8gpu_host_connectivity_destroy(h);
-    if (halo) *halo = std::move(hh);
     return m;
   }
 
@@ -290,15 +259,6 @@ namespace t8gpu::hip {
   };
 
   // ---- Subgrid<4,4> / Subgrid<4,4,4> -------------------------------------------------------------------------
-  template<typename VariableType, typename SubgridType>
-  auto to_vars(SubgridMemoryAccessorOwn<VariableType, SubgridType> acc) {
-    using ft = typename variable_traits<VariableType>::float_type;
-    static_assert(variable_traits<VariableType>::nb_variables == 5, "the Euler kernels expect Rho, Rho_v1..3, Rho_e");
-    vars_t<ft> v;
-    for (int k = 0; k < 5; k++) v.p[k] = acc.data(static_cast<typename variable_traits<VariableType>::index_type>(k));
-    return v;
-  }
-
   using t8gpu::HostSubgridMeshArrays;
 
   /// Device copy of the joined per-block face records (t8gpu_plan_subgrid_create + _records) for the fused

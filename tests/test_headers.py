@@ -34,16 +34,26 @@ def test_reference_style_solver_compiles_against_the_headers(ft):
     compile_example("plain_example.hip", f"plain_example_{ft}", (f"-DT8GPU_FLOAT_TYPE={ft}",))
 
 
-def test_adapt_example_compiles():
-    compile_example("adapt_example.hip", "adapt_example")
+FLOAT_TYPES = ["float", "double"]   # double: nothing else instantiates the fp64 side of adapt / partition / refresh_ghost_layer
 
 
-def test_partition_example_compiles():
-    compile_example("partition_example.hip", "partition_example")
+def compile_example_for(name, ft):
+    return compile_example(f"{name}.hip", f"{name}_{ft}", (f"-DT8GPU_FLOAT_TYPE={ft}",))
 
 
-def test_subgrid_partition_example_compiles():
-    compile_example("subgrid_partition_example.hip", "subgrid_partition_example")
+@pytest.mark.parametrize("ft", FLOAT_TYPES)
+def test_adapt_example_compiles(ft):
+    compile_example_for("adapt_example", ft)
+
+
+@pytest.mark.parametrize("ft", FLOAT_TYPES)
+def test_partition_example_compiles(ft):
+    compile_example_for("partition_example", ft)
+
+
+@pytest.mark.parametrize("ft", FLOAT_TYPES)
+def test_subgrid_partition_example_compiles(ft):
+    compile_example_for("subgrid_partition_example", ft)
 
 
 def test_subgrid_api_compiles():
@@ -108,33 +118,36 @@ def test_subgrid_api_runs(tmp_path):
 
 
 @pytest.mark.gpu
-def test_partition_example_runs():
+@pytest.mark.parametrize("ft", FLOAT_TYPES)
+def test_partition_example_runs(ft):
     """MeshManager::adapt -> partition -> compute_connectivity_information on 2 and 3 ranks (host threads of one process, loopback
     transport: tests/compat/loopback_transport.h) with fused steps in between: bitwise the single-rank run, shares balanced to one
     element (t8gpu/mesh/mesh_manager.inl:196-330, 626-723). Three further scenarios on 2 - 5 ranks -- coarsening below the initial
     level, where a family cut by a rank boundary stays and the forests legitimately differ -- for the invariants: mass conserved,
     balanced shares, every ghost slot equal to its owner's value after refresh_ghost_layer(). The product's transport is t8gpu::RcclTransport over the same interface
     (t8gpu_hip_repartition_*, t8gpu_hip_comm_allgatherv_f64, t8gpu_hip_halo_exchange_*)."""
-    exe = compile_example("partition_example.hip", "partition_example")
+    exe = compile_example_for("partition_example", ft)
     res = subprocess.run([exe], capture_output=True, text=True, timeout=240)
     assert res.returncode == 0 and "partition_example OK" in res.stdout, res.stdout + res.stderr
 
 
 @pytest.mark.gpu
-def test_subgrid_partition_example_runs():
+@pytest.mark.parametrize("ft", FLOAT_TYPES)
+def test_subgrid_partition_example_runs(ft):
     """SubgridMeshManager::adapt -> partition -> compute_connectivity_information on 2 and 3 ranks (loopback transport), whole
     Subgrid<4,4,4> blocks on the wire (cells_per_element = 64), fused block-kernel steps with the ghost blocks refreshed per stage:
     bitwise the single-rank run (t8gpu/mesh/subgrid_mesh_manager.inl:428-558, 1217-1369); the reference's threshold and half of it
     on 2 - 4 ranks (forests differ where a family is cut) for mass, balance and ghost blocks."""
-    exe = compile_example("subgrid_partition_example.hip", "subgrid_partition_example")
+    exe = compile_example_for("subgrid_partition_example", ft)
     res = subprocess.run([exe], capture_output=True, text=True, timeout=240)
     assert res.returncode == 0 and "subgrid_partition_example OK" in res.stdout, res.stdout + res.stderr
 
 
 @pytest.mark.gpu
-def test_adapt_example_runs(tmp_path):
+@pytest.mark.parametrize("ft", FLOAT_TYPES)
+def test_adapt_example_runs(ft, tmp_path):
     """MeshManager::adapt + the adaptive main loop in C++ (tests/compat/adapt_example.hip): mesh changes, mass is kept."""
-    exe = compile_example("adapt_example.hip", "adapt_example")
+    exe = compile_example_for("adapt_example", ft)
     prefix = str(tmp_path / "adapted")
     res = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=dict(os.environ, T8GPU_TEST_VTK_PREFIX=prefix))
     assert res.returncode == 0 and "adapt_example OK" in res.stdout, res.stdout + res.stderr
