@@ -48,12 +48,9 @@ def pressure(solver):
 
 
 def cfl_step(solver, cfl):
-    """cfl * finest cell size / max(|v| + c) of the current state (the same rule for every kind of side)"""
-    u = solver.state().double().cpu().numpy()
-    rho = u[0]
-    v = np.sqrt(u[1] ** 2 + u[2] ** 2 + u[3] ** 2) / rho
-    c = np.sqrt(GAMMA * pressure(solver) / rho)
-    return cfl * 0.5 ** solver.part.mesh.finest_level / float((v + c).max())
+    """cfl * finest cell size / max(|v| + c) of the current state (the same rule for every kind of side); the maximum comes
+    from the device-side state monitor: 128 bytes cross to the host, not the state"""
+    return cfl * 0.5 ** solver.part.mesh.finest_level / solver.monitor().max_speed
 
 
 def main():

@@ -258,6 +258,46 @@ namespace t8gpu::hip {
     }
   };
 
+  /// State monitor (t8gpu_hip_state_monitor_*): the integrals, the entropy, max (|v| + c) and max (|v| + c) / h, min rho,
+  /// min p and the counts of non-finite / non-physical cells of one state, from one pass over it. Owns the workspace and
+  /// the device block (allocate once, reuse). Slots: t8gpu_hip.h; ranks combine blocks by sum / max / min per slot class.
+  class Monitor {
+   public:
+    using block = std::array<double, T8GPU_MONITOR_SLOTS>;
+    Monitor() {
+      T8GPU_CUDA_CHECK_ERROR(hipMalloc(&m_work, t8gpu_hip_state_monitor_workspace_bytes()));
+      T8GPU_CUDA_CHECK_ERROR(hipMalloc(&m_result, sizeof(double) * T8GPU_MONITOR_SLOTS));
+    }
+    ~Monitor() {
+      (void)hipFree(m_work);
+      (void)hipFree(m_result);
+    }
+    Monitor(Monitor const&)            = delete;
+    Monitor& operator=(Monitor const&) = delete;
+    /// enqueue only: the device block (16 doubles), valid on `stream` after the call, overwritten by the next one
+    template<typename ft>
+    [[nodiscard]] double const* run_device(size_t num_cells, int cells_per_element, int dim, vars_t<ft> vars, ft const* volume,
+                                           hipStream_t stream = nullptr) {
+      T8GPU_DISPATCH(ft, t8gpu_hip_state_monitor, num_cells, cells_per_element, dim, vars, volume, m_work, m_result, stream);
+      return m_result;
+    }
+    /// num_cells owned cells (Subgrid: subcells, cells_per_element = SubgridType::size, volume per block); dim = 2 | 3 gives
+    /// the cell length h = (volume / cells_per_element)^(1/dim). One 128-byte copy, one sync.
+    template<typename ft>
+    [[nodiscard]] block run(size_t num_cells, int cells_per_element, int dim, vars_t<ft> vars, ft const* volume,
+                            hipStream_t stream = nullptr) {
+      (void)run_device<ft>(num_cells, cells_per_element, dim, vars, volume, stream);
+      block h{};
+      T8GPU_CUDA_CHECK_ERROR(hipMemcpyAsync(h.data(), m_result, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream));
+      T8GPU_CUDA_CHECK_ERROR(hipStreamSynchronize(stream));
+      return h;
+    }
+
+   private:
+    void*   m_work   = nullptr;
+    double* m_result = nullptr;
+  };
+
   // ---- Subgrid<4,4> / Subgrid<4,4,4> -------------------------------------------------------------------------
   using t8gpu::HostSubgridMeshArrays;
 

@@ -467,6 +467,39 @@ int t8gpu_hip_integral_f32(size_t num_cells, int cells_per_element, const float*
 int t8gpu_hip_integral_f64(size_t num_cells, int cells_per_element, const double* variable, const double* volume,
                            void* workspace, double* result, void* stream);
 
+/* ---- state monitor: CFL rate, integrals, entropy, positivity in one pass ------------------------------
+ * What a run loop asks of the state between steps, from one streaming read of the five planes and the volumes (the
+ * reference answers none of it on the device: compute_integral copies to the host, solver.cu:190-211 and
+ * examples/subgrid/solver.inl:281-305; the Subgrid compute_timestep is unimplemented, solver.inl:309-325).
+ * num_cells = owned cells (Subgrid: subcells); volume per ELEMENT, indexed by i / cells_per_element; the cell volume is
+ * vol = volume[e] / cells_per_element and the cell length h = vol^(1/dim), dim = 2 | 3: the edge of a Cartesian cell, and on
+ * curved cells the cbrt(volume) length of the reference's refinement criterion (solver.cu:240) -- NOT a safe inradius
+ * for prisms and tetrahedra. Arithmetic and accumulation in double for both float types; gamma = 1.4. Per cell
+ *   m2 = mx^2 + my^2 + mz^2,  p = 0.4 (E - m2 / (2 rho)),  c = sqrt(1.4 p / rho),  s = |m| / rho + c;
+ * a cell is FINITE when its five values are, PHYSICAL when finite with rho > 0 and p > 0. result[16] (doubles):
+ *   0-4  sum vol * u_k (rho, mx, my, mz, E)            finite cells
+ *   5    sum vol * m2 / (2 rho)  (kinetic energy)      finite, rho > 0
+ *   6    sum vol * rho * (log p - 1.4 log rho)         physical
+ *   7    max s                                         physical
+ *   8    max s / h  (the CFL step is cfl / this)       physical
+ *   9    min rho                                       finite
+ *   10   min p                                         finite, rho > 0
+ *   11   number of non-finite cells
+ *   12   number of finite, non-physical cells
+ *   13-15  0 (reserved)
+ * Sums and counts 0, maxima 0, minima +inf where no cell qualifies (num_cells = 0). Ranks combine blocks by sum
+ * (0-6, 11, 12), max (7, 8) and min (9, 10). Two launches on `stream` (grid-stride partials, then one workgroup per
+ * slot), no atomics: the same data gives the same bits. 16-byte loads when the five plane pointers are 16-byte
+ * aligned (and the volume pointer, for cells_per_element = 1), one value per lane otherwise.
+ * workspace = t8gpu_hip_state_monitor_workspace_bytes() device bytes. hipErrorInvalidValue for a null workspace or
+ * result, cells_per_element < 1 or dim outside {2, 3}. */
+#define T8GPU_MONITOR_SLOTS 16
+size_t t8gpu_hip_state_monitor_workspace_bytes(void);
+int t8gpu_hip_state_monitor_f32(size_t num_cells, int cells_per_element, int dim, T8gpuVars_f32 state, const float* volume,
+                                void* workspace, double* result /* [16] */, void* stream);
+int t8gpu_hip_state_monitor_f64(size_t num_cells, int cells_per_element, int dim, T8gpuVars_f64 state, const double* volume,
+                                void* workspace, double* result /* [16] */, void* stream);
+
 /* ---- AMR indicator and data transfer for plain elements ---------------------------------
  * estimate_gradient<<<>>>: examples/compressible_euler/kernels.cu:471-501 (|rho_r - rho_l| added to both
  * neighbours; the reference accumulates into its Fluxes/Rho plane, any zeroed plane works). */

@@ -76,10 +76,50 @@ def check_inflow_states(part, inflow_states):
     return s
 
 
+class Monitor:
+    """What one pass of t8gpu_hip_state_monitor_* says about a state (include/t8gpu_hip.h): `block` holds the raw
+    16 doubles, the attributes name its slots. Sums run over the finite cells (kinetic energy: rho > 0 as well; entropy,
+    max_speed, max_rate: the physical cells, finite with rho > 0 and p > 0; min_pressure: finite with rho > 0).
+    entropy = sum vol * rho * (log p - 1.4 log rho): never decreases under the KEPES flux. max_rate = max (|v| + c) / h with the
+    cell length h = vol^(1/dim); a CFL step is cfl / max_rate. With no qualifying cell the maxima are 0 and the minima +inf."""
+    SLOTS = 16
+    SUM_SLOTS, MAX_SLOTS, MIN_SLOTS = (0, 1, 2, 3, 4, 5, 6, 11, 12), (7, 8), (9, 10)
+    __slots__ = ("block",)
+
+    def __init__(self, block):
+        self.block = np.array(block, np.float64, copy=True).reshape(self.SLOTS)
+
+    integrals = property(lambda self: self.block[0:5])
+    kinetic_energy = property(lambda self: float(self.block[5]))
+    entropy = property(lambda self: float(self.block[6]))
+    max_speed = property(lambda self: float(self.block[7]))
+    max_rate = property(lambda self: float(self.block[8]))
+    min_density = property(lambda self: float(self.block[9]))
+    min_pressure = property(lambda self: float(self.block[10]))
+    nonfinite = property(lambda self: int(self.block[11]))
+    unphysical = property(lambda self: int(self.block[12]))
+
+    def __repr__(self):
+        return (f"Monitor(integrals={self.integrals.tolist()}, kinetic_energy={self.kinetic_energy}, entropy={self.entropy}, "
+                f"max_speed={self.max_speed}, max_rate={self.max_rate}, min_density={self.min_density}, "
+                f"min_pressure={self.min_pressure}, nonfinite={self.nonfinite}, unphysical={self.unphysical})")
+
+    @staticmethod
+    def combine(blocks):
+        """The monitor of several ranks' blocks (Monitor objects or arrays of 16 doubles): sums, maxima and minima per slot
+        class. A rank that owns nothing contributes its block of zeros and +inf minima. Pure numpy: needs no GPU."""
+        b = np.stack([np.asarray(getattr(x, "block", x), np.float64).reshape(Monitor.SLOTS) for x in blocks])
+        out = np.zeros(Monitor.SLOTS)
+        out[list(Monitor.SUM_SLOTS)] = b[:, list(Monitor.SUM_SLOTS)].sum(axis=0)
+        out[list(Monitor.MAX_SLOTS)] = b[:, list(Monitor.MAX_SLOTS)].max(axis=0)
+        out[list(Monitor.MIN_SLOTS)] = b[:, list(Monitor.MIN_SLOTS)].min(axis=0)
+        return Monitor(out)
+
+
 class _Solver:
     """What PlainSolver and SubgridSolver share: the step roles (`next` / `prev`, solver.h:100-101), the stage loop with its
-    halo overlap and both step drivers. A solver supplies `owned_cells` (the columns of state()), `_units()` (tiles or
-    blocks of its fused plan), `_stage_compat` and `_native_stepper`."""
+    halo overlap and both step drivers, and the state monitor. A solver supplies `owned_cells` (the columns of state()),
+    `_units()` (tiles or blocks of its fused plan), `_stage_compat`, `_native_stepper` and `_monitor_geometry()`."""
 
     def __init__(self, part, dtype, flux_kind, mode):
         if not torch.cuda.is_available():
@@ -220,6 +260,66 @@ class _Solver:
         for k in range(3):
             self.run_stage(k, delta_t, stream, halo)
 
+    # -- scalar diagnostics, computed on the device ------------------------------------------------
+    def _reduce_buffers(self):
+        if not hasattr(self, "_ws"):
+            n = hip.lib().t8gpu_hip_reduce_workspace_bytes
+            n.restype = C.c_size_t
+            self._ws = torch.zeros(n() // 8, dtype=torch.float64, device="cuda")
+            self._scalar = torch.zeros(1, dtype=torch.float64, device="cuda")
+        return self._ws, self._scalar
+
+    def _monitor_buffers(self):
+        """workspace, device result and pinned host block of the monitor: made on first use and kept"""
+        if not hasattr(self, "_mon"):
+            n = hip.lib().t8gpu_hip_state_monitor_workspace_bytes
+            n.restype = C.c_size_t
+            self._mon = (torch.zeros(n() // 8, dtype=torch.float64, device="cuda"),
+                         torch.zeros(Monitor.SLOTS, dtype=torch.float64, device="cuda"),
+                         torch.zeros(Monitor.SLOTS, dtype=torch.float64).pin_memory())
+        return self._mon
+
+    def monitor_device(self, step=None, stream=None):
+        """One pass of t8gpu_hip_state_monitor_* over the owned cells of state(step) (ghost slots and spare capacity are not
+        read), enqueued on `stream` (default: the current stream): the solver's 16-double device block (slots: Monitor,
+        include/t8gpu_hip.h). No copy, no sync -- for callers that poll or all-reduce on the device. The block is
+        overwritten by the next call."""
+        ws, res, _ = self._monitor_buffers()
+        s = self.next if step is None else step
+        dim, cells_per_element, volumes = self._monitor_geometry()
+        hip.call("t8gpu_hip_state_monitor", self.dtype, C.c_size_t(self.owned_cells), cells_per_element, dim,
+                 self.get_own_variables(s), hip.ptr(volumes), hip.ptr(ws), hip.ptr(res), hip.stream_ptr(stream))
+        return res
+
+    def monitor(self, step=None, stream=None, dist=None):
+        """The Monitor of state(step): one kernel pass, one 128-byte copy to the host, one sync. `dist` combines the ranks'
+        blocks (Monitor.combine) with three all_reduce calls, on the GPU for nccl and on the CPU otherwise."""
+        stream = torch.cuda.current_stream() if stream is None else stream
+        res = self.monitor_device(step, stream)
+        host = self._monitor_buffers()[2]
+        with torch.cuda.stream(stream):
+            host.copy_(res, non_blocking=True)
+        stream.synchronize()
+        block = host.numpy().copy()
+        if dist is not None:
+            mine = torch.from_numpy(block).to("cuda" if dist.get_backend() == "nccl" else "cpu")
+            for op, slots in ((dist.ReduceOp.SUM, Monitor.SUM_SLOTS), (dist.ReduceOp.MAX, Monitor.MAX_SLOTS),
+                              (dist.ReduceOp.MIN, Monitor.MIN_SLOTS)):
+                t = mine.clone()
+                dist.all_reduce(t, op=op)
+                block[list(slots)] = t.cpu().numpy()[list(slots)]
+        return Monitor(block)
+
+    def cfl_timestep(self, cfl=0.7, step=None, dist=None):
+        """cfl / max over the cells of (|v| + c) / h, h = vol^(1/dim), from the state itself: needs no stage to have run (a new
+        solver, a solver fresh from an adapt). On Cartesian cells h is the edge; on curved cells it is cbrt(volume), not an
+        inradius. A state with non-finite or non-physical cells raises instead of giving a step size."""
+        m = self.monitor(step, dist=dist)
+        if m.nonfinite + m.unphysical > 0:
+            raise hip.T8gpuHipError(f"cfl_timestep: the state has {m.nonfinite} non-finite and {m.unphysical} non-physical cells "
+                                    "(rho <= 0 or p <= 0)")
+        return cfl / m.max_rate if m.max_rate > 0 else float("inf")      # (no cells anywhere: no limit)
+
 
 class PlainSolver(_Solver):
     """Plain elements. mode = "compat": reference data flow (face kernel + atomics, RK kernel);
@@ -293,13 +393,8 @@ class PlainSolver(_Solver):
                  self.get_own_variables(dst), fl, hip.ptr(self.planes[25]), hip.fscalar(self.dtype, dt), stream)
 
     # -- scalar diagnostics of the reference solver, computed on the device -----------------------
-    def _reduce_buffers(self):
-        if not hasattr(self, "_ws"):
-            n = hip.lib().t8gpu_hip_reduce_workspace_bytes
-            n.restype = C.c_size_t
-            self._ws = torch.zeros(n() // 8, dtype=torch.float64, device="cuda")
-            self._scalar = torch.zeros(1, dtype=torch.float64, device="cuda")
-        return self._ws, self._scalar
+    def _monitor_geometry(self):
+        return int(self.part.mesh.dim), 1, self.planes[25]     # (the curved meshes of unstructured.py: dim = 3)
 
     def compute_integral(self, variable=0, step=None):
         """sum(volume * variable) over the owned elements (CompressibleEulerSolver::compute_integral)."""
@@ -396,6 +491,18 @@ class SubgridSolver(_Solver):
         hip.call("t8gpu_hip_subgrid_rk3_stage", self.dtype, stage, self.rank, self.N,
                  self.get_own_variables(self.prev), st, self.get_own_variables(dst), fl, hip.ptr(self.volumes),
                  hip.fscalar(self.dtype, dt), stream)
+
+    def _monitor_geometry(self):
+        return self.rank, self.S, self.volumes
+
+    def compute_integral(self, variable=0, step=None):
+        """sum(volume / S * variable) over the owned subcells (SubgridCompressibleEulerSolver::compute_integral,
+        examples/subgrid/solver.inl:281-305, for any variable as on PlainSolver)."""
+        ws, res = self._reduce_buffers()
+        s = self.next if step is None else step
+        hip.call("t8gpu_hip_integral", self.dtype, C.c_size_t(self.owned_cells), self.S, hip.ptr(self.planes[5 * s + variable]),
+                 hip.ptr(self.volumes), hip.ptr(ws), hip.ptr(res), hip.stream_ptr())
+        return float(res.item())
 
     def _units(self):
         return self.N
