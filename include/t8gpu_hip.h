@@ -270,6 +270,21 @@ int t8gpu_hip_plain_fused_stage_f64(int flux_kind, int stage, const T8gpuPlainPl
                                     int tile_count, T8gpuVars_f64 prev, T8gpuVars_f64 mid, T8gpuVars_f64 out,
                                     const double* volume, double delta_t, double* speed_estimates, void* stream);
 
+/* The same with a PLANAR request (ABI 13; planar = 0: exactly the entry points above). planar != 0 is the caller's word that,
+ * over the slots this launch reads and writes, the z-momentum planes (variable 3) of `prev` and `mid` hold the +0 bit pattern
+ * everywhere and that of `out` holds +0 already -- what a 2D run keeps true from step to step. The 2D patch tiles then run a
+ * form of the stage that neither loads nor stores that plane and carries no z terms through the flux; the results are the
+ * general form's bit for bit, signed zeros included, for FINITE states (an infinity or NaN in another variable reaches the
+ * z-momentum in the general form and does not in the planar one). Honoured for KEPES in a whole-plan launch (tile_begin = 0,
+ * tile_count = ntiles) of a plan with 2D patches, no ghost window and no open faces; anything else runs the general form, silently. The
+ * generic tiles of the launch always run the general form. */
+int t8gpu_hip_plain_fused_stage_planar_f32(int flux_kind, int stage, const T8gpuPlainPlan* plan, int tile_begin,
+                                           int tile_count, T8gpuVars_f32 prev, T8gpuVars_f32 mid, T8gpuVars_f32 out,
+                                           const float* volume, float delta_t, float* speed_estimates, void* stream, int planar);
+int t8gpu_hip_plain_fused_stage_planar_f64(int flux_kind, int stage, const T8gpuPlainPlan* plan, int tile_begin,
+                                           int tile_count, T8gpuVars_f64 prev, T8gpuVars_f64 mid, T8gpuVars_f64 out,
+                                           const double* volume, double delta_t, double* speed_estimates, void* stream, int planar);
+
 /* 1 if a whole-plan launch of `tile_count` tiles (flux_kind, float_size = 4 | 8) would run the persistent, software-
  * pipelined tile kernel (kernels_fused_persistent.hip), 0 if it goes to the one-tile-per-workgroup kernels: the launcher's
  * own test, for host code that picks tile caps (t8gpu_amd/fused.py). Only the plan's integer fields and the NULL-ness of
@@ -373,6 +388,20 @@ int t8gpu_hip_plain_stepper_iterate_steps_f64(void* stepper, int flux_kind, doub
  * A stepper WITH a halo always enqueues directly (the two-lane driver), whatever this switch says. */
 int t8gpu_hip_plain_stepper_graph(void* stepper, int enable, int* counts);
 int t8gpu_hip_plain_stepper_timing(void* stepper, int enable);
+/* The planar 2D stage in the step driver (ABI 13). A single-rank stepper over a plain plan with 2D patches, KEPES: at the start
+ * of an iterate / iterate_steps call ONE device reduction ORs the raw bits of the z-momentum planes of the four step slots the
+ * call touches (prev, Step1, Step2, next; the slots the plan addresses) and the host reads the four words after the only
+ * stream synchronisation this adds. prev not all +0: the call runs in the general form. Otherwise the other planes that are
+ * not all +0 are zeroed (hipMemsetAsync; none in steady state) and every stage of the call runs planar
+ * (t8gpu_hip_plain_fused_stage_planar_*). Nothing is remembered from call to call: the caller may write the planes in between.
+ * mode 0 = never, 1 = where the check is amortised (n_steps x elements >= 2^25; the default),
+ * 2 = whenever the check proves it. A plan with open faces (has_open_faces / has_farfield_faces) never runs planar: a
+ * prescribed outside state may carry a z-momentum. A call that checks SYNCHRONISES the stream once, also when the stepper
+ * replays a graph (the check runs before the replay): the host cannot enqueue the next call ahead of the GPU then.
+ * _planar: what the last call DECIDED (1 planar, 0 general); the kernel a stage then launched is named by
+ * t8gpu_hip_last_stage_kernel (the launcher runs the general kernel for launches that are not whole-plan persistent ones). */
+int t8gpu_hip_stepper_set_planar(void* stepper, int mode);
+int t8gpu_hip_stepper_planar(void* stepper);
 /* Diagnostics (scripts/halo_overhead.py): with T8GPU_STEPPER_PROFILE=1 in the environment the step drivers time their own
  * host calls; ns4 / calls4 (may be NULL) receive nanoseconds and counts for {kernel launches, RCCL groups, event records,
  * stream waits} since the last reset. Returns 1 when the profile is on, 0 when off (all zeros). */
@@ -455,6 +484,10 @@ int t8gpu_hip_subgrid_stepper_iterate_steps_f64(void* stepper, int flux_kind, do
  * scalars (double) written on `stream`; `workspace` = t8gpu_hip_reduce_workspace_bytes() device bytes.
  * Fixed reduction tree, no atomics: bitwise reproducible. */
 size_t t8gpu_hip_reduce_workspace_bytes(void);
+/* out4[j] |= OR of the raw bits of planes[j][0 .. n) for j < 4 (float_type planes; out4: DEVICE uint32_t[4], zeroed by the
+ * caller; for 64-bit values the two halves are ORed together). 0 means: every value is +0. One atomic OR per workgroup. */
+int t8gpu_hip_planes_or_bits_f32(size_t n, const float* const planes[4], uint32_t* out4, void* stream);
+int t8gpu_hip_planes_or_bits_f64(size_t n, const double* const planes[4], uint32_t* out4, void* stream);
 /* max over the per-face speed estimates: thrust::reduce(..., maximum) in compute_timestep,
  * examples/compressible_euler/solver.cu:213-217 (the caller all-reduces the scalar across ranks, :218-223,
  * and forms dt = cfl * 0.5^max_level / speed, :225-228). */

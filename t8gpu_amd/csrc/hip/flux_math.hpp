@@ -663,6 +663,106 @@ T8_DEV void kepes_core(const Prim<T>& L, const Prim<T>& R, T uL, T vL, T wL, T u
   f[4] = t8_fma(-half, t8_fma(hp, d4, t8_fma(w, d3, t8_fma(v, d2, t8_fma(k2, d1, hm * d0)))), Fs4);
 }
 
+// ---- PLANAR forms (2D meshes whose z-momentum plane is all +0: kernels_fused_patch.hip, PLANAR instantiations) ---------------
+// The same values as the general forms give for vz = +0 in both cells, bit for bit and signed zeros included, for FINITE
+// physical operands (rho, p, area > 0). An infinity or NaN in another variable reaches the z flux in the general form
+// (0 * inf) and cannot here: the planar kernels are for finite states only.
+//
+// prim_from_state with s[3] = +0: vz = +0 * ir = +0 (ir > 0), and in ke the term fma(vy, vy, vz * vz) = vy^2 + (+0) is
+// vy * vy: a square is never -0, so adding +0 changes nothing. s = {rho, mx, my, E}; q.vz is not set.
+template <class T, bool TAB = false>
+T8_DEV Prim<T> prim_from_state_planar(const T s[4], const double* logtab = nullptr) {
+#pragma clang fp contract(off)
+  const T one = T(1), half = T(0.5), kappa = T(1.4);
+  const T km1 = kappa - one;
+  Prim<T> q;
+  const T ir = t8_rcp(s[0]);
+  q.rho      = s[0];
+  q.vx       = s[1] * ir;
+  q.vy       = s[2] * ir;
+  const T ke = half * t8_fma(q.vx, q.vx, q.vy * q.vy);
+  q.p        = km1 * t8_fma(-s[0], ke, s[3]);
+  const T rp = t8_div(s[0], q.p);
+  q.beta     = half * rp;
+  q.lrho     = TAB ? t8_log_tab(s[0], logtab) : t8_log_fast(s[0]);
+  const T lp = TAB ? t8_log_tab(q.p, logtab) : t8_log_fast(q.p);
+  q.lbeta    = q.lrho - lp;
+  q.v0       = t8_fma(-rp, ke, (kappa - t8_fma(-kappa, q.lrho, lp)) * (one / km1));
+  return q;
+}
+
+// kepes_core for a face with normal +e_x or +e_y of such a mesh: (uL, tL), (uR, tR) are the normal and the IN-PLANE tangential
+// velocity; f = {mass, normal momentum, in-plane tangential momentum, energy}. The general form gets the frame of patch_face():
+//   x-faces (v, w) = (-vz, vy) = (-0, t),   y-faces (v, w) = (vx, -vz) = (t, -0).
+// Call z the slot that holds -0 on both sides. What the general form computes with it, and why each dropped term is an identity:
+//   q2    z * z = +0 enters as fma(z, z, t * t) = (+0) + t^2 or as fma(t, t, +0): a square is never -0, so both are t * t.
+//   dot   the inner sum is t_L t_R with a -0 canonicalised to +0 (x-faces: (+0) + round(t_L t_R); y-faces: fma(t_L, t_R, +0)).
+//         Dropped: dot then differs at most in the sign of a zero, and only when u_L u_R is an exact zero too. Its consumers
+//         do not see that sign: h adds half * dot to kappa / (2 (kappa - 1)) * ib > 0, and k2 adds it to q2, which is never -0
+//         (half a sum of squares), so q2 + (+-0) = q2.
+//   Fs4   z-mean = half * (-0 + -0) = -0, Fs_z = Fs0 * (-0). The products z * Fs_z and t * Fs_t both carry the sign of Fs0
+//         ((-)(-) sign(Fs0), and sign(t)^2 sign(Fs0)), so where t * Fs_t is a zero the two zeros have one sign and their sum
+//         keeps it; where it is not, adding a zero changes nothing: fma(v, Fs2, w * Fs3) = t * Fs_t on both kinds of face.
+//   J_z   = fma(rpR, -0, -(rpL * -0)) = (-0) + (+0) = +0 (rpL, rpR = 2 beta > 0).
+//   c     x-faces: fma(-0, +0, J0) = (-0) + J0 = J0; y-faces: fma(-0, +0, fma(t, Jt, J0)) likewise: x + (-0) = x for every x.
+//   d_z   = D2 * fma(-0, J4, +0) = D2 * (+0) = +0 (a zero of either sign plus +0 is +0; D2 = |u| p1 area >= 0).
+//   f[4]  the term z * d_z = (-0)(+0) = -0 enters by fma(z, d_z, X) = X + (-0) = X (x-faces: innermost but one, y-faces: next).
+//   f_z   = +-0, summed by the patch body as fma(1, f, 0) ...: the z row of `acc` is +0 whatever the signs, and the RK stage of a
+//         plane whose previous and source values are +0 is fma(scale, +0, +0) = +0 (stages 2, 3 alike): the stored z-momentum
+//         is +0, which a planar launch finds in place already.
+// Everything else is the text of kepes_core with v or w renamed t.
+template <class T>
+T8_DEV void kepes_core_planar(const Prim<T>& L, const Prim<T>& R, T uL, T tL, T uR, T tR, T area, T f[4], T& speed) {
+#pragma clang fp contract(off)
+  const T one = T(1), half = T(0.5), kappa = T(1.4);
+  const T km1 = kappa - one, skm1 = one / km1, ikappa = one / kappa;
+  const T q2 = half * (t8_fma(uL, uL, tL * tL) + t8_fma(uR, uR, tR * tR));
+
+  const T bsum = L.beta + R.beta, rbs = t8_rcp_shared(bsum);
+  const T rho  = ln_mean_dlog(L.rho, R.rho, R.lrho - L.lrho);
+  const T ib   = ln_mean_inv_dlog_rs(L.beta, R.beta, R.lbeta - L.lbeta, bsum, rbs);
+  const T rho_mean = half * (L.rho + R.rho);
+  const T u = half * (uL + uR), t = half * (tL + tR);
+  const T a  = t8_sqrt_ratio(kappa * half * (L.p + R.p), rho);
+  const T dot = t8_fma(uL, uR, tL * tR);
+  const T h   = t8_fma(kappa / (T(2) * km1), ib, half * dot);
+  const T p1 = t8_div_by(rho_mean, bsum, rbs);
+
+  const T rho_a = rho * area, p1_a = p1 * area;
+  const T Fs0 = rho_a * u;
+  const T Fs1 = t8_fma(Fs0, u, p1_a);
+  const T Fst = Fs0 * t;
+  const T Fs4 = t8_fma(Fs0 * half, t8_fma(skm1, ib, -q2), t8_fma(u, Fs1, t * Fst));
+
+  speed = t8_abs(u) + a;
+
+  const T au = t8_abs(u);
+  const T ra = rho_a * (half * ikappa), re = rho_a * (km1 * ikappa);
+  const T D0 = t8_abs(u - a) * ra;
+  const T D1 = au * re;
+  const T D2 = au * p1_a;
+  const T D4 = t8_abs(u + a) * ra;
+
+  const T rpL = L.beta + L.beta, rpR = R.beta + R.beta;
+  const T J0 = R.v0 - L.v0;
+  const T J1 = t8_fma(rpR, uR, -(rpL * uL));
+  const T Jt = t8_fma(rpR, tR, -(rpL * tL));
+  const T J4 = rpL - rpR;
+
+  const T ua = u * a;
+  const T hm = h - ua, hp = h + ua, k2 = T(0.25) * (q2 + dot);
+  const T c  = t8_fma(t, Jt, J0);
+  const T d0 = D0 * t8_fma(hm, J4, t8_fma(u - a, J1, c));
+  const T d1 = D1 * t8_fma(k2, J4, t8_fma(u, J1, c));
+  const T dt = D2 * t8_fma(t, J4, Jt);
+  const T d4 = D4 * t8_fma(hp, J4, t8_fma(u + a, J1, c));
+  const T s014 = d0 + d1 + d4;
+  f[0] = t8_fma(-half, s014, Fs0);
+  f[1] = t8_fma(-half, t8_fma(u + a, d4, t8_fma(u, d1, (u - a) * d0)), Fs1);
+  f[2] = t8_fma(-half, t8_fma(t, s014, dt), Fst);
+  f[3] = t8_fma(-half, t8_fma(hp, d4, t8_fma(t, dt, t8_fma(k2, d1, hm * d0))), Fs4);
+}
+
 // The rotation into the face frame and back, spelled out once (same reason: one rounding sequence everywhere).
 template <class T>
 T8_DEV T dot3(T x, T y, T z, const T b[3]) {

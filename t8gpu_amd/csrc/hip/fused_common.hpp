@@ -342,6 +342,20 @@ T8_DEV void words_prim(const T w[kPrimWords], Prim<T>& q) {
   q.rho = w[0]; q.vx = w[1]; q.vy = w[2]; q.vz = w[3]; q.p = w[4]; q.beta = w[5]; q.lrho = w[6]; q.lbeta = w[7]; q.v0 = w[8];
 }
 
+// PLANAR records (kernels_fused_patch.hip): no vz word. Eight payload words in a record of the SAME stride as the nine-word one
+// (rec_words: 10 doubles / 12 floats), so consecutive records keep starting in different bank groups -- eight doubles packed
+// would put the 16-byte record reads of neighbouring cells on four bank groups.
+constexpr int kPrimWordsPlanar = 8;
+template <class T>
+T8_DEV void prim_words_planar(const T s[4], T w[kPrimWordsPlanar], const double* logtab) {
+  const Prim<T> q = prim_from_state_planar<T, sizeof(T) == 8>(s, logtab);
+  w[0] = q.rho; w[1] = q.vx; w[2] = q.vy; w[3] = q.p; w[4] = q.beta; w[5] = q.lrho; w[6] = q.lbeta; w[7] = q.v0;
+}
+template <class T>
+T8_DEV void words_prim_planar(const T w[kPrimWordsPlanar], Prim<T>& q) {
+  q.rho = w[0]; q.vx = w[1]; q.vy = w[2]; q.p = w[3]; q.beta = w[4]; q.lrho = w[5]; q.lbeta = w[6]; q.v0 = w[7];
+}
+
 // persistent, software-pipelined tile kernel (kernels_fused_persistent.hip). Returns -1 when the plan is outside what
 // that kernel takes (the caller then uses the one-tile-per-workgroup kernels), otherwise 0 or a hipError_t.
 template <class T>
@@ -349,10 +363,13 @@ int plain_persistent_stage(int kind, int stage, const T8gpuPlainPlan* plan, int 
                            FVars<T> mid, FVars<T> out, const T* volume, T dt, T* speed, hipStream_t stream);
 
 // structured-patch kernel (kernels_fused_patch.hip): [patch_begin, +patch_count) of tile_order are patch tiles; the generic
-// tiles [tile_begin, +tile_count) ride in the same launch where the mixed kernel takes them (-1: it does not; launch apart)
+// tiles [tile_begin, +tile_count) ride in the same launch where the mixed kernel takes them (-1: it does not; launch apart).
+// planar: the caller vouches for the planar contract (t8gpu_hip.h: t8gpu_hip_plain_fused_stage_planar_*); honoured for KEPES
+// in a persistent launch without a ghost window, otherwise the general form runs.
 template <class T>
 int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch_begin, int patch_count, int tile_begin, int tile_count,
-                      FVars<T> prev, FVars<T> mid, FVars<T> out, const T* volume, T dt, T* speed, bool persistent, hipStream_t stream);
+                      FVars<T> prev, FVars<T> mid, FVars<T> out, const T* volume, T dt, T* speed, bool persistent, bool planar,
+                      hipStream_t stream);
 
 // 3D structured patches (kernels_fused_patch3.hip): [tile_begin, +tile_count) of tile_order are 8 x 8 x 4 patch tiles, all
 // regular or (irregular = true) all irregular ones

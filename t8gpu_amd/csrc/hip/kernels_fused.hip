@@ -115,7 +115,7 @@ int plain_generic_stage(int kind, int stage, const T8gpuPlainPlan* plan, int til
 // (the kernels above / the persistent kernel). Inside every class the patch tiles come first (T8gpuPlainPlan).
 template <class T, class V>
 int plain_fused_stage(int kind, int stage, const T8gpuPlainPlan* plan, int tile_begin, int tile_count, V prev, V mid,
-                      V out, const T* volume, T dt, T* speed, void* stream) {
+                      V out, const T* volume, T dt, T* speed, int planar, void* stream) {
   if (!plan || kind < 0 || kind > 2 || stage < 1 || stage > 3) return static_cast<int>(hipErrorInvalidValue);
   if (tile_begin < 0 || tile_count < 0 || tile_begin + tile_count > plan->ntiles) return static_cast<int>(hipErrorInvalidValue);
   if (plan->max_elems > 256 * 4) return static_cast<int>(hipErrorInvalidValue);
@@ -145,6 +145,10 @@ int plain_fused_stage(int kind, int stage, const T8gpuPlainPlan* plan, int tile_
   const int b = tile_begin, e = tile_begin + tile_count;
   static const bool persistent_always = std::getenv("T8GPU_PERSISTENT") && std::getenv("T8GPU_PERSISTENT")[0] == '2';
   const bool        persistent        = whole || persistent_always;   // (patch launches: persistent grids)
+  // the planar form of the 2D patch body (kernels_fused_patch.hip): whole-plan launches of a plan without a ghost window and
+  // without open faces (their prescribed outside state may carry a z-momentum, which the general tiles would write), KEPES
+  const bool planar_ok = planar != 0 && kind == 0 && tile_begin == 0 && tile_count == plan->ntiles && plan->patch_dim != 3 &&
+                         !plan->ghost_buf && !plan->send_map && !plan->has_open_faces && !plan->has_farfield_faces;
   const hipStream_t s                 = static_cast<hipStream_t>(stream);
   // generic sub-ranges that touch are launched together (single rank: one patch launch + one generic launch)
   int gb = -1, ge = -1;
@@ -192,10 +196,10 @@ int plain_fused_stage(int kind, int stage, const T8gpuPlainPlan* plan, int tile_
       // (the persistent tile kernel where the range covers the plan)
       const bool mixed = qe > qb && static_cast<long long>(pe - pb) * 256 >= static_cast<long long>(qe - qb) * 128;
       int rc = plain_patch_stage<T>(kind, stage, plan, pb, pe - pb, qb, mixed ? qe - qb : 0, fmk<T>(prev), fmk<T>(mid), fmk<T>(out), volume,
-                                    dt, speed, persistent, s);
+                                    dt, speed, persistent, planar_ok, s);
       if (rc == -1)   // (the mixed kernel does not take this plan's generic tiles)
         rc = plain_patch_stage<T>(kind, stage, plan, pb, pe - pb, qb, 0, fmk<T>(prev), fmk<T>(mid), fmk<T>(out), volume, dt, speed,
-                                  persistent, s);
+                                  persistent, planar_ok, s);
       else if (rc == 0 && mixed)
         qe = qb;   // done
       if (rc != 0) return rc;
@@ -273,12 +277,24 @@ int t8gpu_hip_plain_fused_stage_f32(int kind, int stage, const T8gpuPlainPlan* p
                                     T8gpuVars_f32 prev, T8gpuVars_f32 mid, T8gpuVars_f32 out, const float* volume,
                                     float dt, float* speed, void* stream) {
   return t8gpu_hip::plain_fused_stage<float>(kind, stage, plan, tile_begin, tile_count, prev, mid, out, volume, dt,
-                                             speed, stream);
+                                             speed, 0, stream);
 }
 int t8gpu_hip_plain_fused_stage_f64(int kind, int stage, const T8gpuPlainPlan* plan, int tile_begin, int tile_count,
                                     T8gpuVars_f64 prev, T8gpuVars_f64 mid, T8gpuVars_f64 out, const double* volume,
                                     double dt, double* speed, void* stream) {
   return t8gpu_hip::plain_fused_stage<double>(kind, stage, plan, tile_begin, tile_count, prev, mid, out, volume, dt,
-                                              speed, stream);
+                                              speed, 0, stream);
+}
+int t8gpu_hip_plain_fused_stage_planar_f32(int kind, int stage, const T8gpuPlainPlan* plan, int tile_begin, int tile_count,
+                                           T8gpuVars_f32 prev, T8gpuVars_f32 mid, T8gpuVars_f32 out, const float* volume,
+                                           float dt, float* speed, void* stream, int planar) {
+  return t8gpu_hip::plain_fused_stage<float>(kind, stage, plan, tile_begin, tile_count, prev, mid, out, volume, dt,
+                                             speed, planar, stream);
+}
+int t8gpu_hip_plain_fused_stage_planar_f64(int kind, int stage, const T8gpuPlainPlan* plan, int tile_begin, int tile_count,
+                                           T8gpuVars_f64 prev, T8gpuVars_f64 mid, T8gpuVars_f64 out, const double* volume,
+                                           double dt, double* speed, void* stream, int planar) {
+  return t8gpu_hip::plain_fused_stage<double>(kind, stage, plan, tile_begin, tile_count, prev, mid, out, volume, dt,
+                                              speed, planar, stream);
 }
 }

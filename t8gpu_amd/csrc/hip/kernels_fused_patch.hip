@@ -37,14 +37,24 @@ namespace t8gpu_hip {
 // chunk = 0: persistent walk -- the XCD's workgroups stride through its share together (tiles j, j + n, ...); chunk = c > 0:
 // workgroup j of the XCD takes the c CONSECUTIVE tiles [j c, j c + c) of the share and leaves (a grid of ~count / c
 // workgroups that the hardware hands out as slots free up: what a launch beside other kernels wants, see plain_patch_stage)
-template <class T, int KIND, int STAGE, bool NT>
+//
+// PLANAR (KEPES only): the launch's contract is that the z-momentum planes of `prev` and `src` are all +0 over the slots it reads
+// and that of `out` is +0 already over the slots it writes (2D meshes; the native stepper proves it per call, stepper.hip). The
+// body then carries four variables: no load of src.p[3] / prev.p[3] (own cells, side cells, prefetch), no store to out.p[3], no
+// vz word in the LDS records, four flux planes in ff, no z primitive and no z RK update -- and stores the bits the general form
+// stores (flux_math.hpp: kepes_core_planar has the argument term by term). FINITE states only: an infinity or NaN in another
+// variable would reach the z plane in the general form and does not here.
+template <class T, int KIND, int STAGE, bool NT, bool PLANAR = false>
 T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_count, int wg, int nwg, int chunk, const FVars<T>& prev,
                              const FVars<T>& src, const FVars<T>& out, const T* __restrict__ vol, T dt, T* __restrict__ speed) {
-  constexpr int NW  = KIND == 0 ? kPrimWords : 5;
+  static_assert(!PLANAR || KIND == 0, "the planar form exists for KEPES");
+  constexpr int NV  = PLANAR ? 4 : 5;                              // variables carried; variable c lives in plane pl(c)
+  constexpr int NW  = KIND == 0 ? (PLANAR ? kPrimWordsPlanar : kPrimWords) : 5;
   constexpr int REC = rec_words<T, NW>();
+  auto pl = [](int c) { return PLANAR && c == 3 ? 4 : c; };
   extern __shared__ __attribute__((aligned(16))) double lds_raw[];
-  T* const  ff = reinterpret_cast<T*>(lds_raw);               // [5][kPatchFF] the patch's face fluxes
-  T* const  pe = ff + 5 * kPatchFF;                           // [320][REC] primitives (or states): 256 own, 64 across the sides
+  T* const  ff = reinterpret_cast<T*>(lds_raw);               // [NV][kPatchFF] the patch's face fluxes
+  T* const  pe = ff + NV * kPatchFF;                          // [320][REC] primitives (or states): 256 own, 64 across the sides
   constexpr bool kTab = sizeof(T) == 8 && KIND == 0;          // fp64 KEPES: the logarithm table, behind the records
   double* const lt = reinterpret_cast<double*>(pe + REC * 320);
   const int tid = threadIdx.x;
@@ -107,23 +117,23 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
     return d;
   };
   struct Pre {
-    T s0[5], sh[5];
+    T s0[NV], sh[NV];
   };
   // first: the prologue's request. A launch with a ghost window (t8gpu_hip.h; the multi-rank driver's ghost-reading class)
   // runs one patch per workgroup -- plain_patch_stage() sees to it -- so only that request can meet a ghost slot.
   auto prefetch = [&](const Desc& d, int hslot, bool first, bool halo_wave) {
     Pre p;
 #pragma unroll
-    for (int k = 0; k < 5; k++) p.s0[k] = at32<T>(src.p[k], static_cast<unsigned>(d.e0 + tid));
-    if (halo_wave && first && P.ghost_buf) {
+    for (int k = 0; k < NV; k++) p.s0[k] = at32<T>(src.p[pl(k)], static_cast<unsigned>(d.e0 + tid));
+    if (!PLANAR && halo_wave && first && P.ghost_buf) {   // (a planar launch has no ghost window: plain_patch_stage)
 #pragma unroll
-      for (int k = 0; k < 5; k++) p.sh[k] = ghost_window_load<T>(P, src, hslot, k);
+      for (int k = 0; k < NV; k++) p.sh[k] = ghost_window_load<T>(P, src, hslot, pl(k));
     } else if (halo_wave) {
 #pragma unroll
-      for (int k = 0; k < 5; k++) p.sh[k] = at32<T>(src.p[k], static_cast<unsigned>(hslot));
+      for (int k = 0; k < NV; k++) p.sh[k] = at32<T>(src.p[pl(k)], static_cast<unsigned>(hslot));
     } else {
 #pragma unroll
-      for (int k = 0; k < 5; k++) p.sh[k] = T(0);
+      for (int k = 0; k < NV; k++) p.sh[k] = T(0);
     }
     return p;
   };
@@ -133,7 +143,9 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
   int       hs_a = role(0) == 3 ? P.halo_ids[d0.h0 + hl] : 0, hs_b = role(1) == 3 ? P.halo_ids[d1.h0 + hl] : 0;
   Pre       cur = prefetch(d0, hs_a, true, role(0) == 3);
   int       it  = 0;
-  T         res[5] = {T(0), T(0), T(0), T(0), T(0)};
+  T         res[NV];
+#pragma unroll
+  for (int k = 0; k < NV; k++) res[k] = T(0);
   int       res_e  = -1;
   __builtin_amdgcn_s_waitcnt(0);   // (see k_plain_persistent: the prologue's loads must not become a wait inside the loop)
 
@@ -144,10 +156,12 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
     Pre        nxt;
     if (t + stride < tend) nxt = prefetch(d1, hs_b, false, role(it + 1) == 3);
     const int e = d0.e0 + tid;
-    T         pv[5] = {T(0), T(0), T(0), T(0), T(0)};
+    T         pv[NV];
+#pragma unroll
+    for (int k = 0; k < NV; k++) pv[k] = T(0);
     if (STAGE > 1) {
 #pragma unroll
-      for (int k = 0; k < 5; k++) pv[k] = stream_load<NT>(&at32<T>(prev.p[k], static_cast<unsigned>(e)));
+      for (int k = 0; k < NV; k++) pv[k] = stream_load<NT>(&at32<T>(prev.p[pl(k)], static_cast<unsigned>(e)));
     }
     // (patches of uniform volume carry it in their descriptor: 8 of ~130 bytes per element and stage less to load)
     const T volume = (d0.flags & 0x400) ? static_cast<T>(d0.vol) : at32<T>(vol, static_cast<unsigned>(e));
@@ -155,7 +169,9 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
 
     // ---- phase 1: records of the own cell and (wave 3) of the cells across the sides ----------------------------------
     T mine[NW];
-    if (KIND == 0) {
+    if constexpr (PLANAR) {
+      prim_words_planar<T>(cur.s0, mine, lt);
+    } else if constexpr (KIND == 0) {
       prim_words<T>(cur.s0, mine, lt);
     } else {
 #pragma unroll
@@ -164,7 +180,9 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
     rec_store<T, NW>(pe + tid * REC, mine);
     if (halo_wave) {
       T w[NW];
-      if (KIND == 0) {
+      if constexpr (PLANAR) {
+        prim_words_planar<T>(cur.sh, w, lt);
+      } else if constexpr (KIND == 0) {
         prim_words<T>(cur.sh, w, lt);
       } else {
 #pragma unroll
@@ -174,22 +192,28 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
     }
     if (res_e >= 0) {   // results of the previous patch: behind this iteration's first wait (vmcnt retires in order)
 #pragma unroll
-      for (int k = 0; k < 5; k++) stream_store<NT>(&at32<T>(out.p[k], static_cast<unsigned>(res_e)), res[k]);
+      for (int k = 0; k < NV; k++) stream_store<NT>(&at32<T>(out.p[pl(k)], static_cast<unsigned>(res_e)), res[k]);
     }
     __syncthreads();
 
     // ---- phase 2: the lane's +x and +y faces; the - sides ------------------------------------------------------------
-    T gy[5];
+    auto face = [&](bool y, const T* wl, const T* wr, T* g, T& spd) {
+      if constexpr (PLANAR)
+        patch_face_planar<T>(y, wl, wr, area, g, spd);
+      else
+        patch_face<T, KIND, NW>(y, wl, wr, area, g, spd);
+    };
+    T gy[NV];
     {
-      T wr[NW], g[5], sx, sy;
+      T wr[NW], g[NV], sx, sy;
       rec_load<T, NW>(pe + rx * REC, wr);
-      patch_face<T, KIND, NW>(false, mine, wr, area, g, sx);
+      face(false, mine, wr, g, sx);
 #pragma unroll
-      for (int k = 0; k < 5; k++) ff[k * kPatchFF + tid] = g[k];
+      for (int k = 0; k < NV; k++) ff[k * kPatchFF + tid] = g[k];
       rec_load<T, NW>(pe + ry * REC, wr);
-      patch_face<T, KIND, NW>(true, mine, wr, area, gy, sy);
+      face(true, mine, wr, gy, sy);
 #pragma unroll
-      for (int k = 0; k < 5; k++) ff[k * kPatchFF + 256 + tid] = gy[k];
+      for (int k = 0; k < NV; k++) ff[k * kPatchFF + 256 + tid] = gy[k];
       if (speed) {   // the patch's own faces: ids fbase + 2 t (+x) and fbase + 2 t + 1 (+y): one 16-byte store where aligned
         T* const sp = speed + d0.fbase + 2 * tid;
         if ((d0.fbase & 1) == 0 || sizeof(T) == 4) {   // (wave-uniform; fp32: an 8-byte store is aligned for every fbase)
@@ -205,21 +229,21 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
       }
     }
     if (minus_lane) {
-      T wl[NW], wr[NW], g[5], sm;
+      T wl[NW], wr[NW], g[NV], sm;
       rec_load<T, NW>(pe + m_l * REC, wl);
       rec_load<T, NW>(pe + m_r * REC, wr);
-      patch_face<T, KIND, NW>(minus_y, wl, wr, area, g, sm);
+      face(minus_y, wl, wr, g, sm);
 #pragma unroll
-      for (int k = 0; k < 5; k++) ff[k * kPatchFF + 512 + ln] = g[k];
+      for (int k = 0; k < NV; k++) ff[k * kPatchFF + 512 + ln] = g[k];
     }
     __syncthreads();
 
     // ---- phase 3: the four fluxes in ascending face id, RK stage -------------------------------------------------------
     const bool yfirst = tid == 0 ? (d0.flags & 1) != 0 : yfirst_lane;
     const int  a1 = yfirst ? a_my : a_mx, a2 = yfirst ? a_mx : a_my;
-    T          acc[5];
+    T          acc[NV];
 #pragma unroll
-    for (int k = 0; k < 5; k++) {
+    for (int k = 0; k < NV; k++) {
       acc[k] = __builtin_fma(T(1), ff[k * kPatchFF + a1], T(0));
       acc[k] = __builtin_fma(T(1), ff[k * kPatchFF + a2], acc[k]);
       acc[k] = __builtin_fma(T(-1), ff[k * kPatchFF + tid], acc[k]);
@@ -228,7 +252,7 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
     // (a patch of uniform volume: its operands are wave-uniform -- the power-of-two test runs on scalar registers)
     const T scale = (d0.flags & 0x400) ? rk_scale(dt, static_cast<T>(d0.vol)) : dt / volume;
 #pragma unroll
-    for (int k = 0; k < 5; k++) res[k] = rk_stage_update<T, STAGE>(pv[k], cur.s0[k], scale, acc[k]);
+    for (int k = 0; k < NV; k++) res[k] = rk_stage_update<T, STAGE>(pv[k], cur.s0[k], scale, acc[k]);
     res_e = e;
 
     cur  = nxt;
@@ -238,17 +262,18 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
   }
   if (res_e >= 0) {
 #pragma unroll
-    for (int k = 0; k < 5; k++) stream_store<NT>(&at32<T>(out.p[k], static_cast<unsigned>(res_e)), res[k]);
-    if (P.send_map) ghost_window_send<T>(P, res_e, res);   // (one patch per workgroup there: this is its only store)
+    for (int k = 0; k < NV; k++) stream_store<NT>(&at32<T>(out.p[pl(k)], static_cast<unsigned>(res_e)), res[k]);
+    if constexpr (!PLANAR)
+      if (P.send_map) ghost_window_send<T>(P, res_e, res);   // (one patch per workgroup there: this is its only store)
   }
 }
 
 // (second launch bound = waves per SIMD the register allocation must allow: 3 workgroups per CU in fp64, 5 in fp32)
-template <class T, int KIND, int STAGE, bool NT>
+template <class T, int KIND, int STAGE, bool NT, bool PLANAR = false>
 __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_patch(T8gpuPlainPlan P, int tile_begin, int tile_count, int chunk, FVars<T> prev,
                                                                                 FVars<T> src, FVars<T> out, const T* __restrict__ vol, T dt,
                                                                                 T* __restrict__ speed) {
-  plain_patch_body<T, KIND, STAGE, NT>(P, tile_begin, tile_count, blockIdx.x, gridDim.x, chunk, prev, src, out, vol, dt, speed);
+  plain_patch_body<T, KIND, STAGE, NT, PLANAR>(P, tile_begin, tile_count, blockIdx.x, gridDim.x, chunk, prev, src, out, vol, dt, speed);
 }
 
 // ONE launch per stage for a range of tile_order that holds patch tiles AND generic tiles: the first `patch_wgs`
@@ -256,14 +281,16 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_patch(T8g
 // the generic tiles of the benchmark mesh -- 3 % of its elements -- cost 9 % of the stage: a launch of their own, started
 // when the patch launch has drained. Here they start as the persistent patch workgroups finish and fill the ragged end.
 // OPEN: the plan has outflow / inflow faces -- only its generic tiles can see them (a cell with an open face is in no patch)
-template <class T, int KIND, int STAGE, bool NT, bool OPEN = false>
+// PLANAR: the patch workgroups run the planar body; the generic tiles keep the general form (they read the zeros of the
+// z-momentum plane and write +0, as the contract has it), so the kernel's register count is the larger of the two bodies'.
+template <class T, int KIND, int STAGE, bool NT, bool OPEN = false, bool PLANAR = false>
 __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_stage(T8gpuPlainPlan P, int patch_begin, int patch_count, int patch_wgs, int chunk,
                                                                                 int tile_begin, int tile_count, FVars<T> prev, FVars<T> src,
                                                                                 FVars<T> out, const T* __restrict__ vol, T dt,
                                                                                 T* __restrict__ speed) {
   const int b = blockIdx.x;
   if (b < patch_wgs) {
-    plain_patch_body<T, KIND, STAGE, NT>(P, patch_begin, patch_count, b, patch_wgs, chunk, prev, src, out, vol, dt, speed);
+    plain_patch_body<T, KIND, STAGE, NT, PLANAR>(P, patch_begin, patch_count, b, patch_wgs, chunk, prev, src, out, vol, dt, speed);
   } else {
     const int pos = tile_begin + xcd_position(b - patch_wgs, tile_count);
     plain_tile_body<T, KIND, STAGE, true, 2, false, OPEN>(P, pos, prev, src, out, vol, dt, speed);
@@ -276,13 +303,15 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_stage(T8g
 // that the mixed kernel does not take (the caller then launches the two parts separately), else 0 or a hipError_t.
 template <class T>
 int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch_begin, int patch_count, int tile_begin, int tile_count,
-                      FVars<T> prev, FVars<T> mid, FVars<T> out, const T* volume, T dt, T* speed, bool persistent, hipStream_t stream) {
+                      FVars<T> prev, FVars<T> mid, FVars<T> out, const T* volume, T dt, T* speed, bool persistent, bool planar,
+                      hipStream_t stream) {
   if (patch_count <= 0) return tile_count > 0 ? -1 : 0;
   // (does this launch run beside another lane's kernels? a plan with ghost-reading tiles, launched in part)
   const bool shared_gpu = plan->n_interior_tiles < plan->ntiles && patch_count + (tile_count > 0 ? tile_count : 0) < plan->ntiles;
   if (!plan->tile_desc) return static_cast<int>(hipErrorInvalidValue);
   if (!plan_planes_fit_32bit<T>(plan)) return static_cast<int>(hipErrorInvalidValue);
-  size_t lds = record_lds<T>(kind, static_cast<size_t>(5) * kPatchFF, 320);
+  if (plan->ghost_buf || plan->send_map || !persistent || kind != 0) planar = false;   // (the general form, silently)
+  size_t lds = record_lds<T>(kind, static_cast<size_t>(planar ? 4 : 5) * kPatchFF, 320);
   // (far-field faces: the generic tiles run k_plain_fused_p_far in a launch of their own -- under the mixed kernel's register
   //  budget of 3 / 5 workgroups per CU their far-field state spills)
   if (tile_count > 0 && plan->has_farfield_faces) return -1;
@@ -329,23 +358,24 @@ int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch
   // non-temporal stage results / previous-state loads where the stage's planes are a stream for the caches (flux_math.hpp)
   const bool nt = stream_hint(plan->n_slots_addressed, sizeof(T));
   return dispatch(
-      [&](auto K, auto S, auto NT, auto MIXED, auto OPEN) {
+      [&](auto K, auto S, auto NT, auto MIXED, auto OPEN, auto PLANAR) {
+        constexpr bool PL = PLANAR && K == 0;   // (HLL / HLLC: nothing new is instantiated)
         if constexpr (MIXED) {
-          note_stage_kernel<T>(patch_count + tile_count, "k_plain_stage", K, S, NT, OPEN);
-          return launch(&k_plain_stage<T, K, S, NT, OPEN>, grid, block, lds, stream, *plan, patch_begin, patch_count, patch_wgs, chunk,
+          note_stage_kernel<T>(patch_count + tile_count, "k_plain_stage", K, S, NT, OPEN, PL);
+          return launch(&k_plain_stage<T, K, S, NT, OPEN, PL>, grid, block, lds, stream, *plan, patch_begin, patch_count, patch_wgs, chunk,
                         tile_begin, tile_count, prev, mid, out, volume, dt, speed);
         } else {
-          note_stage_kernel<T>(patch_count, "k_plain_patch", K, S, NT);
-          return launch(&k_plain_patch<T, K, S, NT>, grid, block, lds, stream, *plan, patch_begin, patch_count, chunk, prev, mid, out, volume,
+          note_stage_kernel<T>(patch_count, "k_plain_patch", K, S, NT, PL);
+          return launch(&k_plain_patch<T, K, S, NT, PL>, grid, block, lds, stream, *plan, patch_begin, patch_count, chunk, prev, mid, out, volume,
                         dt, speed);
         }
       },
-      kind, stage, nt, tile_count > 0, tile_count > 0 && plan->has_open_faces);
+      kind, stage, nt, tile_count > 0, tile_count > 0 && plan->has_open_faces, planar);
 }
 
 template int plain_patch_stage<float>(int, int, const T8gpuPlainPlan*, int, int, int, int, FVars<float>, FVars<float>, FVars<float>,
-                                      const float*, float, float*, bool, hipStream_t);
+                                      const float*, float, float*, bool, bool, hipStream_t);
 template int plain_patch_stage<double>(int, int, const T8gpuPlainPlan*, int, int, int, int, FVars<double>, FVars<double>, FVars<double>,
-                                       const double*, double, double*, bool, hipStream_t);
+                                       const double*, double, double*, bool, bool, hipStream_t);
 
 }  // namespace t8gpu_hip

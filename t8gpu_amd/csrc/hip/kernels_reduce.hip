@@ -7,6 +7,7 @@
 // Both become a two-level device reduction (grid-stride partials per workgroup -> one workgroup) that
 // writes a device scalar, stays on the stream and is bitwise reproducible (fixed tree, no atomics).
 // The integral accumulates in double whatever float_type is.
+// A third one serves the step driver: the OR of the raw bits of four planes (is a plane all +0?).
 #include <hip/hip_runtime.h>
 
 #include "t8gpu_hip.h"
@@ -89,9 +90,72 @@ int integral(size_t ncells, int cpe, const T* u, const T* volume, void* workspac
   return static_cast<int>(hipGetLastError());
 }
 
+// ---- are these planes all +0? (stepper.hip: the planar decision of a 2D run) --------------------------------------------------
+// OR of the raw 32-bit words of four planes of `nwords` words each, one plane per blockIdx.y: 16-byte loads over the aligned
+// body (four in flight per lane), the at most three words before and after it by workgroup 0, a wavefront OR by shuffles and
+// ONE atomic OR per workgroup into out[plane] (skipped where the workgroup saw only zero bits). -0.0 has a bit set, +0 has none.
+struct OrPlanes {
+  const uint32_t* p[4];
+};
+__global__ __launch_bounds__(256) void k_planes_or_bits(OrPlanes P, size_t nwords, uint32_t* __restrict__ out) {
+  const uint32_t* const p = P.p[blockIdx.y];
+  size_t head = ((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2;   // words before the first 16-byte boundary
+  if (head > nwords) head = nwords;
+  const size_t       nvec = (nwords - head) >> 2;
+  const size_t       tail = nwords - head - 4 * nvec;                       // < 4
+  const uint4* const v    = reinterpret_cast<const uint4*>(p + head);
+  const size_t       step = static_cast<size_t>(gridDim.x) * 256;
+  uint32_t           acc  = 0;
+  size_t             i    = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+  for (; i + 3 * step < nvec; i += 4 * step) {
+    const uint4 a = v[i], b = v[i + step], c = v[i + 2 * step], d = v[i + 3 * step];
+    acc |= (a.x | a.y | a.z | a.w) | (b.x | b.y | b.z | b.w) | (c.x | c.y | c.z | c.w) | (d.x | d.y | d.z | d.w);
+  }
+  for (; i < nvec; i += step) {
+    const uint4 a = v[i];
+    acc |= a.x | a.y | a.z | a.w;
+  }
+  if (blockIdx.x == 0) {
+    if (threadIdx.x < head) acc |= p[threadIdx.x];
+    if (threadIdx.x < tail) acc |= p[head + 4 * nvec + threadIdx.x];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc |= __shfl_xor(acc, off, 64);
+  __shared__ uint32_t part[4];
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t r = part[0] | part[1] | part[2] | part[3];
+    if (r) atomicOr(out + blockIdx.y, r);
+  }
+}
+
+template <class T>
+int planes_or_bits(size_t n, const T* const planes[4], uint32_t* out4, void* stream) {
+  if (!planes || !out4) return static_cast<int>(hipErrorInvalidValue);
+  if (n == 0) return 0;
+  OrPlanes P;
+  for (int j = 0; j < 4; j++) {
+    if (!planes[j]) return static_cast<int>(hipErrorInvalidValue);
+    P.p[j] = reinterpret_cast<const uint32_t*>(planes[j]);
+  }
+  const size_t nwords = n * (sizeof(T) / 4);
+  const size_t per    = 256 * 4 * 4;   // words a workgroup takes per round of its loop
+  size_t       nb     = (nwords + per - 1) / per;
+  nb                  = nb < 1 ? 1 : (nb > 2048 ? 2048 : nb);
+  hipLaunchKernelGGL(k_planes_or_bits, dim3(static_cast<unsigned>(nb), 4), dim3(256), 0, static_cast<hipStream_t>(stream), P, nwords, out4);
+  return static_cast<int>(hipGetLastError());
+}
+
 }  // namespace t8gpu_hip
 
 extern "C" {
+int t8gpu_hip_planes_or_bits_f32(size_t n, const float* const planes[4], uint32_t* out4, void* stream) {
+  return t8gpu_hip::planes_or_bits<float>(n, planes, out4, stream);
+}
+int t8gpu_hip_planes_or_bits_f64(size_t n, const double* const planes[4], uint32_t* out4, void* stream) {
+  return t8gpu_hip::planes_or_bits<double>(n, planes, out4, stream);
+}
 size_t t8gpu_hip_reduce_workspace_bytes(void) { return sizeof(double) * t8gpu_hip::kReduceBlocks; }
 int t8gpu_hip_max_speed_f32(size_t n, const float* speed, void* workspace, double* result, void* stream) {
   return t8gpu_hip::max_speed<float>(n, speed, workspace, result, stream);

@@ -82,6 +82,21 @@ T8_DEV void patch_face(bool y, const T* wl, const T* wr, T area, T g[5], T& spd)
   frame_out<T>(y, f, g);
 }
 
+// PLANAR form of patch_face<T, 0, kPrimWords> (flux_math.hpp: kepes_core_planar has the argument): records without a vz word,
+// g = {mass, x-momentum, y-momentum, energy}. frame_in() routes the in-plane tangential velocity to v on y-faces and to w on
+// x-faces, frame_out() brings its flux back from there; the z slot is not carried.
+template <class T>
+T8_DEV void patch_face_planar(bool y, const T* wl, const T* wr, T area, T g[4], T& spd) {
+  Prim<T> L, R;
+  words_prim_planar<T>(wl, L);
+  words_prim_planar<T>(wr, R);
+  T f[4];
+  kepes_core_planar<T>(L, R, y ? L.vy : L.vx, y ? L.vx : L.vy, y ? R.vy : R.vx, y ? R.vx : R.vy, area, f, spd);
+  g[0] = f[0];
+  g[1] = y ? f[2] : f[1];
+  g[2] = y ? f[1] : f[2];
+  g[3] = f[3];
+}
 
 // the same for a compile-time (or wave-uniform) axis 0 / 1 / 2: the frames of kepes_axis_fixed (flux_math.hpp) with s = +1
 template <class T>

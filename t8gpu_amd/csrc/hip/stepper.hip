@@ -87,6 +87,12 @@ struct Stepper {
   GraphEntry      graph_cache[4];
   unsigned long   graph_clock = 0;
   int             graph_captures = 0, graph_replays = 0;
+  // the planar 2D stage (t8gpu_hip.h: t8gpu_hip_stepper_set_planar; planar_decide below)
+  int             planar_mode = 1;      // 0 never, 1 where the check is amortised, 2 whenever proven
+  bool            planar_now  = false;  // the current call runs planar
+  int             planar_last = 0;      // what the last call did
+  uint32_t*       d_bits = nullptr;     // device: OR of the bits of the four z-momentum planes
+  uint32_t*       h_bits = nullptr;     // pinned host copy
 
   // ---- lanes: the two-lane driver (iterate_lanes); a single rank launches on the deep lane ---------------------------------
   static constexpr int kRing = 4;
@@ -220,16 +226,17 @@ int launch_stage(Stepper* S, Stepper::Lane& L, int kind, const T8gpuPlainPlan* p
   if (n <= 0) return 0;
   HostTimer ht(0);
   if (sample) T8_TRY(lane_tick(L));
+  const int planar = S->planar_now ? 1 : 0;   // (0: exactly t8gpu_hip_plain_fused_stage_*)
   if constexpr (sizeof(T) == 4) {
     if (S->subgrid)
       T8_TRY(t8gpu_hip_subgrid_fused_stage_f32(kind, a.k + 1, &S->splan, b, n, a.pv, a.sv, a.ov, vol, dt, L.stream));
     else
-      T8_TRY(t8gpu_hip_plain_fused_stage_f32(kind, a.k + 1, plan, b, n, a.pv, a.sv, a.ov, vol, dt, a.stage_speed, L.stream));
+      T8_TRY(t8gpu_hip_plain_fused_stage_planar_f32(kind, a.k + 1, plan, b, n, a.pv, a.sv, a.ov, vol, dt, a.stage_speed, L.stream, planar));
   } else {
     if (S->subgrid)
       T8_TRY(t8gpu_hip_subgrid_fused_stage_f64(kind, a.k + 1, &S->splan, b, n, a.pv, a.sv, a.ov, vol, dt, L.stream));
     else
-      T8_TRY(t8gpu_hip_plain_fused_stage_f64(kind, a.k + 1, plan, b, n, a.pv, a.sv, a.ov, vol, dt, a.stage_speed, L.stream));
+      T8_TRY(t8gpu_hip_plain_fused_stage_planar_f64(kind, a.k + 1, plan, b, n, a.pv, a.sv, a.ov, vol, dt, a.stage_speed, L.stream, planar));
   }
   if (sample) T8_TRY(lane_tick(L));
   return 0;
@@ -450,6 +457,64 @@ int iterate(Stepper* S, int kind, T* planes, size_t stride, const T* vol, int pr
   return 0;
 }
 
+// ---- the planar decision (single rank, plain plan with 2D patches, KEPES) ------------------------------------------------------
+// On a 2D mesh the z-momentum is +0 in every cell and stays +0, and the patch kernels have a form that neither moves nor computes
+// it (kernels_fused_patch.hip: PLANAR). Its contract -- the z-momentum planes of everything a stage reads are all +0 bit patterns,
+// that of what it writes is +0 already -- is PROVEN here at the start of every call, never assumed: one reduction ORs the raw bits
+// of that plane in the four step slots the call touches (prev, Step1, Step2, next) over the slots the plan addresses; the host
+// reads the four words through pinned memory after the one stream synchronisation this costs.
+//   prev not all +0 (a 3D-like state, a -0.0 somewhere): the whole call runs the general form;
+//   else: whichever of the other three is not all +0 (stale stage values, NaN of a fresh allocation) is zeroed -- the general form
+//   would store +0 there anyway (flux_math.hpp: kepes_core_planar) -- and every stage of the call runs planar. Between the check
+//   and the end of the call only this call's kernels write those planes. That they keep them +0 holds for interior, periodic and
+//   wall faces (the outside state of a wall mirrors the inside one: no z-momentum comes in). It does NOT hold for open boundaries:
+//   the generic tiles of the launch evaluate inflow and far-field faces against a prescribed state (inflow_entry), which may carry
+//   a z-momentum (a 2.5D setup), and stage 1 would then write a non-zero z-momentum that the planar stages 2 and 3 never read.
+//   A plan with open faces of any kind (outflow included: no argument is made for it) therefore always runs the general form;
+//   the launcher refuses the planar request for such plans too (kernels_fused.hip).
+// Nothing is remembered across calls: callers write the planes in between (a restored initial state, an adapted mesh).
+// Auto mode asks for n_steps x elements >= kPlanarAutoWork, where the check is amortised (DESIGN.md section 4 has the measured
+// costs); a call on a capturing stream cannot synchronise and runs the general form. In graph mode the check runs before the
+// replay, so a call that checks synchronises the caller's stream once: the host cannot enqueue the next call ahead of the GPU.
+// planar_last is the DECISION of the last call; what the launcher then ran is t8gpu_hip_last_stage_kernel's to say (it takes the
+// general kernel for launches that are not whole-plan persistent ones).
+constexpr long long kPlanarAutoWork = 1ll << 25;
+template <class T>
+int planar_decide(Stepper* S, int kind, T* planes, size_t stride, int prev, int next, int n_steps, hipStream_t s) {
+  S->planar_now  = false;
+  S->planar_last = 0;
+  const T8gpuPlainPlan& P = S->plan;
+  if (S->planar_mode == 0 || S->has_halo || S->subgrid || kind != T8GPU_FLUX_KEPES || n_steps <= 0 || !planes) return 0;
+  if (P.patch_dim == 3 || P.n_patch_tiles[0] + P.n_patch_tiles[1] + P.n_patch_tiles[2] <= 0 || P.ghost_buf || P.send_map) return 0;
+  if (P.has_open_faces || P.has_farfield_faces) return 0;   // (a prescribed outside state may carry a z-momentum: see above)
+  const size_t n = P.n_slots_addressed > 0 ? static_cast<size_t>(P.n_slots_addressed) : 0;
+  if (n == 0 || n > stride) return 0;
+  if (S->planar_mode == 1 && static_cast<long long>(n_steps) * static_cast<long long>(n) < kPlanarAutoWork) return 0;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  if (!S->d_bits) T8_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&S->d_bits), 4 * sizeof(uint32_t)));
+  if (!S->h_bits) T8_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->h_bits), 4 * sizeof(uint32_t), hipHostMallocDefault));
+  const int slot[4] = {prev, 1, 2, next};   // Step1 = 1, Step2 = 2 (stage_args)
+  T*        zp[4];
+  for (int j = 0; j < 4; j++) zp[j] = planes + (static_cast<size_t>(slot[j]) * 5 + 3) * stride;
+  T8_HIP_TRY(hipMemsetAsync(S->d_bits, 0, 4 * sizeof(uint32_t), s));
+  if constexpr (sizeof(T) == 4)
+    T8_TRY(t8gpu_hip_planes_or_bits_f32(n, zp, S->d_bits, s));
+  else
+    T8_TRY(t8gpu_hip_planes_or_bits_f64(n, zp, S->d_bits, s));
+  T8_HIP_TRY(hipMemcpyAsync(S->h_bits, S->d_bits, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  T8_HIP_TRY(hipStreamSynchronize(s));
+  if (S->h_bits[0] != 0) return 0;
+  for (int j = 1; j < 4; j++)
+    if (S->h_bits[j] != 0) T8_HIP_TRY(hipMemsetAsync(zp[j], 0, n * sizeof(T), s));
+  S->planar_now  = true;
+  S->planar_last = 1;
+  return 0;
+}
+
 // iterate() of a single-rank stepper through a hipGraph: capture the enqueue sequence once per argument set, then replay
 // it. The capture runs on the stepper's own origin stream (the caller's stream may be the legacy default stream, which
 // cannot capture). Timing events are off in graph mode, and a stepper with peers always enqueues directly (the two-lane
@@ -462,11 +527,12 @@ int iterate_graph(Stepper* S, int kind, T* planes, size_t stride, const T* vol, 
   if (!S->graph_mode || S->timing > 0 || n_steps <= 0 || S->has_halo)
     return iterate<T, V>(S, kind, planes, stride, vol, prev, next, dt, speed, n_steps, s);
   struct Key {
-    int kind, prev, next, n_steps, tsize, subgrid;
+    int kind, prev, next, n_steps, tsize, subgrid, planar, pad;   // (planar: the call's decision picks other kernels)
     const void *planes, *vol, *speed;
     size_t stride;
     double dt;
-  } key{kind, prev, next, n_steps, static_cast<int>(sizeof(T)), S->subgrid ? 1 : 0, planes, vol, speed, stride, static_cast<double>(dt)};
+  } key{kind, prev, next, n_steps, static_cast<int>(sizeof(T)), S->subgrid ? 1 : 0, S->planar_now ? 1 : 0, 0, planes, vol, speed, stride,
+        static_cast<double>(dt)};
   static_assert(sizeof(Key) <= sizeof(S->graph_cache[0].key), "graph key");
   if (!S->graph_stream) {
     T8_HIP_TRY(hipStreamCreateWithFlags(&S->graph_stream, hipStreamNonBlocking));
@@ -791,6 +857,8 @@ int t8gpu_hip_plain_stepper_destroy(void* h) {
     for (hipEvent_t e : L->ring)
       if (e) (void)hipEventDestroy(e);
   }
+  if (S->d_bits) (void)hipFree(S->d_bits);
+  if (S->h_bits) (void)hipHostFree(S->h_bits);
   if (S->d_send_map) (void)hipFree(S->d_send_map);
   if (S->d_send_list) (void)hipFree(S->d_send_list);
   if (S->ev_state) (void)hipEventDestroy(S->ev_state);
@@ -816,6 +884,7 @@ int t8gpu_hip_plain_stepper_iterate_steps_f32(void* h, int flux_kind, float* pla
                                               float delta_t, float* speed, int n_steps, void* stream) {
   if (!h || prev < 0 || prev > 3 || next < 0 || next > 3 || prev == next || n_steps < 0) return static_cast<int>(hipErrorInvalidValue);
   if (static_cast<Stepper*>(h)->subgrid) return static_cast<int>(hipErrorInvalidValue);
+  T8_TRY(planar_decide<float>(static_cast<Stepper*>(h), flux_kind, planes, stride, prev, next, n_steps, static_cast<hipStream_t>(stream)));
   return iterate_graph<float, T8gpuVars_f32>(static_cast<Stepper*>(h), flux_kind, planes, stride, planes + 25 * stride, prev, next,
                                              delta_t, speed, n_steps, static_cast<hipStream_t>(stream));
 }
@@ -823,6 +892,7 @@ int t8gpu_hip_plain_stepper_iterate_steps_f64(void* h, int flux_kind, double* pl
                                               double delta_t, double* speed, int n_steps, void* stream) {
   if (!h || prev < 0 || prev > 3 || next < 0 || next > 3 || prev == next || n_steps < 0) return static_cast<int>(hipErrorInvalidValue);
   if (static_cast<Stepper*>(h)->subgrid) return static_cast<int>(hipErrorInvalidValue);
+  T8_TRY(planar_decide<double>(static_cast<Stepper*>(h), flux_kind, planes, stride, prev, next, n_steps, static_cast<hipStream_t>(stream)));
   return iterate_graph<double, T8gpuVars_f64>(static_cast<Stepper*>(h), flux_kind, planes, stride, planes + 25 * stride, prev, next,
                                               delta_t, speed, n_steps, static_cast<hipStream_t>(stream));
 }
@@ -899,6 +969,17 @@ int t8gpu_hip_runtime_versions(int out4[4]) {
   out4[2] = HIP_VERSION;
   out4[3] = hipRuntimeGetVersion(&hv) == hipSuccess ? hv : -1;
   return 0;
+}
+
+int t8gpu_hip_stepper_set_planar(void* h, int mode) {
+  Stepper* S = static_cast<Stepper*>(h);
+  if (!S || mode < 0 || mode > 2) return static_cast<int>(hipErrorInvalidValue);
+  S->planar_mode = mode;
+  return 0;
+}
+int t8gpu_hip_stepper_planar(void* h) {
+  Stepper* S = static_cast<Stepper*>(h);
+  return S ? S->planar_last : 0;
 }
 
 int t8gpu_hip_plain_stepper_timing(void* h, int enable) {

@@ -128,6 +128,15 @@ class NativeStepper:
         hip.check(hip.lib().t8gpu_hip_plain_stepper_graph(self.handle, -1 if enable is None else int(bool(enable)), counts))
         return counts[0], counts[1]
 
+    def set_planar(self, mode):
+        """The planar 2D stage (t8gpu_hip_stepper_set_planar): 0 never, 1 where its check is amortised (default), 2 whenever
+        the check proves the z-momentum planes all +0."""
+        hip.check(hip.lib().t8gpu_hip_stepper_set_planar(self.handle, int(mode)))
+
+    def planar(self):
+        """1 if the last iterate / iterate_steps call ran the planar form, else 0."""
+        return int(hip.lib().t8gpu_hip_stepper_planar(self.handle))
+
     def timing(self, enable):
         hip.check(hip.lib().t8gpu_hip_plain_stepper_timing(self.handle, int(enable)))
 
