@@ -276,8 +276,10 @@ int t8gpu_hip_plain_fused_stage_f64(int flux_kind, int stage, const T8gpuPlainPl
  * form of the stage that neither loads nor stores that plane and carries no z terms through the flux; the results are the
  * general form's bit for bit, signed zeros included, for FINITE states (an infinity or NaN in another variable reaches the
  * z-momentum in the general form and does not in the planar one). Honoured for KEPES in a whole-plan launch (tile_begin = 0,
- * tile_count = ntiles) of a plan with 2D patches, no ghost window and no open faces; anything else runs the general form, silently. The
- * generic tiles of the launch always run the general form. */
+ * tile_count = ntiles) of a plan with 2D patches, no ghost window and no open faces -- and, in fp64 (ABI 14), with the five planes of `prev` (stages 2, 3), `mid` and `out` equally
+ * spaced, all by the spacing of `mid` (rows of one array, as the step drivers pass them: the kernel addresses plane k as
+ * p[0] + k x spacing); anything else runs the general form, silently. The generic tiles of the launch always run the general
+ * form. */
 int t8gpu_hip_plain_fused_stage_planar_f32(int flux_kind, int stage, const T8gpuPlainPlan* plan, int tile_begin,
                                            int tile_count, T8gpuVars_f32 prev, T8gpuVars_f32 mid, T8gpuVars_f32 out,
                                            const float* volume, float delta_t, float* speed_estimates, void* stream, int planar);
@@ -294,6 +296,11 @@ int t8gpu_hip_plain_persistent_accepts(const T8gpuPlainPlan* plan, int flux_kind
  * (ELL rows + tile descriptors), whose callers need not upload the CSR lists: the launcher's own test, from the plan's
  * integer fields and the NULL-ness of ell / tile_desc alone; no GPU is needed. */
 int t8gpu_hip_plain_needs_csr(const T8gpuPlainPlan* plan);
+/* Bytes of dynamic LDS of a workgroup of the 2D patch launch (kernels_fused_patch.hip) for flux_kind and float_size = 4 | 8, in
+ * the planar form if `planar` (honoured for KEPES, as by the launcher): the patch body's window, or -- `plan` not NULL: its generic
+ * tiles ride in the same launch -- the larger of that and the tile body's window for the plan's max_slots. The launcher's own
+ * sizes; a planar fp64 launch holds four workgroups per CU where this is at most 40 960. -1: bad arguments. No GPU is needed. */
+int t8gpu_hip_plain_patch_lds_bytes(const T8gpuPlainPlan* plan, int flux_kind, int float_size, int planar);
 /* The tangent rows of a geometry dictionary ALREADY ON THE DEVICE (`geo_table`: n_geo rows {n, area} {t1, .} {t2, .} of the
  * plan's float type), recomputed from its normals by the routine the per-face kernels use (flux_math.hpp: face_basis_fast --
  * the frame of kernels.cu:174-193 with one reciprocal square root instead of a square root and three divisions). Plan builders

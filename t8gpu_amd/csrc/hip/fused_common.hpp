@@ -342,9 +342,10 @@ T8_DEV void words_prim(const T w[kPrimWords], Prim<T>& q) {
   q.rho = w[0]; q.vx = w[1]; q.vy = w[2]; q.vz = w[3]; q.p = w[4]; q.beta = w[5]; q.lrho = w[6]; q.lbeta = w[7]; q.v0 = w[8];
 }
 
-// PLANAR records (kernels_fused_patch.hip): no vz word. Eight payload words in a record of the SAME stride as the nine-word one
-// (rec_words: 10 doubles / 12 floats), so consecutive records keep starting in different bank groups -- eight doubles packed
-// would put the 16-byte record reads of neighbouring cells on four bank groups.
+// PLANAR records (kernels_fused_patch.hip): no vz word. fp32: eight payload words in a record of the SAME stride as the nine-word
+// one (rec_words: 12 floats), so consecutive records keep starting in different bank groups. fp64: 64 bytes per record, in
+// chunk planes (rec_split_store / rec_split_load below) -- eight doubles side by side would put the 16-byte record reads of
+// neighbouring cells on four bank groups.
 constexpr int kPrimWordsPlanar = 8;
 template <class T>
 T8_DEV void prim_words_planar(const T s[4], T w[kPrimWordsPlanar], const double* logtab) {
@@ -354,6 +355,33 @@ T8_DEV void prim_words_planar(const T s[4], T w[kPrimWordsPlanar], const double*
 template <class T>
 T8_DEV void words_prim_planar(const T w[kPrimWordsPlanar], Prim<T>& q) {
   q.rho = w[0]; q.vx = w[1]; q.vy = w[2]; q.p = w[3]; q.beta = w[4]; q.lrho = w[5]; q.lbeta = w[6]; q.v0 = w[7];
+}
+
+// PLANAR fp64 records (kernels_fused_patch.hip): the eight payload doubles take 64 bytes -- 320 records 20 480 bytes instead of
+// 25 600, which is what lets a fourth workgroup per CU fit the LDS -- stored as FOUR PLANES OF 16-BYTE CHUNKS: chunk c (words 2 c,
+// 2 c + 1) of record r lies at 16 r + c x (16 x records). A wavefront reads chunk c of its lanes' records with one ds_read_b128,
+// and records r, r' meet in a bank group only where r = r' (mod 16): the behaviour of the padded records (80 bytes = 5 bank
+// groups, 5 odd), where 64-byte records side by side would put neighbouring cells on four bank groups. A record is named by
+// the byte offset 16 r of its first chunk; the plane stride is a compile-time constant and rides in the instruction's offset.
+constexpr int kSplitChunkBytes = 16;
+template <int RECORDS>
+T8_DEV void rec_split_store(double* recs, int off0, const double w[kPrimWordsPlanar]) {
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    double2 v;
+    v.x = w[2 * c];
+    v.y = w[2 * c + 1];
+    *reinterpret_cast<double2*>(reinterpret_cast<char*>(recs) + off0 + c * (kSplitChunkBytes * RECORDS)) = v;
+  }
+}
+template <int RECORDS>
+T8_DEV void rec_split_load(const double* recs, int off0, double w[kPrimWordsPlanar]) {
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    const double2 v = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(recs) + off0 + c * (kSplitChunkBytes * RECORDS));
+    w[2 * c]     = v.x;
+    w[2 * c + 1] = v.y;
+  }
 }
 
 // persistent, software-pipelined tile kernel (kernels_fused_persistent.hip). Returns -1 when the plan is outside what

@@ -44,13 +44,17 @@ namespace t8gpu_hip {
 // vz word in the LDS records, four flux planes in ff, no z primitive and no z RK update -- and stores the bits the general form
 // stores (flux_math.hpp: kepes_core_planar has the argument term by term). FINITE states only: an infinity or NaN in another
 // variable would reach the z plane in the general form and does not here.
+// PLANAR in fp64 (SPLIT below) is built for FOUR workgroups per CU: a register budget of 128 VGPRs, which the patch body
+// meets without a spill (113 / 123 / 123 in stages 1 / 2 / 3), 64-byte LDS records in chunk planes (fused_common.hpp: 39 936 bytes
+// per workgroup against 45 056 with the padded records) and the state planes addressed as base + k x spacing.
 template <class T, int KIND, int STAGE, bool NT, bool PLANAR = false>
 T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_count, int wg, int nwg, int chunk, const FVars<T>& prev,
                              const FVars<T>& src, const FVars<T>& out, const T* __restrict__ vol, T dt, T* __restrict__ speed) {
   static_assert(!PLANAR || KIND == 0, "the planar form exists for KEPES");
   constexpr int NV  = PLANAR ? 4 : 5;                              // variables carried; variable c lives in plane pl(c)
   constexpr int NW  = KIND == 0 ? (PLANAR ? kPrimWordsPlanar : kPrimWords) : 5;
-  constexpr int REC = rec_words<T, NW>();
+  constexpr bool SPLIT = PLANAR && sizeof(T) == 8;                   // 64-byte records in four chunk planes (fused_common.hpp)
+  constexpr int  REC = SPLIT ? kPrimWordsPlanar : rec_words<T, NW>();
   auto pl = [](int c) { return PLANAR && c == 3 ? 4 : c; };
   extern __shared__ __attribute__((aligned(16))) double lds_raw[];
   T* const  ff = reinterpret_cast<T*>(lds_raw);               // [NV][kPatchFF] the patch's face fluxes
@@ -58,6 +62,39 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
   constexpr bool kTab = sizeof(T) == 8 && KIND == 0;          // fp64 KEPES: the logarithm table, behind the records
   double* const lt = reinterpret_cast<double*>(pe + REC * 320);
   const int tid = threadIdx.x;
+  // a record is named by its handle: the word offset of record r, or (SPLIT) the byte offset of its first chunk
+  auto rec_at = [](int r) { return SPLIT ? kSplitChunkBytes * r : r * REC; };
+  auto store_rec = [&](int h, const T* w) {
+    if constexpr (SPLIT)
+      rec_split_store<320>(reinterpret_cast<double*>(pe), h, reinterpret_cast<const double*>(w));
+    else
+      rec_store<T, NW>(pe + h, w);
+  };
+  auto load_rec = [&](int h, T* w) {
+    if constexpr (SPLIT)
+      rec_split_load<320>(reinterpret_cast<const double*>(pe), h, reinterpret_cast<double*>(w));
+    else
+      rec_load<T, NW>(pe + h, w);
+  };
+
+  // Plane k of a state. SPLIT: the launch's contract is that the planes of prev, src and out are EQUALLY SPACED, all by the
+  // spacing of src (plain_patch_stage checks it; the step drivers' planes are rows of one array): a plane is p[0] + k x spacing,
+  // two scalar instructions where it is used, instead of twelve pointers held in scalar registers through the loop -- with them
+  // the stage kernel's loop reloaded 60 - 114 spilled scalars per patch (v_readlane: VALU work). The spacing is made opaque once
+  // per iteration, so that the plane addresses are not hoisted out of the loop into as many register pairs again. (Measured on
+  // c4, ms per step: pointers 0.681, this 0.666; each address opaque where it is formed -- scalar adds, but more scalar spills
+  // in stages 2 and 3 -- 0.679.)
+  using GT = __attribute__((address_space(1))) T;
+  long pstride = 0;
+  if constexpr (SPLIT) pstride = reinterpret_cast<const char*>(src.p[1]) - reinterpret_cast<const char*>(src.p[0]);
+  auto plane = [&](const FVars<T>& v, int k) -> T* {
+    if constexpr (SPLIT) {
+      uintptr_t a = reinterpret_cast<uintptr_t>(v.p[0]) + static_cast<uintptr_t>(pl(k) * pstride);
+      return (T*)reinterpret_cast<GT*>(a);
+    } else {
+      return v.p[pl(k)];
+    }
+  };
 
   // this workgroup's patches (same walk as k_plain_persistent: XCD x takes one contiguous eighth of the range, its
   // workgroups walk it together)
@@ -82,8 +119,9 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
     cj |= ((tid >> (2 * b + 1)) & 1) << b;
   }
   // records of the right operands of the lane's faces; flux slots of its - faces (the + faces of the cells across)
-  const int  rx   = ci < 15 ? patch_morton(ci + 1, cj) : 272 + cj;
-  const int  ry   = cj < 15 ? patch_morton(ci, cj + 1) : 304 + ci;
+  const int  rx   = rec_at(ci < 15 ? patch_morton(ci + 1, cj) : 272 + cj);
+  const int  ry   = rec_at(cj < 15 ? patch_morton(ci, cj + 1) : 304 + ci);
+  const int  rme  = rec_at(tid);
   const int  a_mx = ci > 0 ? patch_morton(ci - 1, cj) : 512 + cj;
   const int  a_my = cj > 0 ? 256 + patch_morton(ci, cj - 1) : 528 + ci;
   const bool yfirst_lane = patch_ctz4(cj) >= patch_ctz4(ci);   // (cell (0, 0): per patch, from the descriptor)
@@ -98,8 +136,8 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
   auto role = [&](int it) { return (wv + it) & 3; };
   const int  hl      = ln;                                     // side-cell lane: cell hl of [-x | +x | -y | +y] x 16
   const bool minus_y = ln >= 16;                               // - face lanes 0-31 of the role-0 wavefront: -x side, then -y side
-  const int  m_l = 256 + (minus_y ? 32 : 0) + (ln & 15);       // left operand: the cell across; right: the patch's cell
-  const int  m_r = minus_y ? patch_morton(ln & 15, 0) : patch_morton(0, ln & 15);
+  const int  m_l = rec_at(256 + (minus_y ? 32 : 0) + (ln & 15));   // left operand: the cell across; right: the patch's cell
+  const int  m_r = rec_at(minus_y ? patch_morton(ln & 15, 0) : patch_morton(0, ln & 15));
 
   typedef int int8v __attribute__((ext_vector_type(8)));
   struct Desc {
@@ -124,13 +162,13 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
   auto prefetch = [&](const Desc& d, int hslot, bool first, bool halo_wave) {
     Pre p;
 #pragma unroll
-    for (int k = 0; k < NV; k++) p.s0[k] = at32<T>(src.p[pl(k)], static_cast<unsigned>(d.e0 + tid));
+    for (int k = 0; k < NV; k++) p.s0[k] = at32<T>(plane(src, k), static_cast<unsigned>(d.e0 + tid));
     if (!PLANAR && halo_wave && first && P.ghost_buf) {   // (a planar launch has no ghost window: plain_patch_stage)
 #pragma unroll
       for (int k = 0; k < NV; k++) p.sh[k] = ghost_window_load<T>(P, src, hslot, pl(k));
     } else if (halo_wave) {
 #pragma unroll
-      for (int k = 0; k < NV; k++) p.sh[k] = at32<T>(src.p[pl(k)], static_cast<unsigned>(hslot));
+      for (int k = 0; k < NV; k++) p.sh[k] = at32<T>(plane(src, k), static_cast<unsigned>(hslot));
     } else {
 #pragma unroll
       for (int k = 0; k < NV; k++) p.sh[k] = T(0);
@@ -150,6 +188,7 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
   __builtin_amdgcn_s_waitcnt(0);   // (see k_plain_persistent: the prologue's loads must not become a wait inside the loop)
 
   for (; t < tend; t += stride, it++) {
+    if constexpr (SPLIT) asm volatile("" : "+s"(pstride));
     const bool halo_wave = role(it) == 3, minus_lane = role(it) == 0 && ln < 32;
     const Desc d2   = load_desc(t + 2 * stride);
     const int  hs_c = role(it + 2) == 3 ? P.halo_ids[d2.h0 + hl] : 0;
@@ -161,7 +200,7 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
     for (int k = 0; k < NV; k++) pv[k] = T(0);
     if (STAGE > 1) {
 #pragma unroll
-      for (int k = 0; k < NV; k++) pv[k] = stream_load<NT>(&at32<T>(prev.p[pl(k)], static_cast<unsigned>(e)));
+      for (int k = 0; k < NV; k++) pv[k] = stream_load<NT>(&at32<T>(plane(prev, k), static_cast<unsigned>(e)));
     }
     // (patches of uniform volume carry it in their descriptor: 8 of ~130 bytes per element and stage less to load)
     const T volume = (d0.flags & 0x400) ? static_cast<T>(d0.vol) : at32<T>(vol, static_cast<unsigned>(e));
@@ -177,7 +216,7 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
 #pragma unroll
       for (int k = 0; k < 5; k++) mine[k] = cur.s0[k];
     }
-    rec_store<T, NW>(pe + tid * REC, mine);
+    store_rec(rme, mine);
     if (halo_wave) {
       T w[NW];
       if constexpr (PLANAR) {
@@ -188,11 +227,11 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
 #pragma unroll
         for (int k = 0; k < 5; k++) w[k] = cur.sh[k];
       }
-      rec_store<T, NW>(pe + (256 + hl) * REC, w);
+      store_rec(rec_at(256 + hl), w);
     }
     if (res_e >= 0) {   // results of the previous patch: behind this iteration's first wait (vmcnt retires in order)
 #pragma unroll
-      for (int k = 0; k < NV; k++) stream_store<NT>(&at32<T>(out.p[pl(k)], static_cast<unsigned>(res_e)), res[k]);
+      for (int k = 0; k < NV; k++) stream_store<NT>(&at32<T>(plane(out, k), static_cast<unsigned>(res_e)), res[k]);
     }
     __syncthreads();
 
@@ -206,11 +245,11 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
     T gy[NV];
     {
       T wr[NW], g[NV], sx, sy;
-      rec_load<T, NW>(pe + rx * REC, wr);
+      load_rec(rx, wr);
       face(false, mine, wr, g, sx);
 #pragma unroll
       for (int k = 0; k < NV; k++) ff[k * kPatchFF + tid] = g[k];
-      rec_load<T, NW>(pe + ry * REC, wr);
+      load_rec(ry, wr);
       face(true, mine, wr, gy, sy);
 #pragma unroll
       for (int k = 0; k < NV; k++) ff[k * kPatchFF + 256 + tid] = gy[k];
@@ -230,8 +269,8 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
     }
     if (minus_lane) {
       T wl[NW], wr[NW], g[NV], sm;
-      rec_load<T, NW>(pe + m_l * REC, wl);
-      rec_load<T, NW>(pe + m_r * REC, wr);
+      load_rec(m_l, wl);
+      load_rec(m_r, wr);
       face(minus_y, wl, wr, g, sm);
 #pragma unroll
       for (int k = 0; k < NV; k++) ff[k * kPatchFF + 512 + ln] = g[k];
@@ -262,15 +301,21 @@ T8_DEV void plain_patch_body(const T8gpuPlainPlan& P, int tile_begin, int tile_c
   }
   if (res_e >= 0) {
 #pragma unroll
-    for (int k = 0; k < NV; k++) stream_store<NT>(&at32<T>(out.p[pl(k)], static_cast<unsigned>(res_e)), res[k]);
+    for (int k = 0; k < NV; k++) stream_store<NT>(&at32<T>(plane(out, k), static_cast<unsigned>(res_e)), res[k]);
     if constexpr (!PLANAR)
       if (P.send_map) ghost_window_send<T>(P, res_e, res);   // (one patch per workgroup there: this is its only store)
   }
 }
 
-// (second launch bound = waves per SIMD the register allocation must allow: 3 workgroups per CU in fp64, 5 in fp32)
+// (second launch bound = waves per SIMD the register allocation must allow: 3 workgroups per CU in fp64, 5 in fp32 -- and 4 in
+//  the planar fp64 form, whose body needs 113 / 123 / 123 VGPRs in stages 1 / 2 / 3 and whose LDS window is below a quarter CU's)
+template <class T, bool PLANAR>
+constexpr int patch_wgs_per_cu() {
+  return sizeof(T) == 8 ? (PLANAR ? 4 : 3) : 5;
+}
+
 template <class T, int KIND, int STAGE, bool NT, bool PLANAR = false>
-__global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_patch(T8gpuPlainPlan P, int tile_begin, int tile_count, int chunk, FVars<T> prev,
+__global__ __launch_bounds__(256, (patch_wgs_per_cu<T, PLANAR>())) void k_plain_patch(T8gpuPlainPlan P, int tile_begin, int tile_count, int chunk, FVars<T> prev,
                                                                                 FVars<T> src, FVars<T> out, const T* __restrict__ vol, T dt,
                                                                                 T* __restrict__ speed) {
   plain_patch_body<T, KIND, STAGE, NT, PLANAR>(P, tile_begin, tile_count, blockIdx.x, gridDim.x, chunk, prev, src, out, vol, dt, speed);
@@ -284,7 +329,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_patch(T8g
 // PLANAR: the patch workgroups run the planar body; the generic tiles keep the general form (they read the zeros of the
 // z-momentum plane and write +0, as the contract has it), so the kernel's register count is the larger of the two bodies'.
 template <class T, int KIND, int STAGE, bool NT, bool OPEN = false, bool PLANAR = false>
-__global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_stage(T8gpuPlainPlan P, int patch_begin, int patch_count, int patch_wgs, int chunk,
+__global__ __launch_bounds__(256, (patch_wgs_per_cu<T, PLANAR>())) void k_plain_stage(T8gpuPlainPlan P, int patch_begin, int patch_count, int patch_wgs, int chunk,
                                                                                 int tile_begin, int tile_count, FVars<T> prev, FVars<T> src,
                                                                                 FVars<T> out, const T* __restrict__ vol, T dt,
                                                                                 T* __restrict__ speed) {
@@ -295,6 +340,24 @@ __global__ __launch_bounds__(256, sizeof(T) == 8 ? 3 : 5) void k_plain_stage(T8g
     const int pos = tile_begin + xcd_position(b - patch_wgs, tile_count);
     plain_tile_body<T, KIND, STAGE, true, 2, false, OPEN>(P, pos, prev, src, out, vol, dt, speed);
   }
+}
+
+// are the five planes of v spaced like the first two of `ref`?
+template <class T>
+bool planes_equally_spaced(const FVars<T>& v, const FVars<T>& ref) {
+  const ptrdiff_t d = reinterpret_cast<const char*>(ref.p[1]) - reinterpret_cast<const char*>(ref.p[0]);
+  for (int k = 0; k < 4; k++)
+    if (reinterpret_cast<const char*>(v.p[k + 1]) - reinterpret_cast<const char*>(v.p[k]) != d) return false;
+  return true;
+}
+
+// LDS window of a generic tile in the mixed launch: what plain_tile_body<T, K, S, true, 2> takes (kernels_fused.hip: the pipelined
+// kernel with a geometry dictionary, two passes of 256 faces). fp64 KEPES: 8 x (9 x slots + 1 280) + 2 064 bytes.
+template <class T>
+size_t mixed_tile_lds(int kind, const T8gpuPlainPlan* plan) {
+  const int    nw  = kind == 0 ? kPrimWords : 5;
+  const size_t tab = lds_log_table<T>(kind);
+  return sizeof(T) * (static_cast<size_t>(nw) * plan_slots(*plan) + static_cast<size_t>(5) * 256) + (tab ? tab + 16 : 0);
 }
 
 // Patch tiles [patch_begin, patch_begin + patch_count) of tile_order, and -- in the same launch -- the generic tiles
@@ -311,23 +374,29 @@ int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch
   if (!plan->tile_desc) return static_cast<int>(hipErrorInvalidValue);
   if (!plan_planes_fit_32bit<T>(plan)) return static_cast<int>(hipErrorInvalidValue);
   if (plan->ghost_buf || plan->send_map || !persistent || kind != 0) planar = false;   // (the general form, silently)
-  size_t lds = record_lds<T>(kind, static_cast<size_t>(planar ? 4 : 5) * kPatchFF, 320);
+  // (the planar fp64 body addresses plane k as p[0] + k x spacing: planes not so spaced run the general form as well)
+  if (planar && sizeof(T) == 8 && !(planes_equally_spaced(mid, mid) && planes_equally_spaced(out, mid) && (stage == 1 || planes_equally_spaced(prev, mid))))
+    planar = false;
+  size_t lds = patch_lds<T>(kind, planar);
+  // the planar fp64 kernels are built for four workgroups per CU; a launch has four where its LDS window allows them
+  const bool planar64 = planar && sizeof(T) == 8;
   // (far-field faces: the generic tiles run k_plain_fused_p_far in a launch of their own -- under the mixed kernel's register
   //  budget of 3 / 5 workgroups per CU their far-field state spills)
   if (tile_count > 0 && plan->has_farfield_faces) return -1;
   if (tile_count > 0) {
-    // what plain_tile_body<T, K, S, true, 2> takes (kernels_fused.hip: the pipelined kernel with a geometry dictionary, two
-    // passes of 256 faces), and its LDS window
+    // what plain_tile_body<T, K, S, true, 2> takes, and its LDS window
     if (!plain_tiles_pipelined(plan) || plan->max_faces > 512 || !plan->geo_idx || !plan->geo_table || plan->n_geo <= 0) return -1;
-    const int    nw       = kind == 0 ? kPrimWords : 5;
-    const size_t tab      = lds_log_table<T>(kind);
-    const size_t lds_tile = sizeof(T) * (static_cast<size_t>(nw) * plan_slots(*plan) + static_cast<size_t>(5) * 256) + (tab ? tab + 16 : 0);
+    const size_t lds_tile = mixed_tile_lds<T>(kind, plan);
     if (lds_tile > lds) lds = lds_tile;
     if (sizeof(T) == 8 && 3 * lds > static_cast<size_t>(156) * 1024) return -1;   // (the kernel lives on three workgroups per CU)
   }
+  // (else three, under the guard above: generic tiles of more than 398 slots; T8GPU_PATCH_WGS=3: three, for A/B runs)
+  static const int per_cu_env = env_per_cu("T8GPU_PATCH_WGS");
+  const bool       four       = planar64 && lds <= kLdsQuarterCU && per_cu_env != 3;
   const int cus = device_cu_count();
   if (cus == 0) return static_cast<int>(hipErrorInvalidDevice);
-  // persistent = true: the launch covers the whole plan -- as many patch workgroups as stay resident (3 per CU in fp64).
+  // persistent = true: the launch covers the whole plan -- as many patch workgroups as stay resident (3 per CU in fp64, 4 in
+  // the planar form).
   // persistent = false: a class of a multi-rank stage, launched beside the pack / RCCL / unpack kernels of the exchange: one
   // patch per workgroup, so that slots free up continuously. That costs the patch kernel its software pipeline (13 % at c2
   // size, 19 % at c4 size, measured on one rank), but a "polite" persistent grid of two workgroups per CU for the class
@@ -336,7 +405,7 @@ int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch
   // workgroups that never leave.
   // a ghost window (t8gpu_hip.h) is honoured by a workgroup's FIRST patch only (plain_patch_body): one patch per workgroup
   if (plan->ghost_buf || plan->send_map) persistent = false;
-  const int  per_cu    = sizeof(T) == 8 ? 3 : 5;
+  const int  per_cu    = sizeof(T) == 8 ? (four ? 4 : 3) : 5;
   const int  resident  = cus * per_cu;
   // A persistent launch that shares the GPU with the other lane's kernels (the interior launch of a multi-rank stage: the plan
   // has ghost-reading tiles and the range is not the whole plan) must not count on all its workgroups being resident from
@@ -373,9 +442,22 @@ int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch
       kind, stage, nt, tile_count > 0, tile_count > 0 && plan->has_open_faces, planar);
 }
 
+// (t8gpu_hip_plain_patch_lds_bytes: the windows above, for the host)
+size_t plain_patch_window(int kind, int float_size, bool planar, const T8gpuPlainPlan* tiles) {
+  if (kind != 0) planar = false;
+  const size_t lds  = float_size == 8 ? patch_lds<double>(kind, planar) : patch_lds<float>(kind, planar);
+  const size_t tile = !tiles ? 0 : float_size == 8 ? mixed_tile_lds<double>(kind, tiles) : mixed_tile_lds<float>(kind, tiles);
+  return tile > lds ? tile : lds;
+}
+
 template int plain_patch_stage<float>(int, int, const T8gpuPlainPlan*, int, int, int, int, FVars<float>, FVars<float>, FVars<float>,
                                       const float*, float, float*, bool, bool, hipStream_t);
 template int plain_patch_stage<double>(int, int, const T8gpuPlainPlan*, int, int, int, int, FVars<double>, FVars<double>, FVars<double>,
                                        const double*, double, double*, bool, bool, hipStream_t);
 
 }  // namespace t8gpu_hip
+
+extern "C" int t8gpu_hip_plain_patch_lds_bytes(const T8gpuPlainPlan* plan, int flux_kind, int float_size, int planar) {
+  if (flux_kind < 0 || flux_kind > 2 || (float_size != 4 && float_size != 8)) return -1;
+  return static_cast<int>(t8gpu_hip::plain_patch_window(flux_kind, float_size, planar != 0, plan));
+}

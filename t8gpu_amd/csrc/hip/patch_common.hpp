@@ -29,6 +29,17 @@ bool plan_planes_fit_32bit(const T8gpuPlainPlan* plan) {
 
 constexpr int kPatchFF = 544;   // flux slots per variable: 256 +x faces, 256 +y faces, 16 -x side, 16 -y side
 
+// dynamic LDS of the 2D patch body: flux slots of the variables carried, 320 records, the logarithm table. Planar fp64 KEPES
+// (64-byte records in chunk planes: fused_common.hpp): 8 x 4 x 544 + 64 x 320 + 2 048 = 39 936 bytes.
+template <class T>
+size_t patch_lds(int kind, bool planar) {
+  if (planar && kind == 0 && sizeof(T) == 8)
+    return sizeof(T) * 4 * kPatchFF + sizeof(T) * kPrimWordsPlanar * 320 + lds_log_table<T>(kind);
+  return record_lds<T>(kind, static_cast<size_t>(planar ? 4 : 5) * kPatchFF, 320);
+}
+// what a workgroup may take where four are to be resident in a CU's 160 KiB of LDS
+constexpr size_t kLdsQuarterCU = 160 * 1024 / 4;
+
 T8_DEV int patch_morton(int i, int j) {
   int t = 0;
 #pragma unroll
