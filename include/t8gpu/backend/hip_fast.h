@@ -215,7 +215,8 @@ namespace t8gpu::hip {
                      typename variable_traits<VariableType>::float_type* speed, int flux_kind = T8GPU_FLUX_KEPES,
                      hipStream_t stream = nullptr, int n_steps = 1) {
     using ft = typename variable_traits<VariableType>::float_type;
-    // n_steps > 1: prev / next are the roles of the FIRST step and alternate (after an odd count the caller swaps once more)
+    // n_steps > 1: prev / next are the roles of the FIRST step and alternate (after an odd count the caller swaps once more);
+    // `speed` holds the estimates of the LAST step on return, those of the steps before are not materialised (t8gpu_hip.h)
     T8GPU_DISPATCH(ft, t8gpu_hip_plain_stepper_iterate_steps, plan.stepper(), flux_kind, mesh.planes_base(), mesh.plane_stride(),
                    static_cast<int>(prev), static_cast<int>(next), delta_t, speed, n_steps, stream);
   }

@@ -373,7 +373,12 @@ int t8gpu_hip_halo_exchange_f64(const T8gpuHalo* halo, T8gpuVars_f64 state, void
  * them between steps calls t8gpu_hip_halo_exchange_* (T8GPU_GHOST_WINDOW=0: pack / unpack kernels, slots refreshed).
  * iterate_steps: n_steps consecutive steps in one call, prev / next given for the FIRST step and swapped
  * from step to step (after an odd n_steps the caller's roles are swapped once more); the two streams then
- * meet only at the entry and the exit of the call instead of once per step. */
+ * meet only at the entry and the exit of the call instead of once per step.
+ * speed_estimates (ABI 15): when the call's work is done the array holds the estimates of the call's LAST step, one value
+ * for every face, exactly what n_steps calls of one step leave there (what compute_timestep reads: "computed at the last
+ * step of the last timestepping", solver.h:88-91). The estimates of the steps before are NOT materialised: nothing can
+ * read them before the next step overwrites them, so only the third stage of the last step is handed the array
+ * (t8gpu_hip_stepper_set_speed_every_step below). A caller that wants them per step calls with n_steps = 1. */
 int t8gpu_hip_plain_stepper_create(const T8gpuPlainPlan* plan, const T8gpuHalo* halo_or_null, void** stepper);
 int t8gpu_hip_plain_stepper_destroy(void* stepper);
 int t8gpu_hip_plain_stepper_iterate_f32(void* stepper, int flux_kind, float* planes, size_t stride, int prev, int next,
@@ -409,6 +414,14 @@ int t8gpu_hip_plain_stepper_timing(void* stepper, int enable);
  * t8gpu_hip_last_stage_kernel (the launcher runs the general kernel for launches that are not whole-plan persistent ones). */
 int t8gpu_hip_stepper_set_planar(void* stepper, int mode);
 int t8gpu_hip_stepper_planar(void* stepper);
+/* Which stages of an iterate_steps call write the speed estimates (ABI 15): on = 0, the third stage of the call's last step
+ * only (the default); on = 1, the third stage of every step (the behaviour before ABI 15; for A/B measurements). The array
+ * holds the same bits on return either way. A new stepper starts with on = 1 if T8GPU_SPEED_EVERY_STEP is set to anything
+ * but "" or "0..." in the environment. The mode is part of the argument set of a captured graph.
+ * _speed_stages: how many RK stages of the last call were handed a non-NULL speed_estimates (a stage counts once, however
+ * many lanes or tile classes it is launched in; 0 for Subgrid steppers, which have no such array). */
+int t8gpu_hip_stepper_set_speed_every_step(void* stepper, int on);
+int t8gpu_hip_stepper_speed_stages(void* stepper);
 /* Diagnostics (scripts/halo_overhead.py): with T8GPU_STEPPER_PROFILE=1 in the environment the step drivers time their own
  * host calls; ns4 / calls4 (may be NULL) receive nanoseconds and counts for {kernel launches, RCCL groups, event records,
  * stream waits} since the last reset. Returns 1 when the profile is on, 0 when off (all zeros). */

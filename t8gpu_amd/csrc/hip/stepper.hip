@@ -63,6 +63,11 @@ struct HostTimer {   // cat: 0 kernel launch, 1 RCCL group, 2 event record, 3 st
   }
 };
 
+inline bool env_on(const char* name) {   // set, not empty and not "0..."
+  const char* v = std::getenv(name);
+  return v && v[0] != '\0' && v[0] != '0';
+}
+
 struct Stepper {
   T8gpuPlainPlan   plan{};      // plain elements: units = tiles of the plan
   T8gpuSubgridPlan splan{};     // Subgrid blocks: units = blocks in block_order position order
@@ -83,6 +88,7 @@ struct Stepper {
     hipGraphExec_t exec = nullptr;  // prev / next swap with every odd n_steps), so the cache holds a few
     unsigned char  key[96] = {0};
     unsigned long  used = 0;
+    int            speed_stages = 0;   // stages of the captured sequence that write the speed estimates
   };
   GraphEntry      graph_cache[4];
   unsigned long   graph_clock = 0;
@@ -93,6 +99,11 @@ struct Stepper {
   int             planar_last = 0;      // what the last call did
   uint32_t*       d_bits = nullptr;     // device: OR of the bits of the four z-momentum planes
   uint32_t*       h_bits = nullptr;     // pinned host copy
+  // the per-face speed estimates (t8gpu_hip.h: t8gpu_hip_stepper_set_speed_every_step; stage_args below)
+  // 0 the third stage of a call's last step writes them, 1 the third stage of every step; T8GPU_SPEED_EVERY_STEP in the
+  // environment sets the mode a new stepper starts in
+  int             speed_every_step = env_on("T8GPU_SPEED_EVERY_STEP") ? 1 : 0;
+  int             speed_stages = 0;     // stages of the last call that were handed the array
 
   // ---- lanes: the two-lane driver (iterate_lanes); a single rank launches on the deep lane ---------------------------------
   static constexpr int kRing = 4;
@@ -194,7 +205,7 @@ struct StageArgs {
   T*  stage_speed;
 };
 template <class T, class V>
-StageArgs<T, V> stage_args(T* planes, size_t stride, int prev, int next, T* speed, int g) {
+StageArgs<T, V> stage_args(T* planes, size_t stride, int prev, int next, T* speed, int g, int n_steps, bool every_step) {
   StageArgs<T, V> a;
   a.k          = g % 3;
   const int pr = (g / 3) % 2 == 0 ? prev : next, nx = (g / 3) % 2 == 0 ? next : prev;
@@ -202,10 +213,12 @@ StageArgs<T, V> stage_args(T* planes, size_t stride, int prev, int next, T* spee
   a.pv = step_vars<V>(planes, stride, pr);
   a.sv = step_vars<V>(planes, stride, src);
   a.ov = step_vars<V>(planes, stride, dst);
-  // The per-face speed estimates are rewritten by every stage and read only between steps (compute_timestep uses
-  // those "computed at the last step of the last timestepping", solver.h:88-91): only the third stage writes them
-  // (same contents after every step, a tenth less HBM traffic per step).
-  a.stage_speed = a.k == 2 ? speed : nullptr;
+  // The per-face speed estimates are rewritten by every stage and read only between CALLS (compute_timestep uses
+  // those "computed at the last step of the last timestepping", solver.h:88-91): only the third stage of the call's
+  // last step writes them. Every third stage would store the whole array (one value per face) and the next step
+  // overwrite it before anyone can look: same contents on return, F + B stores less per intermediate step.
+  // every_step (t8gpu_hip_stepper_set_speed_every_step): the third stage of every step, for A/B runs.
+  a.stage_speed = a.k == 2 && (every_step || g == 3 * n_steps - 1) ? speed : nullptr;
   return a;
 }
 
@@ -329,6 +342,8 @@ int iterate_lanes(Stepper* S, int kind, T* planes, size_t stride, const T* vol, 
   S->lane_abort.store(false, std::memory_order_relaxed);
   const int timing = S->timing;
   if (timing > 0) S->stages_timed += 3 * ((n_steps + timing - 1) / timing);
+  const bool every_step = S->speed_every_step != 0;
+  S->speed_stages = 0;
 
   // entry: the lanes see everything the caller queued on s
   T8_HIP_TRY(hipEventRecord(S->ev_state, s));
@@ -342,7 +357,7 @@ int iterate_lanes(Stepper* S, int kind, T* planes, size_t stride, const T* vol, 
   // ---- comm lane, stage g: RCCL_g -> A_g -> [C_(g-1)] -> B_g --------------------------------------------------------------
   auto comm_stage = [=, &DL, &XL](int g) -> int {
     const T8gpuHalo&      h      = S->halo;
-    const StageArgs<T, V> a      = stage_args<T, V>(planes, stride, prev, next, speed, g);
+    const StageArgs<T, V> a      = stage_args<T, V>(planes, stride, prev, next, speed, g, n_steps, every_step);
     const bool            sample = timing > 0 && (g / 3) % timing == 0;
     if (!S->zero_copy || g == 0)   // (ghost window: the A tiles of stage g-1 have filled the send buffer)
       T8_TRY((halo_pack<T, V>(h, a.sv, XL.stream)));
@@ -370,8 +385,9 @@ int iterate_lanes(Stepper* S, int kind, T* planes, size_t stride, const T* vol, 
   };
   // ---- deep lane, stage g: [B_(g-1)] -> C_g --------------------------------------------------------------------------------
   auto deep_stage = [=, &DL, &XL](int g) -> int {
-    const StageArgs<T, V> a      = stage_args<T, V>(planes, stride, prev, next, speed, g);
+    const StageArgs<T, V> a      = stage_args<T, V>(planes, stride, prev, next, speed, g, n_steps, every_step);
     const bool            sample = timing > 0 && (g / 3) % timing == 0;
+    if (a.stage_speed) S->speed_stages++;   // (counted on this lane only: the comm lane runs the same stage's other tiles)
     if (nd > 0) {
       if (g > 0) {
         if (!lane_wait_recorded(S, XL, g - 1)) return 0;
@@ -447,11 +463,14 @@ int iterate(Stepper* S, int kind, T* planes, size_t stride, const T* vol, int pr
   static const char* const stage_name[3] = {"t8gpu.rk_stage1", "t8gpu.rk_stage2", "t8gpu.rk_stage3"};
   Stepper::Lane& L = S->deep_lane;
   L.stream = s;
+  const bool every_step = S->speed_every_step != 0;
+  S->speed_stages = 0;
   for (int g = 0; g < 3 * n_steps; g++) {
-    const StageArgs<T, V> a = stage_args<T, V>(planes, stride, prev, next, speed, g);
+    const StageArgs<T, V> a = stage_args<T, V>(planes, stride, prev, next, speed, g, n_steps, every_step);
     t8gpu_hip::Range stage_range(stage_name[a.k]);
     const bool sample = S->timing > 0 && (g / 3) % S->timing == 0;
     if (sample) S->stages_timed++;
+    if (a.stage_speed) S->speed_stages++;
     T8_TRY((launch_stage<T, V>(S, L, kind, &S->plan, a, 0, nt, vol, dt, sample)));
   }
   return 0;
@@ -524,15 +543,17 @@ int planar_decide(Stepper* S, int kind, T* planes, size_t stride, int prev, int 
 template <class T, class V>
 int iterate_graph(Stepper* S, int kind, T* planes, size_t stride, const T* vol, int prev, int next, T dt, T* speed, int n_steps,
                   hipStream_t s) {
+  S->speed_stages = 0;
   if (!S->graph_mode || S->timing > 0 || n_steps <= 0 || S->has_halo)
     return iterate<T, V>(S, kind, planes, stride, vol, prev, next, dt, speed, n_steps, s);
   struct Key {
-    int kind, prev, next, n_steps, tsize, subgrid, planar, pad;   // (planar: the call's decision picks other kernels)
+    int kind, prev, next, n_steps, tsize, subgrid, planar, every_step;   // (planar: the call's decision picks other kernels;
+                                                                         //  every_step: which stages write the speed estimates)
     const void *planes, *vol, *speed;
     size_t stride;
     double dt;
-  } key{kind, prev, next, n_steps, static_cast<int>(sizeof(T)), S->subgrid ? 1 : 0, S->planar_now ? 1 : 0, 0, planes, vol, speed, stride,
-        static_cast<double>(dt)};
+  } key{kind, prev, next, n_steps, static_cast<int>(sizeof(T)), S->subgrid ? 1 : 0, S->planar_now ? 1 : 0,
+        S->speed_every_step ? 1 : 0, planes, vol, speed, stride, static_cast<double>(dt)};
   static_assert(sizeof(Key) <= sizeof(S->graph_cache[0].key), "graph key");
   if (!S->graph_stream) {
     T8_HIP_TRY(hipStreamCreateWithFlags(&S->graph_stream, hipStreamNonBlocking));
@@ -568,10 +589,12 @@ int iterate_graph(Stepper* S, int kind, T* planes, size_t stride, const T* vol, 
     }
     std::memset(lru->key, 0, sizeof(lru->key));
     std::memcpy(lru->key, &key, sizeof(Key));
+    lru->speed_stages = S->speed_stages;
     S->graph_captures++;
     hit = lru;
   }
   hit->used = ++S->graph_clock;
+  S->speed_stages = hit->speed_stages;   // (a replay runs what was captured)
   T8_HIP_TRY(hipEventRecord(S->ev_graph_in, s));                         // the graph starts behind the caller's work ...
   T8_HIP_TRY(hipStreamWaitEvent(S->graph_stream, S->ev_graph_in, 0));
   T8_HIP_TRY(hipGraphLaunch(hit->exec, S->graph_stream));
@@ -980,6 +1003,17 @@ int t8gpu_hip_stepper_set_planar(void* h, int mode) {
 int t8gpu_hip_stepper_planar(void* h) {
   Stepper* S = static_cast<Stepper*>(h);
   return S ? S->planar_last : 0;
+}
+
+int t8gpu_hip_stepper_set_speed_every_step(void* h, int on) {
+  Stepper* S = static_cast<Stepper*>(h);
+  if (!S || on < 0 || on > 1) return static_cast<int>(hipErrorInvalidValue);
+  S->speed_every_step = on;
+  return 0;
+}
+int t8gpu_hip_stepper_speed_stages(void* h) {
+  Stepper* S = static_cast<Stepper*>(h);
+  return S ? S->speed_stages : 0;
 }
 
 int t8gpu_hip_plain_stepper_timing(void* h, int enable) {

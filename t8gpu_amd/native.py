@@ -137,6 +137,15 @@ class NativeStepper:
         """1 if the last iterate / iterate_steps call ran the planar form, else 0."""
         return int(hip.lib().t8gpu_hip_stepper_planar(self.handle))
 
+    def set_speed_every_step(self, on):
+        """Which stages of an iterate_steps() call write the speed estimates (t8gpu_hip_stepper_set_speed_every_step): False,
+        the third stage of the call's last step only (default); True, the third stage of every step. Same array on return."""
+        hip.check(hip.lib().t8gpu_hip_stepper_set_speed_every_step(self.handle, int(bool(on))))
+
+    def speed_stages(self):
+        """How many RK stages of the last iterate / iterate_steps call were handed the speed array."""
+        return int(hip.lib().t8gpu_hip_stepper_speed_stages(self.handle))
+
     def timing(self, enable):
         hip.check(hip.lib().t8gpu_hip_plain_stepper_timing(self.handle, int(enable)))
 

@@ -237,7 +237,8 @@ class _Solver:
 
     def iterate_steps(self, n_steps, delta_t, stream=None, halo=None):
         """n_steps steps with a fixed delta_t. With the native stepper this is ONE call: the exchange stream and
-        the compute stream then meet only at its entry and exit (see csrc/hip/stepper.hip)."""
+        the compute stream then meet only at its entry and exit (see csrc/hip/stepper.hip). `speed` then holds the
+        estimates of the call's last step, as after n_steps single steps; those of the steps before are not written."""
         if n_steps <= 0:
             return
         if self.stepper is None:
