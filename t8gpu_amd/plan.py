@@ -46,7 +46,7 @@ class HostPlainPlan:
 
     def __init__(self, N, G, F, B, ndim, face_neighbors, normals, areas, tmax=256, fcap=512, want_face_geo=True,
                  patches=False, volumes=None, irregular=True, two_classes=False, boundary_kinds=None):
-        """patches=True: structured 16 x 16 patches are cut out of the tiling (tile_plan.cpp: find_patches); they are
+        """patches=True: structured 16 x 16 patches are cut out of the tiling (tile_patches.hpp: find_patches); they are
         tiles without face records (`tile_patch[t]` = 1), first inside every class of `tile_order` (`n_patch_class`).
         want_face_geo=False: leave `face_geo` (32 bytes per tile face, only read by the kernels that have no geometry
         dictionary) empty when the plan has a dictionary -- at c4 size that is 700 MB of host copying per plan.
