@@ -63,7 +63,7 @@ def main():
     ap.add_argument("--cfl", type=float, default=0.35)
     ap.add_argument("--sides", choices=list(SIDES), default="farfield", help="the kind of all four sides")
     ap.add_argument("--flux", choices=list(FLUXES), default="kepes")
-    ap.add_argument("--out", default=None, help="directory of the .vtu written at the end (density, energy, momentum)")
+    ap.add_argument("--out", default=None, help="directory of the .vtu written at the end (density, energy, momentum, pressure, dilatation)")
     ap.add_argument("--toy", action="store_true", help="levels 3-5, t_end 0.05 (a quick check)")
     args = ap.parse_args()
     if args.toy:
@@ -110,6 +110,8 @@ def main():
         fields = [vtk.get_host_scalar_variable(solver, solver.next, 0, "density"),
                   vtk.get_host_scalar_variable(solver, solver.next, 4, "energy"),
                   vtk.get_host_vector_variable(solver, solver.next, (1, 2, 3), "momentum")]
+        # derived fields, formed on the device (fields.py; the gradient fields take no term from boundary faces)
+        fields += [vtk.get_host_derived_variable(solver, name) for name in ("pressure", "dilatation")]
         print("wrote", vtk.save_variables_to_vtk(solver, fields, os.path.join(args.out, "acoustic_pulse")))
 
 

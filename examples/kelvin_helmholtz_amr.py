@@ -33,7 +33,7 @@ def main():
     ap.add_argument("--max-level", type=int, default=9)
     ap.add_argument("--threshold", type=float, default=10.0)     # mesh_manager.inl:141
     ap.add_argument("--dtype", default="f64", choices=["f32", "f64"])
-    ap.add_argument("--vtk", default=None, help="prefix of the .vtu / .pvtu files written at the end (density, energy, momentum)")
+    ap.add_argument("--vtk", default=None, help="prefix of the .vtu / .pvtu files written at the end (density, energy, momentum, pressure, mach, vorticity)")
     args = ap.parse_args()
     dtype = torch.float64 if args.dtype == "f64" else torch.float32
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -114,6 +114,8 @@ def main():
         fields = [vtk.get_host_scalar_variable(solver, solver.next, 0, "density"),
                   vtk.get_host_scalar_variable(solver, solver.next, 4, "energy"),
                   vtk.get_host_vector_variable(solver, solver.next, (1, 2, 3), "momentum")]
+        # derived fields, formed on the device (fields.py; the gradient fields take no term from boundary faces)
+        fields += [vtk.get_host_derived_variable(solver, name, halo=halo) for name in ("pressure", "mach", "vorticity")]
         say("wrote", vtk.save_variables_to_vtk(solver, fields, args.vtk, dist=dist))
     say(f"iterate: {total(cells) / total(t_iter, 'max') / 1e6:.1f} M cell-updates/s (host-synchronised per step), "
         f"adapt: {t_adapt:.2f} s total, iterate: {t_iter:.2f} s total")

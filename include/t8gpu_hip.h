@@ -553,7 +553,52 @@ int t8gpu_hip_state_monitor_f32(size_t num_cells, int cells_per_element, int dim
 int t8gpu_hip_state_monitor_f64(size_t num_cells, int cells_per_element, int dim, T8gpuVars_f64 state, const double* volume,
                                 void* workspace, double* result /* [16] */, void* stream);
 
-/* ---- AMR indicator and data transfer for plain elements ---------------------------------
+/* ---- derived output fields: pressure, velocity, Mach, entropy, vorticity, dilatation, schlieren ---------
+ * What a run writes to look at itself, formed on the device from the five planes of one step (csrc/hip/fields.hip; the
+ * reference writes conserved variables only). All arithmetic in double whatever float_type is, gamma = 1.4,
+ * u = (m_x, m_y, m_z) / rho. Output planes (doubles, one value per owned cell in storage order; a vector is three planes):
+ *    0      pressure    0.4 (E - |m|^2 / (2 rho))
+ *    1-3    velocity    m / rho
+ *    4      mach        |u| / sqrt(1.4 p / rho)
+ *    5      entropy     log p - 1.4 log rho                    (the per-cell integrand of monitor slot 6 without rho vol)
+ *    6-8    vorticity   (1 / 2 V_c) sum_s A_s n_s x (u_o - u_c)
+ *    9      dilatation  (1 / 2 V_c) sum_s A_s n_s . (u_o - u_c)
+ *    10     schlieren   | (1 / 2 V_c) sum_s A_s n_s (rho_o - rho_c) |
+ * The sums run over the INTERIOR faces (sub-faces) s of cell c: n_s the unit normal outward from c, A_s the area, o the cell
+ * across s -- the jump form of the Green-Gauss gradient, the central difference on uniform Cartesian cells, exactly +-0 for
+ * a uniform state. Boundary faces of every kind contribute no term (a zero-jump closure); at a 2:1 face the arithmetic face
+ * mean is first-order consistent only. Non-physical cells get their IEEE results. A 2-component normal
+ * has z = 0.
+ * A NULL plane is not computed and nothing is stored for it. When planes 6-10 are all NULL the connectivity pointers
+ * (volume, face arrays, CSR) may be NULL and no neighbour is read. csr_offsets[n + 1] / csr_entries: the element -> faces
+ * lists of t8gpu_host_cell_faces (t8gpu_host.h), device copies. The neighbour's slot may be a ghost slot: its state must be
+ * current. Gathers without atomics: a cell sums its terms in CSR order (inside a hanging Subgrid face j-major, i-minor; the
+ * in-block faces of a subcell first, -x +x -y +y -z +z), so two calls give the same bits. One launch on `stream`.
+ * Plain elements: one lane per owned element; V_c = volume[c]; face f has normals[normal_dim f ..] outward from
+ * l = face_neighbors[2 f] and face_surfaces[f], as t8gpu_hip_flux_faces_* reads them.
+ * Subgrid blocks: one wavefront per Subgrid<4,4,4> block, four Subgrid<4,4> blocks per wavefront; V_c = volumes[e] / S;
+ * in-block faces have area h^(rank-1), h = volumes[e]^(1/rank) / 4; an outer sub-face has face_surfaces[f] / SF and the
+ * cell pair of t8gpu_hip_subgrid_outer_* (a hanging face is listed by the finer block).
+ * Returns 0 for n <= 0; hipErrorInvalidValue, before any launch, for normal_dim / rank outside {2, 3} or a requested
+ * gradient plane with a NULL connectivity pointer. */
+typedef struct T8gpuFieldPlanes { double* p[11]; } T8gpuFieldPlanes;
+#define T8GPU_FIELD_PLANES 11
+int t8gpu_hip_plain_fields_f32(int num_elements, int normal_dim, T8gpuVars_f32 state, const float* volume,
+                               const int32_t* face_neighbors, const float* face_normals, const float* face_surfaces,
+                               const int32_t* csr_offsets, const int32_t* csr_entries, T8gpuFieldPlanes out, void* stream);
+int t8gpu_hip_plain_fields_f64(int num_elements, int normal_dim, T8gpuVars_f64 state, const double* volume,
+                               const int32_t* face_neighbors, const double* face_normals, const double* face_surfaces,
+                               const int32_t* csr_offsets, const int32_t* csr_entries, T8gpuFieldPlanes out, void* stream);
+int t8gpu_hip_subgrid_fields_f32(int rank, int num_blocks, T8gpuVars_f32 state, const float* volumes,
+                                 const int32_t* face_neighbors, const int32_t* face_level_difference,
+                                 const int32_t* face_neighbor_offset, const float* face_normals, const float* face_surfaces,
+                                 const int32_t* csr_offsets, const int32_t* csr_entries, T8gpuFieldPlanes out, void* stream);
+int t8gpu_hip_subgrid_fields_f64(int rank, int num_blocks, T8gpuVars_f64 state, const double* volumes,
+                                 const int32_t* face_neighbors, const int32_t* face_level_difference,
+                                 const int32_t* face_neighbor_offset, const double* face_normals, const double* face_surfaces,
+                                 const int32_t* csr_offsets, const int32_t* csr_entries, T8gpuFieldPlanes out, void* stream);
+
+/* ---- AMR indicator and data transfer for plain elements---------------------------------
  * estimate_gradient<<<>>>: examples/compressible_euler/kernels.cu:471-501 (|rho_r - rho_l| added to both
  * neighbours; the reference accumulates into its Fluxes/Rho plane, any zeroed plane works). */
 int t8gpu_hip_estimate_gradient_f32(int num_faces, const int32_t* face_neighbors, const int32_t* indices,

@@ -234,6 +234,16 @@ int t8gpu_host_write_vtu(const char* path, int dim, int64_t num_elements, const 
 int t8gpu_host_write_pvtu(const char* path, int num_pieces, const char* const* piece_files, int num_fields,
                           const char* const* names, const int32_t* components);
 
+/* ---- element -> interior faces (csrc/host/cell_faces.cpp) ------------------------------------------
+ * The CSR lists the gather kernels of the derived output fields walk (t8gpu_hip.h: t8gpu_hip_plain_fields_*,
+ * t8gpu_hip_subgrid_fields_*): a counting sort of face_neighbors[2 * num_faces] (the interior faces). Row e of
+ * offsets[n_owned + 1] / entries holds, for every interior face f with element e on one side, 2 f + side (side 0: e is l of
+ * face f), ascending in f. Only elements < n_owned get rows: a ghost side adds no entry, so entries holds at most
+ * 2 * num_faces values (its capacity). For Subgrid partitions the elements are the blocks. Returns the number of entries, or a
+ * negative value for a null pointer, a negative index or count, or num_faces >= 2^30. */
+int64_t t8gpu_host_cell_faces(int32_t n_owned, int64_t num_faces, const int32_t* face_neighbors, int32_t* offsets /* n_owned + 1 */,
+                              int32_t* entries /* capacity 2 * num_faces */);
+
 /* ---- host utilities ------------------------------------------------------------------------------ */
 /* memcpy over the planners' OpenMP threads (staging of large uploads into an application-owned pinned buffer) */
 void t8gpu_host_parallel_copy(void* dst, const void* src, size_t bytes);

@@ -311,6 +311,14 @@ class _Solver:
                 block[list(slots)] = t.cpu().numpy()[list(slots)]
         return Monitor(block)
 
+    def derived_fields(self, names, step=None, stream=None, halo=None):
+        """{name: float64 device tensor} of the derived output fields `names` -- "pressure", "velocity", "mach", "entropy",
+        "vorticity", "dilatation", "schlieren" (fields.py) -- for the owned cells of state(step) in storage
+        order, [cells] or [3, cells]. One pass of t8gpu_hip_*_fields_* enqueued on `stream`, no sync. `halo` refreshes the
+        ghost slots of that step first (the gradient fields read them); without it the caller vouches that they are current."""
+        from . import fields
+        return fields.derived_fields(self, names, step, stream, halo)
+
     def cfl_timestep(self, cfl=0.7, step=None, dist=None):
         """cfl / max over the cells of (|v| + c) / h, h = vol^(1/dim), from the state itself: needs no stage to have run (a new
         solver, a solver fresh from an adapt). On Cartesian cells h is the edge; on curved cells it is cbrt(volume), not an

@@ -72,6 +72,22 @@ def column_major_to_z_order(solver, values):
     return out
 
 
+def get_host_derived_variable(solver, name, step=None, halo=None):
+    """One derived output field (solver.derived_fields: "pressure", "vorticity", ...) as doubles on the host, ready for
+    save_variables_to_vtk: a scalar as it is, a vector interleaved xyz; for a Subgrid solver every plane in z-order first."""
+    t = solver.derived_fields([name], step, halo=halo)[name]
+    planes = [t] if t.dim() == 1 else [t[k] for k in range(3)]
+    if hasattr(solver, "S"):
+        planes = [column_major_to_z_order(solver, p.contiguous()) for p in planes]
+    n = _own_cells(solver)
+    if len(planes) == 1:
+        return HostVariableInfo(SCALAR, planes[0].cpu().numpy(), name)
+    out = torch.empty(3 * n, dtype=torch.float64, device="cuda")
+    hip.call("t8gpu_hip_host_vector_variable", torch.float64, C.c_size_t(n), hip.ptr(planes[0]), hip.ptr(planes[1]), hip.ptr(planes[2]),
+             hip.ptr(out), hip.stream_ptr())
+    return HostVariableInfo(VECTOR, out.cpu().numpy().reshape(n, 3), name)
+
+
 def _write(solver, fields, prefix, dist, ascii):
     part = solver.part
     rank, nranks = part.rank, part.nranks
