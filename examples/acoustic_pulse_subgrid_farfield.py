@@ -69,7 +69,14 @@ def main():
     ap.add_argument("--adapt-every", type=int, default=20)
     ap.add_argument("--min-level", type=int, default=3, help="coarsest block level (a block holds 4 x 4 subcells)")
     ap.add_argument("--max-level", type=int, default=6)
-    ap.add_argument("--threshold", type=float, default=0.02)
+    ap.add_argument("--threshold", type=float, default=None, help="refine above this (default 0.02; loehner: 0.8)")
+    ap.add_argument("--indicator", choices=["reference", "loehner"], default="reference",
+                    help="what steers the adaptation: the reference's dimensional criterion, or the scale-free Loehner "
+                         "indicator (amr.Loehner; then --threshold defaults to 0.8, --coarsen to 0.2, --buffer to 1: the customary "
+                         "values for this estimator, which nobody has tuned on this solver)")
+    ap.add_argument("--quantities", default="density", help="loehner: comma-separated, of density, pressure, mach, entropy")
+    ap.add_argument("--coarsen", type=float, default=None, help="loehner: coarsen a family whose mean lies below this (default 0.2)")
+    ap.add_argument("--buffer", type=int, default=None, help="loehner: layers of face neighbours refined ahead of a feature (default 1)")
     ap.add_argument("--cfl", type=float, default=0.35)
     ap.add_argument("--flux", choices=list(FLUXES), default="kepes")
     ap.add_argument("--ramp", type=float, nargs="?", const=0.95, default=None,
@@ -79,6 +86,13 @@ def main():
     args = ap.parse_args()
     if args.toy:
         args.min_level, args.max_level, args.t_end, args.adapt_every = 2, 3, 0.05, 5
+    indicator, coarsen = None, None
+    if args.indicator == "loehner":
+        indicator = amr.Loehner(tuple(args.quantities.split(",")), buffer=1 if args.buffer is None else args.buffer)
+        coarsen = 0.2 if args.coarsen is None else args.coarsen
+        args.threshold = 0.8 if args.threshold is None else args.threshold
+    elif args.threshold is None:
+        args.threshold = 0.02
 
     mesh = SynthMesh(2, args.min_level, args.min_level, sides=(("farfield", 0),) * 4)
     part = mesh.partition(subgrid=True)
@@ -86,7 +100,7 @@ def main():
                            open_boundaries=True, farfield=True, inflow_states=ambient_state())
 
     def adapt(s):
-        return amr.adapt_subgrid(s, args.threshold, args.min_level, args.max_level)[0]
+        return amr.adapt_subgrid(s, args.threshold, args.min_level, args.max_level, indicator=indicator, coarsen_below=coarsen)[0]
 
     for _ in range(args.max_level - args.min_level):      # refine around the pulse, then re-evaluate the state
         solver = adapt(solver)
@@ -125,6 +139,8 @@ def main():
                   vtk.get_host_vector_variable(solver, solver.next, (1, 2, 3), "momentum")]
         # derived fields, formed on the device (fields.py; the gradient fields take no term from boundary faces)
         fields += [vtk.get_host_derived_variable(solver, name) for name in ("pressure", "dilatation")]
+        if indicator is not None:
+            fields.append(vtk.get_host_indicator_variable(solver, indicator))
         print("wrote", vtk.save_variables_to_vtk(solver, fields, os.path.join(args.out, "acoustic_pulse_subgrid")))
 
 

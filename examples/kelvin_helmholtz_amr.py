@@ -31,10 +31,24 @@ def main():
     ap.add_argument("--adapt-every", type=int, default=50)
     ap.add_argument("--min-level", type=int, default=5)
     ap.add_argument("--max-level", type=int, default=9)
-    ap.add_argument("--threshold", type=float, default=10.0)     # mesh_manager.inl:141
+    ap.add_argument("--threshold", type=float, default=None, help="refine above this (default 10.0; loehner: 0.8)")     # mesh_manager.inl:141
+    ap.add_argument("--indicator", choices=["reference", "loehner"], default="reference",
+                    help="what steers the adaptation: the reference's dimensional criterion, or the scale-free Loehner "
+                         "indicator (amr.Loehner; then --threshold defaults to 0.8, --coarsen to 0.2, --buffer to 1: the customary "
+                         "values for this estimator, which nobody has tuned on this solver)")
+    ap.add_argument("--quantities", default="density", help="loehner: comma-separated, of density, pressure, mach, entropy")
+    ap.add_argument("--coarsen", type=float, default=None, help="loehner: coarsen a family whose mean lies below this (default 0.2)")
+    ap.add_argument("--buffer", type=int, default=None, help="loehner: layers of face neighbours refined ahead of a feature (default 1)")
     ap.add_argument("--dtype", default="f64", choices=["f32", "f64"])
     ap.add_argument("--vtk", default=None, help="prefix of the .vtu / .pvtu files written at the end (density, energy, momentum, pressure, mach, vorticity)")
     args = ap.parse_args()
+    indicator, coarsen = None, None
+    if args.indicator == "loehner":
+        indicator = amr.Loehner(tuple(args.quantities.split(",")), buffer=1 if args.buffer is None else args.buffer)
+        coarsen = 0.2 if args.coarsen is None else args.coarsen
+        args.threshold = 0.8 if args.threshold is None else args.threshold
+    elif args.threshold is None:
+        args.threshold = 10.0
     dtype = torch.float64 if args.dtype == "f64" else torch.float32
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     rehearsal = os.environ.get("T8GPU_REHEARSAL", "0") == "1"
@@ -51,10 +65,10 @@ def main():
 
     def adapt(s):
         if world == 1:
-            return amr.adapt(s, args.threshold, args.min_level, args.max_level)[0]
+            return amr.adapt(s, args.threshold, args.min_level, args.max_level, indicator=indicator, coarsen_below=coarsen)[0]
         # refreshes the ghost slots of the current state itself (the indicator reads them), through the run's halo object
         return amr.adapt_partitioned(s, dist, host_staged=rehearsal, halo=halo_of.get(id(s)), threshold=args.threshold,
-                                     min_level=args.min_level, max_level=args.max_level)
+                                     min_level=args.min_level, max_level=args.max_level, indicator=indicator, coarsen_below=coarsen)
 
     def total(x, op="sum"):
         if world == 1:
@@ -116,6 +130,8 @@ def main():
                   vtk.get_host_vector_variable(solver, solver.next, (1, 2, 3), "momentum")]
         # derived fields, formed on the device (fields.py; the gradient fields take no term from boundary faces)
         fields += [vtk.get_host_derived_variable(solver, name, halo=halo) for name in ("pressure", "mach", "vorticity")]
+        if indicator is not None:
+            fields.append(vtk.get_host_indicator_variable(solver, indicator, halo=halo))
         say("wrote", vtk.save_variables_to_vtk(solver, fields, args.vtk, dist=dist))
     say(f"iterate: {total(cells) / total(t_iter, 'max') / 1e6:.1f} M cell-updates/s (host-synchronised per step), "
         f"adapt: {t_adapt:.2f} s total, iterate: {t_iter:.2f} s total")

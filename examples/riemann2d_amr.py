@@ -39,20 +39,34 @@ def main():
     ap.add_argument("--adapt-every", type=int, default=20)
     ap.add_argument("--min-level", type=int, default=5)
     ap.add_argument("--max-level", type=int, default=9)
-    ap.add_argument("--threshold", type=float, default=10.0)     # mesh_manager.inl:141
+    ap.add_argument("--threshold", type=float, default=None, help="refine above this (default 10.0; loehner: 0.8)")     # mesh_manager.inl:141
+    ap.add_argument("--indicator", choices=["reference", "loehner"], default="reference",
+                    help="what steers the adaptation: the reference's dimensional density jump, or the scale-free Loehner "
+                         "indicator (amr.Loehner; then --threshold defaults to 0.8, --coarsen to 0.2, --buffer to 1: the customary "
+                         "values for this estimator, which nobody has tuned on this solver)")
+    ap.add_argument("--quantities", default="density", help="loehner: comma-separated, of density, pressure, mach, entropy")
+    ap.add_argument("--coarsen", type=float, default=None, help="loehner: coarsen a family whose mean lies below this (default 0.2)")
+    ap.add_argument("--buffer", type=int, default=None, help="loehner: layers of face neighbours refined ahead of a feature (default 1)")
     ap.add_argument("--cfl", type=float, default=0.35)
     ap.add_argument("--out", default=None, help="directory of the .vtu written at the end (density, energy, momentum, pressure, schlieren)")
     ap.add_argument("--toy", action="store_true", help="levels 3-5, t_end 0.05 (a quick check)")
     args = ap.parse_args()
     if args.toy:
         args.min_level, args.max_level, args.t_end, args.adapt_every = 3, 5, 0.05, 5
+    indicator, coarsen = None, None
+    if args.indicator == "loehner":
+        indicator = amr.Loehner(tuple(args.quantities.split(",")), buffer=1 if args.buffer is None else args.buffer)
+        coarsen = 0.2 if args.coarsen is None else args.coarsen
+        args.threshold = 0.8 if args.threshold is None else args.threshold
+    elif args.threshold is None:
+        args.threshold = 10.0
 
     sides = ("outflow",) * 4
     mesh = SynthMesh(2, args.min_level, args.min_level, sides=sides)
     solver = PlainSolver(mesh.partition(), torch.float64, mode="fused", state=initial_state(mesh.partition()))
 
     def adapt(s):
-        return amr.adapt(s, args.threshold, args.min_level, args.max_level)[0]
+        return amr.adapt(s, args.threshold, args.min_level, args.max_level, indicator=indicator, coarsen_below=coarsen)[0]
 
     for _ in range(args.max_level - args.min_level):      # refine around the discontinuities, then re-evaluate the state
         solver = adapt(solver)
@@ -61,11 +75,14 @@ def main():
     solver.use_native_stepper()
     t, it, cells, t_iter = 0.0, 0, 0, 0.0
     while t < args.t_end - 1e-12:
-        if it % args.adapt_every == 0 and it > 0:
+        fresh = it % args.adapt_every == 0 and it > 0
+        if fresh:
             solver = adapt(solver)
             solver.use_native_stepper()
         if it == 0:
             dt = 0.1 * 2.0 ** -solver.part.mesh.finest_level
+        elif fresh:
+            dt = solver.cfl_timestep(cfl=args.cfl)                 # a solver fresh from an adapt has no face speeds yet
         else:
             dt = solver.compute_timestep(cfl=args.cfl)             # CFL step from the speeds of the last step (open faces too)
         dt = min(dt, args.t_end - t)
@@ -89,6 +106,8 @@ def main():
                   vtk.get_host_vector_variable(solver, solver.next, (1, 2, 3), "momentum")]
         # derived fields, formed on the device (fields.py; the gradient fields take no term from boundary faces)
         fields += [vtk.get_host_derived_variable(solver, name) for name in ("pressure", "schlieren")]
+        if indicator is not None:
+            fields.append(vtk.get_host_indicator_variable(solver, indicator))
         print("wrote", vtk.save_variables_to_vtk(solver, fields, os.path.join(args.out, "riemann2d")))
 
 

@@ -598,6 +598,54 @@ int t8gpu_hip_subgrid_fields_f64(int rank, int num_blocks, T8gpuVars_f64 state, 
                                  const int32_t* face_neighbor_offset, const double* face_normals, const double* face_surfaces,
                                  const int32_t* csr_offsets, const int32_t* csr_entries, T8gpuFieldPlanes out, void* stream);
 
+/* ---- scale-free refinement indicator (csrc/hip/indicator.hip) ------------------------------
+ * Loehner's estimator without cross terms, per axis, with a noise filter and a boundary closure. For cell c (an element, or a
+ * subcell of a Subgrid block) and a scalar q, over the INTERIOR (sub-)faces s of c -- o the cell across, n_s the unit normal
+ * outward from c, A_s the area, everything in double whatever float_type is:
+ *    h = V^(1/dim)   (subcell: (V_block / S)^(1/rank));   d_s = (h_c + h_o) / 2;   w_s,a = A_s |n_s,a|,  a = x, y, z
+ *    N_a = sum_s w_s,a (q_o - q_c) / d_s        D_a = sum_s w_s,a (|q_o - q_c| + filter (|q_o| + |q_c|)) / d_s
+ *    b_a = sum_s A_s n_s,a    W_a = sum_s w_s,a    k_a = W_a > 0 ? max(0, 1 - |b_a| / W_a) : 0
+ *    E_q = sqrt(sum_a (k_a N_a)^2) / sqrt(sum_a D_a^2)    (0 where the denominator is 0)
+ * and E = the maximum of E_q over the quantities of quantity_mask: bit 0 density, 1 pressure, 2 mach, 3 entropy (the formulas
+ * of the output fields above, gamma = 1.4). E is dimensionless, lies in [0, 1] and does not depend on the level. Boundary
+ * faces add no term; k_a closes the cell: b_a is what its interior faces leave open, so a Cartesian cell at a wall has k_a = 0
+ * along the wall normal, a cell with all faces interior k_a = 1. A face to a ghost slot is an interior face: the ghost state
+ * (and, for the plain kernel, volume[ghost]) must be current. A uniform state gives exactly +0; a linear q on a uniform
+ * Cartesian mesh gives exactly 0 when its differences are exact (the file is compiled without contraction into fused
+ * multiply-adds for that). Non-finite or non-physical states: not specified. Gathers without atomics, summed in the order of
+ * the output fields above (CSR order; inside a hanging face j-major, i-minor; in-block faces first): two calls, same bits.
+ * Plain: one lane per owned element, writes out[num_elements]; dim is the mesh dimension of h (2 for a 2D mesh stored with
+ * normal_dim = 3). Subgrid: writes cell_out[num_blocks S] (per subcell, storage order) and block_out[num_blocks] (the maximum
+ * over the block's subcells); either may be NULL and is then left alone.
+ * Returns 0 for n <= 0; hipErrorInvalidValue, before any launch, for a NULL state plane or connectivity pointer, an empty
+ * mask, a bit above 3, filter < 0, normal_dim / dim / rank outside {2, 3}.
+ * t8gpu_hip_indicator_spread: one buffer layer, out[e] = max(in[e], in[o] over the face neighbours o of e) for the owned
+ * elements or blocks e; `in` has num_elements + ghosts entries, ghost entries are read; in != out. max is exact. */
+#define T8GPU_INDICATOR_DENSITY 1u
+#define T8GPU_INDICATOR_PRESSURE 2u
+#define T8GPU_INDICATOR_MACH 4u
+#define T8GPU_INDICATOR_ENTROPY 8u
+int t8gpu_hip_plain_indicator_f32(int num_elements, int normal_dim, int dim, unsigned quantity_mask, double filter, T8gpuVars_f32 state,
+                                  const float* volume, const int32_t* face_neighbors, const float* face_normals,
+                                  const float* face_surfaces, const int32_t* csr_offsets, const int32_t* csr_entries, double* out,
+                                  void* stream);
+int t8gpu_hip_plain_indicator_f64(int num_elements, int normal_dim, int dim, unsigned quantity_mask, double filter, T8gpuVars_f64 state,
+                                  const double* volume, const int32_t* face_neighbors, const double* face_normals,
+                                  const double* face_surfaces, const int32_t* csr_offsets, const int32_t* csr_entries, double* out,
+                                  void* stream);
+int t8gpu_hip_subgrid_indicator_f32(int rank, int num_blocks, unsigned quantity_mask, double filter, T8gpuVars_f32 state,
+                                    const float* volumes, const int32_t* face_neighbors, const int32_t* face_level_difference,
+                                    const int32_t* face_neighbor_offset, const float* face_normals, const float* face_surfaces,
+                                    const int32_t* csr_offsets, const int32_t* csr_entries, double* cell_out, double* block_out,
+                                    void* stream);
+int t8gpu_hip_subgrid_indicator_f64(int rank, int num_blocks, unsigned quantity_mask, double filter, T8gpuVars_f64 state,
+                                    const double* volumes, const int32_t* face_neighbors, const int32_t* face_level_difference,
+                                    const int32_t* face_neighbor_offset, const double* face_normals, const double* face_surfaces,
+                                    const int32_t* csr_offsets, const int32_t* csr_entries, double* cell_out, double* block_out,
+                                    void* stream);
+int t8gpu_hip_indicator_spread(int num_elements, const double* in, const int32_t* face_neighbors, const int32_t* csr_offsets,
+                               const int32_t* csr_entries, double* out, void* stream);
+
 /* ---- AMR indicator and data transfer for plain elements---------------------------------
  * estimate_gradient<<<>>>: examples/compressible_euler/kernels.cu:471-501 (|rho_r - rho_l| added to both
  * neighbours; the reference accumulates into its Fluxes/Rho plane, any zeroed plane works). */

@@ -76,6 +76,10 @@ void t8gpu_synth_part_kh_ic(const void* part, int cells_per_dim, double* out, si
  * adapt_data[n_new+1]: first old element of every new element (mesh_manager.inl:258-281); returns 0 on success. */
 void  t8gpu_synth_mesh_marks(const void* mesh, const double* criteria, double threshold, int min_level, int max_level,
                              int family_members_averaged, int8_t* marks);
+/* the same walk with two thresholds: +1 where criteria > refine_above, -1 for a complete family whose mean is
+ * < coarsen_below (coarsen_below == refine_above: the marks of the call above, byte for byte) */
+void  t8gpu_synth_mesh_marks_hysteresis(const void* mesh, const double* criteria, double refine_above, double coarsen_below,
+                                        int min_level, int max_level, int family_members_averaged, int8_t* marks);
 /* clears the -1 marks of families cut by a partition offset (a family is only coarsened on one process) */
 void  t8gpu_synth_mesh_unmark_split_families(const void* mesh, int8_t* marks, const int64_t* offsets, int n_offsets);
 void* t8gpu_synth_mesh_adapt(const void* mesh, const int8_t* marks);

@@ -26,17 +26,117 @@ def refinement_criteria(solver):
     return crit
 
 
-def adapt(solver, threshold=10.0, min_level=1, max_level=4, family_members_averaged=4, volume_dim=None):
+class Loehner:
+    """The scale-free refinement indicator of csrc/hip/indicator.hip (include/t8gpu_hip.h): Loehner's estimator
+    without cross terms, per axis, on the maximum over `quantities` ("density", "pressure", "mach", "entropy"), with the noise
+    filter `filter` (eps) and `buffer` layers of face neighbours added to every flagged element / block. Dimensionless, in
+    [0, 1], independent of the level: one pair of thresholds serves every problem and every max_level. Pass it as
+    `indicator=` to the adapt functions of this module; `threshold` is then the refine threshold (customarily 0.8) and
+    `coarsen_below` the coarsen threshold (customarily 0.2)."""
+    QUANTITIES = {"density": 1, "pressure": 2, "mach": 4, "entropy": 8}       # T8GPU_INDICATOR_* of include/t8gpu_hip.h
+
+    def __init__(self, quantities=("density",), filter=0.01, buffer=0):
+        names = [quantities] if isinstance(quantities, str) else list(quantities)
+        if not names:
+            raise ValueError("Loehner needs at least one quantity")
+        for name in names:
+            if name not in self.QUANTITIES:
+                raise ValueError(f"unknown indicator quantity {name!r}: one of {', '.join(self.QUANTITIES)}")
+        if not float(filter) >= 0.0:
+            raise ValueError(f"filter must be >= 0, got {filter}")
+        if int(buffer) != buffer or buffer < 0:
+            raise ValueError(f"buffer must be a number of layers >= 0, got {buffer}")
+        self.quantities, self.filter, self.buffer = tuple(names), float(filter), int(buffer)
+        self.mask = 0
+        for name in names:
+            self.mask |= self.QUANTITIES[name]
+
+    def _launch(self, solver, step, stream, halo, cell_out, block_out):
+        from . import fields
+        s = solver.next if step is None else step
+        stream = torch.cuda.current_stream() if stream is None else stream
+        if halo is not None:
+            with torch.cuda.stream(stream):
+                halo.exchange(solver.step_planes(s))
+        off, ent = fields._csr(solver)
+        st, sp = solver.get_own_variables(s), hip.stream_ptr(stream)
+        mask, eps = C.c_uint(self.mask), C.c_double(self.filter)
+        if hasattr(solver, "S"):
+            hip.call("t8gpu_hip_subgrid_indicator", solver.dtype, solver.rank, solver.N, mask, eps, st, hip.ptr(solver.volumes),
+                     hip.ptr(solver.fn), hip.ptr(solver.level_diff), hip.ptr(solver.nb_offset), hip.ptr(solver.normals),
+                     hip.ptr(solver.areas), hip.ptr(off), hip.ptr(ent), hip.ptr(cell_out), hip.ptr(block_out), sp)
+        else:
+            hip.call("t8gpu_hip_plain_indicator", solver.dtype, solver.N, solver.ndim, int(solver.part.mesh.dim), mask, eps, st,
+                     hip.ptr(solver.get_own_volume()), hip.ptr(solver.fn), hip.ptr(solver.normals), hip.ptr(solver.areas),
+                     hip.ptr(off), hip.ptr(ent), hip.ptr(cell_out), sp)
+
+    def cell_values(self, solver, step=None, stream=None, halo=None):
+        """float64 device tensor [owned_cells] of the indicator of state(step) in storage order (Subgrid: per subcell). One
+        launch on `stream`, no sync. `halo` refreshes the ghost slots of that step first, as for derived_fields; without it
+        the caller vouches that they are current."""
+        stream = torch.cuda.current_stream() if stream is None else stream
+        with torch.cuda.stream(stream):
+            out = torch.empty(solver.owned_cells, dtype=torch.float64, device="cuda")
+        self._launch(solver, step, stream, halo, out, None)
+        return out
+
+    def criteria(self, solver, halo=None, ghosts_current=False):
+        """float64 device tensor [N] of the `next` state: one value per element / block (Subgrid: the maximum over the block's
+        subcells), after `buffer` spread passes (t8gpu_hip_indicator_spread). On several ranks `halo` (the run's HaloExchange)
+        also refreshes the ghost entries of the criteria before every pass, so that the marks do not depend on the number
+        of ranks. ghosts_current: the caller has just exchanged the state through `halo`; it is not exchanged again."""
+        from . import fields
+        N, G = solver.N, solver.G
+        cur = torch.zeros(N + G, dtype=torch.float64, device="cuda")
+        state_halo = None if ghosts_current else halo
+        if hasattr(solver, "S"):
+            self._launch(solver, None, None, state_halo, None, cur)
+        else:
+            self._launch(solver, None, None, state_halo, cur, None)
+        if self.buffer and N > 0:
+            off, ent = fields._csr(solver)
+            nxt = torch.zeros_like(cur)
+            for _ in range(self.buffer):
+                if G > 0:
+                    if halo is None:
+                        raise ValueError("buffer layers on a partition with ghosts need halo= (the ghost entries of the criteria "
+                                         "are exchanged between the passes)")
+                    halo.exchange_elements(cur)
+                hip.check(hip.lib().t8gpu_hip_indicator_spread(N, hip.ptr(cur), hip.ptr(solver.fn), hip.ptr(off), hip.ptr(ent),
+                                                               hip.ptr(nxt), hip.stream_ptr()))
+                cur, nxt = nxt, cur
+        return cur[:N]
+
+
+def _marks(mesh, crit, threshold, min_level, max_level, family_members_averaged, coarsen_below):
+    """the one-threshold walk of the reference, or (coarsen_below given) the two-threshold one"""
+    if coarsen_below is None:
+        return mesh.marks_from_criteria(crit, threshold, min_level, max_level, family_members_averaged)
+    return mesh.marks_from_criteria(crit, threshold, min_level, max_level, family_members_averaged, coarsen_below=coarsen_below)
+
+
+def _criteria(solver, indicator, halo=None):
+    """the criteria [N] on the device: the reference's (indicator None) or indicator.criteria(); with a `halo` the caller has
+    exchanged the state's ghosts already"""
+    if indicator is not None:
+        return indicator.criteria(solver, halo, ghosts_current=halo is not None)
+    return subgrid_refinement_criteria(solver) if hasattr(solver, "S") else refinement_criteria(solver)
+
+
+def adapt(solver, threshold=10.0, min_level=1, max_level=4, family_members_averaged=4, volume_dim=None, indicator=None,
+          coarsen_below=None):
     """Refine / coarsen the mesh of a single-rank PlainSolver by the reference's criterion and transfer the
-    current solution. Returns the new solver (same dtype, flux, kernel tier, step bookkeeping)."""
+    current solution. Returns the new solver (same dtype, flux, kernel tier, step bookkeeping).
+    indicator (a Loehner): its criteria instead of the reference's, `threshold` the refine threshold; coarsen_below: the
+    coarsen threshold of the two-threshold marks (None: `threshold`, the reference's walk)."""
     import time
     part = solver.part
     assert part.nranks == 1, "multi-rank adaptation goes through amr.adapt_partitioned"
     mesh = part.mesh
     t0 = time.perf_counter()
-    crit = refinement_criteria(solver).double().cpu().numpy()
+    crit = _criteria(solver, indicator).double().cpu().numpy()
     t1 = time.perf_counter()
-    marks = mesh.marks_from_criteria(crit, threshold, min_level, max_level, family_members_averaged)
+    marks = _marks(mesh, crit, threshold, min_level, max_level, family_members_averaged, coarsen_below)
     new_mesh, adapt_data = mesh.adapt(marks)
     new_part = new_mesh.partition(0, 1, subgrid=False, normal_dim=part.normal_dim)
     t2 = time.perf_counter()
@@ -128,9 +228,12 @@ class PartitionedAdapt(_Repartition):
     MeshManager::partition, t8gpu/mesh/mesh_manager.inl:196-330, 645-723): a message is 5 variables + volume per element,
     packed by a gather kernel."""
 
-    def __init__(self, solver, all_criteria, threshold=10.0, min_level=1, max_level=4, family_members_averaged=4):
+    def __init__(self, solver, all_criteria, threshold=10.0, min_level=1, max_level=4, family_members_averaged=4, indicator=None,
+                 coarsen_below=None):
+        """indicator: where all_criteria came from (adapt_partitioned evaluates it; nothing here depends on it);
+        coarsen_below: the coarsen threshold of the two-threshold marks (None: `threshold`)"""
         part = solver.part
-        super().__init__(solver, part.mesh.marks_from_criteria(all_criteria, threshold, min_level, max_level, family_members_averaged))
+        super().__init__(solver, _marks(part.mesh, all_criteria, threshold, min_level, max_level, family_members_averaged, coarsen_below))
         dtype, dev = solver.dtype, solver.planes.device
         # 1. local data transfer (adapt_variables_and_volume) into 6 temporary planes
         self.tmp = torch.zeros((6, max(1, self.n_have)), dtype=dtype, device=dev)
@@ -193,13 +296,14 @@ def adapt_partitioned(solver, dist, host_staged=False, halo=None, **kw):
     step driver refreshes those slots -- a stage only exchanges the ghosts of its SOURCE state, so after a step the
     last stage's output carries ghost values two stages old. The exchange is therefore part of this function (through
     `halo`, the run's HaloExchange of this partition, or a temporary one): refinement marks must not depend on the
-    number of ranks."""
+    number of ranks. indicator= (a Loehner) and coarsen_below= go to PartitionedAdapt; the indicator's buffer passes exchange
+    the ghost entries of the criteria through the same `halo`."""
     if solver.part.nranks > 1:
         if halo is None:
             from .halo import HaloExchange
             halo = HaloExchange(solver.part, solver.dtype, dist, overlap=False, stage_through_host=host_staged)
         halo.exchange(solver.step_planes(solver.next))
-    all_crit = _gather_criteria(refinement_criteria(solver).double(), solver, dist, host_staged)
+    all_crit = _gather_criteria(_criteria(solver, kw.get("indicator"), halo).double(), solver, dist, host_staged)
     pa = PartitionedAdapt(solver, all_crit, **kw)
     pa.transport(dist, host_staged)
     new = pa.finish()
@@ -215,15 +319,16 @@ def subgrid_refinement_criteria(solver):
     return crit
 
 
-def adapt_subgrid(solver, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4):
+def adapt_subgrid(solver, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4, indicator=None, coarsen_below=None):
     """SubgridCompressibleEulerSolver::adapt (examples/subgrid/solver.inl:327-345) for a single-rank SubgridSolver:
-    H1-seminorm indicator, the forest adapt, block-wise data transfer (subgrid_mesh_manager.inl:246-425)."""
+    H1-seminorm indicator, the forest adapt, block-wise data transfer (subgrid_mesh_manager.inl:246-425).
+    indicator (a Loehner): its block maxima instead, `threshold` the refine threshold; coarsen_below: as for adapt()."""
     from .solver import SubgridSolver
     part = solver.part
     assert part.nranks == 1
     mesh = part.mesh
-    crit = subgrid_refinement_criteria(solver).double().cpu().numpy()
-    marks = mesh.marks_from_criteria(crit, threshold, min_level, max_level, family_members_averaged)
+    crit = _criteria(solver, indicator).double().cpu().numpy()
+    marks = _marks(mesh, crit, threshold, min_level, max_level, family_members_averaged, coarsen_below)
     new_mesh, adapt_data = mesh.adapt(marks)
     new_part = new_mesh.partition(0, 1, subgrid=True)
     S = solver.S
@@ -245,10 +350,12 @@ class PartitionedSubgridAdapt(_Repartition):
     injection / mean (subgrid_mesh_manager.inl:246-425), a message is 5 x 4^rank values + one volume per block. A run of
     blocks is contiguous in every variable plane, so a message is six slices; no gather kernel is needed."""
 
-    def __init__(self, solver, all_criteria, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4):
+    def __init__(self, solver, all_criteria, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4, indicator=None,
+                 coarsen_below=None):
+        """indicator / coarsen_below: as for PartitionedAdapt"""
         from .solver import SubgridSolver
         part = solver.part
-        super().__init__(solver, part.mesh.marks_from_criteria(all_criteria, threshold, min_level, max_level, family_members_averaged))
+        super().__init__(solver, _marks(part.mesh, all_criteria, threshold, min_level, max_level, family_members_averaged, coarsen_below))
         S = self.S = solver.S
         dtype, dev = solver.dtype, solver.planes.device
         self.tmp = torch.zeros((5, max(1, self.n_have) * S), dtype=dtype, device=dev)
@@ -292,9 +399,18 @@ class PartitionedSubgridAdapt(_Repartition):
         return new
 
 
-def adapt_subgrid_partitioned(solver, dist, host_staged=False, **kw):
-    """Collective: every rank calls it with its own SubgridSolver; returns the rank's new solver."""
-    all_crit = _gather_criteria(subgrid_refinement_criteria(solver).double(), solver, dist, host_staged)
+def adapt_subgrid_partitioned(solver, dist, host_staged=False, halo=None, **kw):
+    """Collective: every rank calls it with its own SubgridSolver; returns the rank's new solver.
+    The reference's criterion reads no other block, so without indicator= nothing is exchanged. A Loehner indicator reads the
+    ghost blocks of the `next` state: they are exchanged first, through `halo` (the run's HaloExchange of this partition) or a
+    temporary one, as in adapt_partitioned."""
+    indicator = kw.get("indicator")
+    if indicator is not None and solver.part.nranks > 1:
+        if halo is None:
+            from .halo import HaloExchange
+            halo = HaloExchange(solver.part, solver.dtype, dist, overlap=False, stage_through_host=host_staged)
+        halo.exchange(solver.step_planes(solver.next))
+    all_crit = _gather_criteria(_criteria(solver, indicator, halo).double(), solver, dist, host_staged)
     pa = PartitionedSubgridAdapt(solver, all_crit, **kw)
     pa.transport(dist, host_staged)
     return pa.finish()

@@ -588,6 +588,28 @@ void t8gpu_synth_mesh_marks(const void* mesh, const double* criteria, double thr
   }
 }
 
+// The same walk with two thresholds (hysteresis): +1 if criteria > refine_above, -1 for a complete family whose mean is
+// < coarsen_below. With coarsen_below == refine_above these are the marks of t8gpu_synth_mesh_marks, byte for byte; with
+// coarsen_below < refine_above the elements in between keep their level, so a cell near one threshold does not flicker.
+void t8gpu_synth_mesh_marks_hysteresis(const void* mesh, const double* criteria, double refine_above, double coarsen_below,
+                                       int min_level, int max_level, int family_members_averaged, int8_t* marks) {
+  const Mesh&  M    = *static_cast<const Mesh*>(mesh);
+  const size_t n    = M.leaves.size();
+  const int    nsub = 1 << M.dim;
+  const int    navg = family_members_averaged > 0 ? std::min(family_members_averaged, nsub) : nsub;
+#pragma omp parallel for num_threads(host_threads()) schedule(static)
+  for (int64_t e = 0; e < static_cast<int64_t>(n); e++)
+    marks[e] = (M.leaves[e].level < max_level && criteria[e] > refine_above) ? 1 : 0;
+#pragma omp parallel for num_threads(host_threads()) schedule(static)
+  for (int64_t e = 0; e < static_cast<int64_t>(n); e++) {
+    if (__atomic_load_n(&marks[e], __ATOMIC_RELAXED) != 0 || M.leaves[e].level <= min_level || !is_family_start(M, static_cast<size_t>(e))) continue;
+    double mean = 0;
+    for (int ch = 0; ch < navg; ch++) mean += criteria[e + ch] / navg;
+    if (mean < coarsen_below)
+      for (int ch = 0; ch < nsub; ch++) __atomic_store_n(&marks[e + ch], static_cast<int8_t>(-1), __ATOMIC_RELAXED);
+  }
+}
+
 // A family whose members live on two ranks is not coarsened (t8code only coarsens families that are
 // complete on one process): clear the -1 marks of families cut by a partition offset.
 void t8gpu_synth_mesh_unmark_split_families(const void* mesh, int8_t* marks, const int64_t* offsets, int n_offsets) {

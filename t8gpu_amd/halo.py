@@ -133,3 +133,30 @@ class HaloExchange:
     def exchange(self, planes5):
         self.start(planes5)
         self.finish()
+
+    def exchange_elements(self, values):
+        """One value per element or block: `values` is a float64 tensor [N + G]; sends values[send_idx] to every peer and fills
+        the ghost entries values[N:] in recv_off order (the refinement criteria between two buffer passes, amr.Loehner). Torch
+        indexing only -- once per adapt cycle, not a hot path -- on the current stream; on CUDA (nccl), on CPU (gloo) and with
+        stage_through_host. The owned entries are left alone."""
+        if values.dtype != torch.float64 or values.dim() != 1 or values.numel() != self.N + self.G:
+            raise ValueError(f"exchange_elements takes a float64 tensor [N + G] = [{self.N + self.G}]")
+        if not self.peers:
+            return
+        send = values[self.send_idx.to(values.device).long()]
+        recv = torch.empty(self.G, dtype=torch.float64, device=values.device)
+        staged = self.stage_through_host and values.is_cuda
+        if staged:
+            torch.cuda.current_stream().synchronize()
+            send, recv = send.cpu(), recv.cpu()
+        ops = []
+        for j, p in enumerate(self.peers):
+            r0, r1, s0, s1 = self.recv_off[j], self.recv_off[j + 1], self.send_off[j], self.send_off[j + 1]
+            if r1 > r0:
+                ops.append(self.dist.P2POp(self.dist.irecv, recv[r0:r1], p))
+            if s1 > s0:
+                ops.append(self.dist.P2POp(self.dist.isend, send[s0:s1], p))
+        if ops:
+            for req in self.dist.batch_isend_irecv(ops):
+                req.wait()
+        values[self.N:] = recv.to(values.device)

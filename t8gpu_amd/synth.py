@@ -38,6 +38,8 @@ def lib():
         _lib.t8gpu_synth_part_halo.argtypes = [C.c_void_p] + [C.c_void_p] * 6
         _lib.t8gpu_synth_part_kh_ic.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         _lib.t8gpu_synth_mesh_marks.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib.t8gpu_synth_mesh_marks_hysteresis.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                                                           C.c_void_p]
         _lib.t8gpu_synth_mesh_unmark_split_families.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         _lib.t8gpu_synth_mesh_adapt.restype = C.c_void_p
         _lib.t8gpu_synth_mesh_adapt.argtypes = [C.c_void_p, C.c_void_p]
@@ -155,13 +157,19 @@ class SynthMesh:
         return Partition(self, rank, nranks, subgrid, normal_dim)
 
     # -- adaptation (MeshManager::adapt without the data transfer, which runs on the device) --------
-    def marks_from_criteria(self, criteria, threshold, min_level, max_level, family_members_averaged=4):
-        """The reference's adapt callback for every element: +1 refine, -1 coarsen, 0 keep."""
+    def marks_from_criteria(self, criteria, threshold, min_level, max_level, family_members_averaged=4, coarsen_below=None):
+        """The reference's adapt callback for every element: +1 refine, -1 coarsen, 0 keep. coarsen_below (None: `threshold`,
+        through the reference's one-threshold walk): a family is coarsened when its mean lies below it, so that the elements
+        between the two thresholds keep their level."""
         crit = np.ascontiguousarray(criteria, np.float64)
         assert crit.size == self.num_elements
         marks = np.zeros(self.num_elements, np.int8)
-        lib().t8gpu_synth_mesh_marks(self._h, _p(crit), float(threshold), int(min_level), int(max_level),
-                                     int(family_members_averaged), _p(marks))
+        if coarsen_below is None:
+            lib().t8gpu_synth_mesh_marks(self._h, _p(crit), float(threshold), int(min_level), int(max_level),
+                                         int(family_members_averaged), _p(marks))
+        else:
+            lib().t8gpu_synth_mesh_marks_hysteresis(self._h, _p(crit), float(threshold), float(coarsen_below), int(min_level),
+                                                    int(max_level), int(family_members_averaged), _p(marks))
         return marks
 
     def partition_offsets(self, nranks):

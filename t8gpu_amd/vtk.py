@@ -88,6 +88,15 @@ def get_host_derived_variable(solver, name, step=None, halo=None):
     return HostVariableInfo(VECTOR, out.cpu().numpy().reshape(n, 3), name)
 
 
+def get_host_indicator_variable(solver, indicator, name="indicator", halo=None, step=None):
+    """The per-cell values of a refinement indicator (amr.Loehner.cell_values) as doubles on the host, ready for
+    save_variables_to_vtk; for a Subgrid solver in z-order, as get_host_derived_variable."""
+    t = indicator.cell_values(solver, step, halo=halo)
+    if hasattr(solver, "S"):
+        t = column_major_to_z_order(solver, t)
+    return HostVariableInfo(SCALAR, t.cpu().numpy(), name)
+
+
 def _write(solver, fields, prefix, dist, ascii):
     part = solver.part
     rank, nranks = part.rank, part.nranks
