@@ -10,10 +10,21 @@
 //
 // PINNING STATUS: the reference ships no tests, fixtures or golden vectors
 //  and cannot be built here (needs nvcc + t8code/libsc).
-// The only known answers are the three vectors recorded in SURVEY.md section 8c
-// (KEPES f64/f32, HLL f32), produced by the survey from the reference's own
-// functions; tests/test_oracle_golden.py checks them. Beyond those three
-// vectors parity is UNPINNED and rests on algebraic invariants.
+// What pins this file to it (tests/golden/README.md):
+//  * the three known answers of SURVEY.md section 8c (KEPES f64/f32, HLL f32)
+//    and the 10 240 flux vectors per float type made from the reference's own
+//    flux functions compiled for the host: tests/test_oracle_golden.py, bit for
+//    bit;
+//  * the executed kernel vectors -- inputs and outputs of the reference's
+//    kernel BODIES (plain and Subgrid flux kernels with the 2:1 hanging map,
+//    walls, the six RK stages) run on tiny AMR meshes:
+//    tests/test_oracle_reference_kernels.py, bit for bit;
+//  * the HIP tiers meet those same arrays directly, not only through this file:
+//    tests/test_gpu_reference_kernels.py (compat kernels one by one, the
+//    element -> slot map, one fused stage per kernel form).
+// Both fixtures come from host compilations behind stand-ins for the CUDA
+// qualifiers and built-ins, so by the project's rules
+// parity formally stays "unpinned".
 #pragma once
 
 #include <algorithm>

@@ -15,35 +15,12 @@ iteration per CUDA thread"), and every array of every case agrees BIT FOR BIT in
 The stand-ins the generator needs (CUDA built-ins, the accessor-owning friend classes) keep parity "unpinned" by the project
 rules."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import _oracle as O
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-PATH = os.path.join(HERE, "golden", "reference_kernel_vectors.npz")
-KEPES = 0
-
-_cache = {}
-
-
-def vectors():
-    if "z" not in _cache:
-        _cache["z"] = np.load(PATH, allow_pickle=False)
-    return _cache["z"]
-
-
-def case_names():
-    return sorted({k.split("|")[0] for k in vectors().files if "|" in k})
-
-
-def load(case, tag):
-    z = vectors()
-    ins = {k.split("|")[3]: z[k] for k in z.files if k.startswith(f"{case}|{tag}|in|")}
-    outs = {k.split("|")[3]: z[k] for k in z.files if k.startswith(f"{case}|{tag}|out|")}
-    return ins, outs
+from _kernel_vectors import KEPES, case_names, load, vectors
 
 
 def rel(a, b):
