@@ -26,6 +26,7 @@ from t8gpu_amd.synth import SynthMesh  # noqa: E402
 GAMMA = 1.4
 AMBIENT = (1.0, 1.0)   # rho, p
 SIDES = {"farfield": ("farfield", 0), "inflow": 0, "outflow": "outflow", "wall": "wall"}
+PROBES = ((0.5, 0.5), (0.75, 0.5), (0.9, 0.9))   # --probes: the pulse's centre, half way to a side, near a corner
 FLUXES = {"kepes": hip.KEPES, "hll": hip.HLL, "hllc": hip.HLLC}
 
 
@@ -72,6 +73,9 @@ def main():
     ap.add_argument("--flux", choices=list(FLUXES), default="kepes")
     ap.add_argument("--out", default=None, help="directory of the .vtu written at the end (density, energy, momentum, pressure, dilatation)")
     ap.add_argument("--toy", action="store_true", help="levels 3-5, t_end 0.05 (a quick check)")
+    ap.add_argument("--probes", action="store_true",
+                    help="record pressure at three fixed points every step, sampled on the device (sample_points), and save the "
+                         "series as acoustic_pulse_probes.npy in --out (default: the working directory): rows t, p_0, p_1, p_2")
     args = ap.parse_args()
     if args.toy:
         args.min_level, args.max_level, args.t_end, args.adapt_every = 3, 5, 0.05, 5
@@ -97,6 +101,8 @@ def main():
         solver.planes[5 * solver.next:5 * solver.next + 5] = ic
     solver.use_native_stepper()
     t, it, cells, t_iter = 0.0, 0, 0, 0.0
+    probes = torch.tensor(PROBES, dtype=torch.float64, device="cuda") if args.probes else None
+    series = []            # per step [t, p_0, p_1, p_2] on the device: read back once at the end
     while t < args.t_end - 1e-12:
         if it % args.adapt_every == 0:
             if it > 0:
@@ -112,6 +118,8 @@ def main():
         t += dt
         it += 1
         cells += solver.N
+        if probes is not None:
+            series.append((t, solver.sample_points(probes, "pressure")["pressure"]))
         if it % 50 == 0:
             print(f"it {it:5d}  t {t:.4f}  elements {solver.N:8d}  finest level {solver.part.mesh.finest_level}  dt {dt:.3e}",
                   flush=True)
@@ -119,6 +127,13 @@ def main():
     residual = float(np.abs(pressure(solver) - AMBIENT[1]).max())
     print(f"t = {t:.4f} after {it} steps, {solver.N} elements; {cells / t_iter / 1e6:.1f} M cell-updates/s (host-synchronised)")
     print(f"sides {args.sides}, flux {args.flux}: residual max |p - p_inf| = {residual:.3e}")
+    if probes is not None:
+        os.makedirs(args.out or ".", exist_ok=True)
+        path = os.path.join(args.out or ".", "acoustic_pulse_probes.npy")
+        p = torch.stack([s[1] for s in series], dim=1).cpu().numpy()
+        np.save(path, np.concatenate([np.array([[s[0] for s in series]]), p]))
+        print(f"wrote {path}: pressure at {PROBES} over {len(series)} steps, max |p - p_inf| = "
+              f"{', '.join(f'{x:.3e}' for x in np.abs(p - AMBIENT[1]).max(axis=1))}")
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         fields = [vtk.get_host_scalar_variable(solver, solver.next, 0, "density"),

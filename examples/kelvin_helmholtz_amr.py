@@ -17,6 +17,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from t8gpu_amd import amr, hostmem, vtk  # noqa: E402
@@ -41,6 +42,10 @@ def main():
     ap.add_argument("--buffer", type=int, default=None, help="loehner: layers of face neighbours refined ahead of a feature (default 1)")
     ap.add_argument("--dtype", default="f64", choices=["f32", "f64"])
     ap.add_argument("--vtk", default=None, help="prefix of the .vtu / .pvtu files written at the end (density, energy, momentum, pressure, mach, vorticity)")
+    ap.add_argument("--image", type=int, default=None, metavar="N",
+                    help="save N x N images of schlieren and density, sampled on the device (sample_grid), as .npy files beside the "
+                         "VTK output (prefix --vtk, or kh): at the end, and every --image-every steps")
+    ap.add_argument("--image-every", type=int, default=None, metavar="K")
     args = ap.parse_args()
     indicator, coarsen = None, None
     if args.indicator == "loehner":
@@ -76,6 +81,20 @@ def main():
         t = torch.tensor([x], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.SUM if op == "sum" else dist.ReduceOp.MAX)
         return float(t.item())
+
+    def save_images(s, it):
+        """schlieren and density of the current state on an N x N grid: one derived_fields pass and one fused sampling launch;
+        a pixel belongs to exactly one rank, the others contribute 0"""
+        images = s.sample_grid(["schlieren", "density"], (args.image, args.image), halo=halo_of.get(id(s)), fill=0.0)
+        prefix = args.vtk or "kh"
+        os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
+        for name, image in images.items():
+            if world > 1:
+                image = image.cpu() if rehearsal else image
+                dist.all_reduce(image)
+            if rank == 0:
+                np.save(f"{prefix}_{name}_{it:06d}.npy", image.cpu().numpy())
+        say(f"images at it {it}: {prefix}_{{schlieren,density}}_{it:06d}.npy", flush=True)
 
     mesh = SynthMesh(2, args.min_level, args.min_level)
     solver = PlainSolver(mesh.partition(rank, world), dtype, mode="fused")
@@ -116,12 +135,16 @@ def main():
         torch.cuda.synchronize()
         t_iter += time.perf_counter() - t0
         cells += solver.N
+        if args.image and args.image_every and (it + 1) % args.image_every == 0 and it + 1 < args.steps:
+            save_images(solver, it + 1)
         if it % 100 == 0:
             mon = solver.monitor(dist=dist)
             drift = float(abs(mon.integrals - mass0).max())
             say(f"it {it:5d}  elements {int(total(solver.N)):8d}  finest level {solver.part.mesh.finest_level}  dt {dt:.3e}  "
                 f"conservation drift {drift:.2e}  entropy {mon.entropy:.9e}  min p {mon.min_pressure:.4e}", flush=True)
     assert bool(torch.isfinite(solver.state()).all())
+    if args.image:
+        save_images(solver, args.steps)
     if args.vtk:
         # CompressibleEulerSolver::save_conserved_variables_to_vtk (examples/compressible_euler/solver.cu:177-186)
         os.makedirs(os.path.dirname(os.path.abspath(args.vtk)), exist_ok=True)

@@ -50,6 +50,9 @@ def main():
     ap.add_argument("--cfl", type=float, default=0.35)
     ap.add_argument("--out", default=None, help="directory of the .vtu written at the end (density, energy, momentum, pressure, schlieren)")
     ap.add_argument("--toy", action="store_true", help="levels 3-5, t_end 0.05 (a quick check)")
+    ap.add_argument("--lineout", action="store_true",
+                    help="save density along the diagonal (0, 0) - (1, 1), sampled on the device (sample_points), as "
+                         "riemann2d_lineout.npy in --out (default: the working directory): rows s, x, y, density")
     args = ap.parse_args()
     if args.toy:
         args.min_level, args.max_level, args.t_end, args.adapt_every = 3, 5, 0.05, 5
@@ -99,6 +102,14 @@ def main():
                   flush=True)
     assert bool(torch.isfinite(solver.state()).all())
     print(f"t = {t:.4f} after {it} steps, {solver.N} elements; {cells / t_iter / 1e6:.1f} M cell-updates/s (host-synchronised)")
+    if args.lineout:
+        n = 2 ** (solver.part.mesh.finest_level + 1)               # two points per finest cell: cell values, not interpolated
+        s = (np.arange(n) + 0.5) / n
+        rho = solver.sample_points(np.stack([s, s], axis=1), "density")["density"].cpu().numpy()
+        os.makedirs(args.out or ".", exist_ok=True)
+        path = os.path.join(args.out or ".", "riemann2d_lineout.npy")
+        np.save(path, np.stack([s * np.sqrt(2.0), s, s, rho]))
+        print(f"wrote {path}: density along the diagonal at {n} points, {rho.min():.4f} .. {rho.max():.4f}")
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         fields = [vtk.get_host_scalar_variable(solver, solver.next, 0, "density"),

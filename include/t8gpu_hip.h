@@ -598,6 +598,58 @@ int t8gpu_hip_subgrid_fields_f64(int rank, int num_blocks, T8gpuVars_f64 state, 
                                  const int32_t* face_neighbor_offset, const double* face_normals, const double* face_surfaces,
                                  const int32_t* csr_offsets, const int32_t* csr_entries, T8gpuFieldPlanes out, void* stream);
 
+/* ---- sampling on Cartesian forests: probe points, image grids, conservative resampling (csrc/hip/sample.hip)
+ * From a coordinate of the unit square / cube to the storage index of the cell that holds it, and from there to values. With
+ * D = T8GPU_SAMPLE_DEPTH: the integer coordinate of x in [0, 1) is floor(x 2^D), the key of a point the bit-interleave of its
+ * integer coordinates with x in the lowest bit. keys[num_elements] holds the key of every owned element's lower corner and
+ * levels[num_elements] its level, both in storage order (device arrays; t8gpu_amd/sample.py builds them): the keys ascend
+ * strictly and element e covers [keys[e], keys[e] + 2^(dim (D - levels[e]))). cells_per_axis is 1 for plain elements and 4
+ * for Subgrid blocks, whose cells have level levels[e] + 2; levels up to D (blocks: D - 2).
+ * Ownership: a point belongs to the cell with lo <= x < hi on every axis, so a point on a shared face or corner goes to the
+ * cell on the higher side. The cell index is the storage index among the owned cells: e, or e S + i + 4 j (+ 16 k) with
+ * (i, j, k) the two bits of the integer coordinates below the block's level. It is -1 for a point with a coordinate < 0 or
+ * >= 1, NaN or infinite (tested on the doubles, before any conversion), and for a point in no owned element (another rank's).
+ * Values are those of the holding cell cast to double, `fill` for cell -1; nothing is interpolated. Plane k of a
+ * T8gpuSamplePlanes is read from q[k] (the state's float type) when that is not NULL, else from d[k] (doubles, e.g. the
+ * planes of t8gpu_hip_*_fields_*); outputs are [num_planes][points or pixels], doubles.
+ * t8gpu_hip_sample_locate: cells[i] for points[i dim .. i dim + dim), one lane per point.
+ * t8gpu_hip_sample_gather: out[k][i] = plane k at cells[i], or fill.
+ * t8gpu_hip_sample_grid: both fused over a grid of n[0] x n[1] (x n[2]) pixels, x fastest, pixel centre
+ * lo + (i + 0.5) (hi - lo) / n per axis, evaluated in exactly this order without contraction (an axis with lo == hi is a slice
+ * plane at that coordinate); one wavefront per 8 x 8 tile of pixels, ragged tiles masked. `cells` may be NULL; with
+ * num_planes = 0 only the cells are written.
+ * t8gpu_hip_sample_uniform: conservative resampling onto the 2^level pixels per axis of a uniform level. For pixel P
+ * sums[k][P] = sum of w q over the owned cells that meet P and weights[P] = sum of w, w = 2^(-dim level of the smaller of
+ * pixel and cell): a pixel inside a cell takes w q of that cell, a pixel covering several cells sums them in ascending
+ * storage order in double. With weights = NULL sums[k][P] holds sum / weight instead, `fill` where the weight is 0. The order
+ * of a sum does not depend on the launch: two calls give the same bits. Ranks combine by adding sums and weights.
+ * No atomics, no LDS. Return 0 without a launch for num_points = 0 (gather: or num_planes = 0); hipErrorInvalidValue, before any
+ * launch, for dim outside {2, 3}, cells_per_axis outside {1, 4}, 2^31 or more owned cells, more than T8GPU_SAMPLE_PLANES
+ * planes or a plane with q and d both NULL, a grid extent <= 0, level outside [0, D], uniform without a plane, a NULL array that would be used. */
+#define T8GPU_SAMPLE_DEPTH 20
+#define T8GPU_SAMPLE_PLANES 16
+typedef struct T8gpuSamplePlanes_f32 { const float* q[16]; const double* d[16]; } T8gpuSamplePlanes_f32;
+typedef struct T8gpuSamplePlanes_f64 { const double* q[16]; const double* d[16]; } T8gpuSamplePlanes_f64;
+typedef struct T8gpuSampleGrid { double lo[3]; double hi[3]; int32_t n[3]; int32_t pad; } T8gpuSampleGrid;
+int t8gpu_hip_sample_locate(int dim, size_t num_points, const double* points, const uint64_t* keys, const int32_t* levels,
+                            int num_elements, int cells_per_axis, int32_t* cells, void* stream);
+int t8gpu_hip_sample_gather_f32(size_t num_points, const int32_t* cells, int num_planes, T8gpuSamplePlanes_f32 planes, double fill,
+                                double* out, void* stream);
+int t8gpu_hip_sample_gather_f64(size_t num_points, const int32_t* cells, int num_planes, T8gpuSamplePlanes_f64 planes, double fill,
+                                double* out, void* stream);
+int t8gpu_hip_sample_grid_f32(int dim, T8gpuSampleGrid grid, const uint64_t* keys, const int32_t* levels, int num_elements,
+                              int cells_per_axis, int num_planes, T8gpuSamplePlanes_f32 planes, double fill, double* out,
+                              int32_t* cells, void* stream);
+int t8gpu_hip_sample_grid_f64(int dim, T8gpuSampleGrid grid, const uint64_t* keys, const int32_t* levels, int num_elements,
+                              int cells_per_axis, int num_planes, T8gpuSamplePlanes_f64 planes, double fill, double* out,
+                              int32_t* cells, void* stream);
+int t8gpu_hip_sample_uniform_f32(int dim, int level, const uint64_t* keys, const int32_t* levels, int num_elements,
+                                 int cells_per_axis, int num_planes, T8gpuSamplePlanes_f32 planes, double fill, double* sums,
+                                 double* weights, void* stream);
+int t8gpu_hip_sample_uniform_f64(int dim, int level, const uint64_t* keys, const int32_t* levels, int num_elements,
+                                 int cells_per_axis, int num_planes, T8gpuSamplePlanes_f64 planes, double fill, double* sums,
+                                 double* weights, void* stream);
+
 /* ---- scale-free refinement indicator (csrc/hip/indicator.hip) ------------------------------
  * Loehner's estimator without cross terms, per axis, with a noise filter and a boundary closure. For cell c (an element, or a
  * subcell of a Subgrid block) and a scalar q, over the INTERIOR (sub-)faces s of c -- o the cell across, n_s the unit normal

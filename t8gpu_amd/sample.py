@@ -1,0 +1,290 @@
+"""Sampling of cell data on Cartesian forests (csrc/hip/sample.hip, include/t8gpu_hip.h: t8gpu_hip_sample_*):
+probe points, image grids and slices, conservative resampling onto a uniform level. Piecewise-constant finite-volume values
+cast to double, no interpolation, no atomics; results are bitwise defined.
+
+The geometry is one array of Morton keys. With D = DEPTH = 20 the integer coordinate of x in [0, 1) is floor(x 2^D), the key
+of a point the bit-interleave of its integer coordinates (x in the lowest bit), the key of an element that of its lower
+corner. In storage order the keys of a SynthMesh partition ascend strictly and are contiguous, key[i + 1] = key[i] +
+2^(dim (D - level[i])), so the cell of a point is upper_bound(keys, key(point)) - 1 plus one containment check, and the
+leaves inside a dyadic pixel are one contiguous index range. `morton_keys` and `host_locate` are numpy and need no GPU;
+`Sampler` is what `_Solver.locate / sample_points / sample_grid / resample_uniform` forward to.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import fields
+from .synth import SynthMesh
+
+DEPTH = 20                      # T8GPU_SAMPLE_DEPTH
+MAX_PLANES = 16                 # T8GPU_SAMPLE_PLANES: planes of one launch
+# name -> (first plane of a step's five, planes): the conserved names; the derived ones are fields.FIELDS
+STATE = {"density": (0, 1), "momentum": (1, 3), "energy": (4, 1)}
+NAMES = tuple(STATE) + tuple(fields.FIELDS)
+
+
+class SamplePlanes(C.Structure):
+    """T8gpuSamplePlanes_f32 / _f64: plane k is read from q[k] (the state's float type) or, q[k] NULL, from d[k] (doubles)"""
+    _fields_ = [("q", C.c_void_p * MAX_PLANES), ("d", C.c_void_p * MAX_PLANES)]
+
+
+class SampleGrid(C.Structure):
+    """T8gpuSampleGrid"""
+    _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("n", C.c_int32 * 3), ("pad", C.c_int32)]
+
+
+def check_names(names):
+    """`names` (one name or several) as a list without repeats; an unknown name raises ValueError listing the valid ones"""
+    names = [names] if isinstance(names, str) else list(names)
+    for name in names:
+        if name not in NAMES:
+            raise ValueError(f"unknown field {name!r}: one of {', '.join(NAMES)}")
+    return list(dict.fromkeys(names))
+
+
+def plane_count(name):
+    return (STATE.get(name) or fields.FIELDS[name])[1]
+
+
+def _spread(v, dim):
+    """bit b of v (uint64, below 2^21) to bit dim * b: the constant-step "magic bits" """
+    x = v.astype(np.uint64)                  # (a copy: the steps below work in place, with one scratch array)
+    tmp = np.empty_like(x)
+    if dim == 2:
+        steps = ((16, 0x0000FFFF0000FFFF), (8, 0x00FF00FF00FF00FF), (4, 0x0F0F0F0F0F0F0F0F), (2, 0x3333333333333333),
+                 (1, 0x5555555555555555))
+    else:
+        steps = ((32, 0x001F00000000FFFF), (16, 0x001F0000FF0000FF), (8, 0x100F00F00F00F00F), (4, 0x10C30C30C30C30C3),
+                 (2, 0x1249249249249249))
+    for shift, mask in steps:                # x = (x | (x << shift)) & mask
+        np.left_shift(x, np.uint64(shift), out=tmp)
+        np.bitwise_or(x, tmp, out=x)
+        np.bitwise_and(x, np.uint64(mask), out=x)
+    return x
+
+
+def interleave(coords, dim):
+    """keys of integer coordinates [M, >= dim] (each below 2^DEPTH): x in the lowest bit"""
+    key = _spread(coords[:, 0], dim)
+    for a in range(1, dim):
+        s = _spread(coords[:, a], dim)
+        np.left_shift(s, np.uint64(a), out=s)
+        key |= s
+    return key
+
+
+def check_partition(part, subgrid=None):
+    """(dim, cells per block axis) of a partition the sampler takes: a SynthMesh partition (TypeError otherwise: the curved
+    meshes of unstructured.py have no keys) with its owned levels within DEPTH (Subgrid: level + 2; ValueError otherwise)
+    and fewer than 2^31 owned cells (ValueError)."""
+    if not isinstance(getattr(part, "mesh", None), SynthMesh):
+        raise TypeError(f"sampling needs a Cartesian SynthMesh partition, not one of {type(getattr(part, 'mesh', None)).__name__}")
+    sub = 4 if (part.subgrid if subgrid is None else subgrid) else 1
+    dim = part.mesh.dim
+    top = int(part.levels[:part.N].max()) + (2 if sub == 4 else 0) if part.N else 0
+    if top > DEPTH:
+        raise ValueError(f"cell level {top} is above the sampling depth {DEPTH}")
+    if part.N * sub ** dim >= 2 ** 31:
+        raise ValueError(f"{part.N * sub ** dim} owned cells: the cell index is an int32")
+    return dim, sub
+
+
+def morton_keys(part):
+    """uint64[N]: the key of every owned element's anchor, floor((centre - 2^-(level + 1)) 2^DEPTH) per axis, interleaved"""
+    dim, _ = check_partition(part, subgrid=False)
+    half = np.ldexp(0.5, DEPTH - part.levels[:part.N])              # 2^-(level + 1) 2^DEPTH; products and differences are exact
+    anchor = np.floor(part.centres[:part.N, :dim] * 2.0 ** DEPTH - half[:, None])
+    return interleave(anchor.astype(np.uint64), dim)
+
+
+def host_locate(part, points, subgrid=None, keys=None):
+    """int32[M]: the storage index among the owned cells of the cell that holds each of points[M, dim], by the half-open rule
+    lo <= x < hi; -1 for a point outside [0, 1)^dim, NaN or infinite, or in no owned element. subgrid (default: the
+    partition's): cells are the 4^dim subcells of a block, index e S + i + 4 j (+ 16 k). The definition the device
+    kernels follow, in numpy."""
+    dim, sub = check_partition(part, subgrid)
+    pts = np.asarray(points, np.float64).reshape(-1, dim)
+    out = np.full(pts.shape[0], -1, np.int32)
+    if part.N == 0 or pts.shape[0] == 0:
+        return out
+    keys = morton_keys(part) if keys is None else keys
+    ok = np.all((pts >= 0.0) & (pts < 1.0), axis=1)                 # (before any conversion: NaN compares false)
+    idx = np.floor(pts[ok] * 2.0 ** DEPTH).astype(np.uint64)
+    key = interleave(idx, dim)
+    e = np.searchsorted(keys, key, side="right").astype(np.int64) - 1
+    lev = part.levels[:part.N].astype(np.int64)
+    ec = np.maximum(e, 0)
+    held = (e >= 0) & (key - keys[ec] < (np.uint64(1) << (dim * (DEPTH - lev[ec])).astype(np.uint64)))
+    cell = ec.copy()
+    if sub == 4:
+        sh = (DEPTH - lev[ec] - 2).astype(np.uint64)
+        cell = ec * 4 ** dim
+        for a in range(dim):
+            cell += (((idx[:, a] >> sh) & np.uint64(3)).astype(np.int64)) << (2 * a)
+    out[ok] = np.where(held, cell, -1).astype(np.int32)
+    return out
+
+
+class Sampler:
+    """Keys and levels of a solver's owned elements on the device, built and uploaded once, and the sampling calls on them.
+    Made on first use by `sampler(solver)` and kept on the solver (a solver's mesh never changes; an adapt makes a new
+    solver). Every call is enqueued on `stream` (default: the current stream) without a host sync; a rank of a partitioned
+    run samples its owned cells only and returns cell -1 / `fill` / weight 0 for the rest."""
+
+    def __init__(self, solver):
+        import torch
+        from . import hip
+        self.solver, part = solver, solver.part
+        self.dim, self.sub = check_partition(part, hasattr(solver, "S"))
+        self.N = part.N
+        keys = morton_keys(part)
+        if keys.size == 0:
+            keys = np.zeros(1, np.uint64)                           # (owns nothing: a valid pointer all the same)
+        levels = np.ascontiguousarray(part.levels[:max(1, part.N)], np.int32)
+        self.keys = torch.from_numpy(keys.view(np.int64)).cuda()
+        self.levels = torch.from_numpy(levels).cuda()
+        self._hip = hip
+
+    # -- arguments -------------------------------------------------------------------------------------------------
+    def _forest(self):
+        return self._hip.ptr(self.keys), self._hip.ptr(self.levels), self.N, self.sub
+
+    def _points(self, points):
+        import torch
+        if isinstance(points, torch.Tensor):
+            p = points.to(device="cuda", dtype=torch.float64)
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(points, np.float64)).cuda()
+        if p.ndim != 2 or p.shape[1] != self.dim:
+            raise ValueError(f"points must have shape [M, {self.dim}], got {tuple(p.shape)}")
+        return p.contiguous()
+
+    def _sources(self, names, step, stream, halo):
+        """(names, SamplePlanes, number of planes, what to keep alive): state planes by pointer, derived names through one
+        derived_fields pass over the owned cells"""
+        names = check_names(names)
+        total = sum(plane_count(n) for n in names)
+        if total > MAX_PLANES:
+            raise ValueError(f"{total} planes asked for, one call takes {MAX_PLANES}")
+        s = self.solver.next if step is None else step
+        derived = [n for n in names if n in fields.FIELDS]
+        got = self.solver.derived_fields(derived, s, stream, halo) if derived else {}
+        src, k = SamplePlanes(), 0
+        for name in names:
+            if name in STATE:
+                first, count = STATE[name]
+                for j in range(count):
+                    src.q[k + j] = self.solver.planes[5 * s + first + j].data_ptr()
+            else:
+                count = fields.FIELDS[name][1]
+                planes = got[name].reshape(count, -1)
+                for j in range(count):
+                    src.d[k + j] = planes[j].data_ptr()
+            k += count
+        return names, src, total, got
+
+    @staticmethod
+    def _split(names, out, shape):
+        """{name: view of out[planes, ...]} in the shape of one plane, [3, ...] for a vector"""
+        res, k = {}, 0
+        for name in names:
+            count = plane_count(name)
+            res[name] = out[k].view(shape) if count == 1 else out[k:k + count].view((count,) + tuple(shape))
+            k += count
+        return res
+
+    def _stream(self, stream):
+        import torch
+        return torch.cuda.current_stream() if stream is None else stream
+
+    # -- the calls ---------------------------------------------------------------------------------------------------
+    def _locate(self, p, stream):
+        import torch
+        cells = torch.empty(p.shape[0], dtype=torch.int32, device="cuda")
+        if p.shape[0]:
+            lib = self._hip.lib()
+            lib.t8gpu_hip_sample_locate.restype = C.c_int
+            self._hip.check(lib.t8gpu_hip_sample_locate(self.dim, C.c_size_t(p.shape[0]), self._hip.ptr(p), *self._forest(),
+                                                        self._hip.ptr(cells), self._hip.stream_ptr(stream)))
+        return cells
+
+    def locate(self, points, stream=None):
+        import torch
+        stream = self._stream(stream)
+        with torch.cuda.stream(stream):
+            return self._locate(self._points(points), stream)
+
+    def sample_points(self, points, names, step=None, stream=None, halo=None, fill=math.nan):
+        import torch
+        stream = self._stream(stream)
+        with torch.cuda.stream(stream):
+            p = self._points(points)
+            m = p.shape[0]
+            names = check_names(names)
+            if m == 0:
+                return self._split(names, torch.empty((sum(map(plane_count, names)), 0), dtype=torch.float64, device="cuda"), (0,))
+            names, src, total, keep = self._sources(names, step, stream, halo)
+            cells = self._locate(p, stream)
+            out = torch.empty((total, m), dtype=torch.float64, device="cuda")
+            self._hip.call("t8gpu_hip_sample_gather", self.solver.dtype, C.c_size_t(m), self._hip.ptr(cells), total, src,
+                           C.c_double(fill), self._hip.ptr(out), self._hip.stream_ptr(stream))
+            del keep
+        return self._split(names, out, (m,))
+
+    def sample_grid(self, names, shape, lo=None, hi=None, step=None, stream=None, halo=None, fill=math.nan, cells=False):
+        import torch
+        dim = self.dim
+        shape = tuple(int(n) for n in shape)
+        lo = (0.0,) * dim if lo is None else tuple(float(x) for x in lo)
+        hi = (1.0,) * dim if hi is None else tuple(float(x) for x in hi)
+        if not (len(shape) == len(lo) == len(hi) == dim):
+            raise ValueError(f"shape, lo and hi need {dim} entries each")
+        if any(n < 0 for n in shape):
+            raise ValueError(f"negative grid extent in {shape}")
+        names = check_names(names)
+        image, pixels = shape[::-1], math.prod(shape)
+        stream = self._stream(stream)
+        with torch.cuda.stream(stream):
+            cell = torch.empty(image, dtype=torch.int32, device="cuda") if cells else None
+            if pixels == 0:
+                res = self._split(names, torch.empty((sum(map(plane_count, names)), 0), dtype=torch.float64, device="cuda"), image)
+            else:
+                names, src, total, keep = self._sources(names, step, stream, halo)
+                g = SampleGrid()
+                for a in range(dim):
+                    g.lo[a], g.hi[a], g.n[a] = lo[a], hi[a], shape[a]
+                out = torch.empty((total, pixels), dtype=torch.float64, device="cuda")
+                self._hip.call("t8gpu_hip_sample_grid", self.solver.dtype, dim, g, *self._forest(), total, src, C.c_double(fill),
+                               self._hip.ptr(out), self._hip.ptr(cell), self._hip.stream_ptr(stream))
+                del keep
+                res = self._split(names, out, image)
+        if cells:
+            res["cell"] = cell
+        return res
+
+    def resample_uniform(self, names, level, step=None, stream=None, halo=None, fill=math.nan, partial=False):
+        import torch
+        level = int(level)
+        if not 0 <= level <= DEPTH:
+            raise ValueError(f"level must lie in 0..{DEPTH}, got {level}")
+        image = (1 << level,) * self.dim
+        stream = self._stream(stream)
+        with torch.cuda.stream(stream):
+            names, src, total, keep = self._sources(names, step, stream, halo)
+            if total == 0:
+                raise ValueError("resample_uniform needs at least one name")
+            out = torch.empty((total, 1 << (self.dim * level)), dtype=torch.float64, device="cuda")
+            weights = torch.empty(image, dtype=torch.float64, device="cuda") if partial else None
+            self._hip.call("t8gpu_hip_sample_uniform", self.solver.dtype, self.dim, level, *self._forest(), total, src,
+                           C.c_double(fill), self._hip.ptr(out), self._hip.ptr(weights), self._hip.stream_ptr(stream))
+            del keep
+        res = self._split(names, out, image)
+        return (res, weights) if partial else res
+
+
+def sampler(solver):
+    """the solver's Sampler: built on the first sampling call, then kept (as fields._csr keeps the CSR)"""
+    if getattr(solver, "_sampler", None) is None:
+        solver._sampler = Sampler(solver)
+    return solver._sampler

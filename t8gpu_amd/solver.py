@@ -319,6 +319,36 @@ class _Solver:
         from . import fields
         return fields.derived_fields(self, names, step, stream, halo)
 
+    # -- sampling on Cartesian forests (sample.py): cell values cast to double, never interpolated ----------------
+    def locate(self, points, stream=None):
+        """int32 device tensor [M]: the storage index among the owned cells of the cell that holds each of points[M, dim] (a host
+        or device array, taken to float64) under the half-open rule lo <= x < hi; -1 for a point outside [0, 1)^dim, NaN or
+        infinite, or owned by another rank. Enqueued on `stream`, no sync. A mesh that is no SynthMesh raises TypeError."""
+        from . import sample
+        return sample.sampler(self).locate(points, stream)
+
+    def sample_points(self, points, names, step=None, stream=None, halo=None, fill=float("nan")):
+        """{name: float64 device tensor [M] or [3, M]} of `names` -- "density", "momentum", "energy" of state(step) and every name
+        of derived_fields -- at points[M, dim]: the value of the holding cell, `fill` where locate gives -1. Derived names cost
+        one derived_fields pass over the owned cells first, with `halo` handed on."""
+        from . import sample
+        return sample.sampler(self).sample_points(points, names, step, stream, halo, fill)
+
+    def sample_grid(self, names, shape, lo=None, hi=None, step=None, stream=None, halo=None, fill=float("nan"), cells=False):
+        """sample_points on the pixel centres lo + (i + 0.5) (hi - lo) / n of a grid of shape (nx, ny[, nz]) over the box lo..hi
+        (default: the whole domain), in one fused launch that forms no point array: tensors [ny, nx], [nz, ny, nx] or [3, ...],
+        x fastest. An axis with lo == hi is a slice plane at that coordinate. cells=True adds "cell": the int32 indices."""
+        from . import sample
+        return sample.sampler(self).sample_grid(names, shape, lo, hi, step, stream, halo, fill, cells)
+
+    def resample_uniform(self, names, level, step=None, stream=None, halo=None, fill=float("nan"), partial=False):
+        """Conservative resampling onto the 2^level pixels per axis of a uniform level, shapes as sample_grid: per pixel
+        sum(w q) / sum(w) over the owned cells that meet it, w = 2^(-dim level of the smaller of pixel and cell), summed in
+        ascending storage order in double; `fill` where no owned cell meets the pixel. partial=True: ({name: sums}, weights)
+        instead, for ranks to add up and divide once."""
+        from . import sample
+        return sample.sampler(self).resample_uniform(names, level, step, stream, halo, fill, partial)
+
     def cfl_timestep(self, cfl=0.7, step=None, dist=None):
         """cfl / max over the cells of (|v| + c) / h, h = vol^(1/dim), from the state itself: needs no stage to have run (a new
         solver, a solver fresh from an adapt). On Cartesian cells h is the edge; on curved cells it is cbrt(volume), not an
