@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from t8gpu_amd import amr, hip, vtk  # noqa: E402
+from t8gpu_amd import amr, boundary, hip, vtk  # noqa: E402
 from t8gpu_amd.solver import PlainSolver  # noqa: E402
 from t8gpu_amd.synth import SynthMesh  # noqa: E402
 
@@ -76,6 +76,9 @@ def main():
     ap.add_argument("--probes", action="store_true",
                     help="record pressure at three fixed points every step, sampled on the device (sample_points), and save the "
                          "series as acoustic_pulse_probes.npy in --out (default: the working directory): rows t, p_0, p_1, p_2")
+    ap.add_argument("--budget", action="store_true",
+                    help="print, every 50 steps and at the end, the change of mass and energy (monitor()) against the "
+                         "boundary flux integrated in time on the device (boundary.Budget), and their difference")
     args = ap.parse_args()
     if args.toy:
         args.min_level, args.max_level, args.t_end, args.adapt_every = 3, 5, 0.05, 5
@@ -100,6 +103,7 @@ def main():
         ic = torch.from_numpy(initial_state(solver.part)).to(solver.dtype).cuda()
         solver.planes[5 * solver.next:5 * solver.next + 5] = ic
     solver.use_native_stepper()
+    budget = boundary.Budget(solver) if args.budget else None
     t, it, cells, t_iter = 0.0, 0, 0, 0.0
     probes = torch.tensor(PROBES, dtype=torch.float64, device="cuda") if args.probes else None
     series = []            # per step [t, p_0, p_1, p_2] on the device: read back once at the end
@@ -115,6 +119,8 @@ def main():
         solver.iterate(dt)
         torch.cuda.synchronize()
         t_iter += time.perf_counter() - t0
+        if budget is not None:
+            budget.add_step(solver, dt)
         t += dt
         it += 1
         cells += solver.N
@@ -123,6 +129,10 @@ def main():
         if it % 50 == 0:
             print(f"it {it:5d}  t {t:.4f}  elements {solver.N:8d}  finest level {solver.part.mesh.finest_level}  dt {dt:.3e}",
                   flush=True)
+            if budget is not None:
+                print(budget.line(solver), flush=True)
+    if budget is not None and it % 50 != 0:
+        print(budget.line(solver))
     assert bool(torch.isfinite(solver.state()).all())
     residual = float(np.abs(pressure(solver) - AMBIENT[1]).max())
     print(f"t = {t:.4f} after {it} steps, {solver.N} elements; {cells / t_iter / 1e6:.1f} M cell-updates/s (host-synchronised)")

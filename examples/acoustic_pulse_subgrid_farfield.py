@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from t8gpu_amd import amr, hip, vtk  # noqa: E402
+from t8gpu_amd import amr, boundary, hip, vtk  # noqa: E402
 from t8gpu_amd.solver import SubgridSolver  # noqa: E402
 from t8gpu_amd.synth import SynthMesh  # noqa: E402
 
@@ -83,6 +83,9 @@ def main():
                     help="ambient pressure at t_end: the far-field state is updated before every step (set_inflow_states)")
     ap.add_argument("--out", default=None, help="directory of the .vtu written at the end (density, energy, momentum, pressure, dilatation)")
     ap.add_argument("--toy", action="store_true", help="block levels 2-3, t_end 0.05 (a quick check)")
+    ap.add_argument("--budget", action="store_true",
+                    help="print, every 50 steps and at the end, the change of mass and energy (monitor()) against the "
+                         "boundary flux integrated in time on the device (boundary.Budget), and their difference")
     args = ap.parse_args()
     if args.toy:
         args.min_level, args.max_level, args.t_end, args.adapt_every = 2, 3, 0.05, 5
@@ -107,6 +110,7 @@ def main():
         ic = torch.from_numpy(initial_state(solver.part)).to(solver.dtype).cuda()
         solver.planes[5 * solver.next:5 * solver.next + 5] = ic
     solver.use_native_stepper()
+    budget = boundary.Budget(solver) if args.budget else None
     t, it, cells, t_iter = 0.0, 0, 0, 0.0
     while t < args.t_end - 1e-12:
         if it % args.adapt_every == 0:
@@ -122,11 +126,17 @@ def main():
         solver.iterate(dt)
         torch.cuda.synchronize()
         t_iter += time.perf_counter() - t0
+        if budget is not None:
+            budget.add_step(solver, dt)
         t += dt
         it += 1
         cells += solver.owned_cells
         if it % 50 == 0:
             print(f"it {it:5d}  t {t:.4f}  blocks {solver.N:8d}  finest level {solver.part.mesh.finest_level}  dt {dt:.3e}", flush=True)
+            if budget is not None:
+                print(budget.line(solver), flush=True)
+    if budget is not None and it % 50 != 0:
+        print(budget.line(solver))
     assert bool(torch.isfinite(solver.state()).all())
     p_inf = 0.4 * float(solver.inflow_states[0, 4])
     p = pressure(solver)

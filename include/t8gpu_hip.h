@@ -553,6 +553,61 @@ int t8gpu_hip_state_monitor_f32(size_t num_cells, int cells_per_element, int dim
 int t8gpu_hip_state_monitor_f64(size_t num_cells, int cells_per_element, int dim, T8gpuVars_f64 state, const double* volume,
                                 void* workspace, double* result /* [16] */, void* stream);
 
+/* ---- boundary budgets: the boundary faces' fluxes and wall pressure forces, summed per face group ------
+ * The other half of the monitor's conservation check on a domain with open sides: change of the integral + dt * boundary
+ * flux = 0, stage by stage (the reference has nothing of the kind). `state` is read through the arrays the
+ * boundary kernels above take (face_neighbors, face_normals, face_surfaces with the boundary entries after the num_faces
+ * interior ones; boundary_kinds, NULL = every face a wall; inflow_table, NULL allowed when no face is an inflow or
+ * far-field face). The caller labels every boundary face with a group < num_groups <= T8GPU_BOUNDARY_GROUPS_MAX and hands
+ * the faces over sorted by group: face_order[B] (DEVICE, int32: indices 0 .. B - 1 of the boundary faces, a stable sort by
+ * group) and group_offsets[num_groups + 1] (HOST, int32: the first position of every group in face_order, [0] = 0,
+ * [num_groups] = B; read during the call). result[num_groups][T8GPU_BOUNDARY_SLOTS] (DEVICE, doubles), every slot a sum over
+ * the faces of the group (Subgrid blocks: over the sub-faces, each with the area face_surfaces / sub-faces):
+ *   0      A
+ *   1-5    A * g_k   g = the scheme's numerical flux through the face along the OUTWARD normal, in xyz (rho, mx, my, mz, E):
+ *                    the vector t8gpu_hip_flux_boundary_bc_* / t8gpu_hip_subgrid_boundary_far_* subtract from the inside cell,
+ *                    from the same routines in float_type; outside state by kind (wall: mirrored; outflow: the inside state;
+ *                    inflow k: row k; far field k: the characteristic state against row k)
+ *   6-8    A * p * n   p = 0.4 (E - |m|^2 / (2 rho)) of the inside cell
+ *   9      A * p
+ *   10     A * max(g_0, 0)   mass leaving; mass entering is slot 10 - slot 1
+ *   11     number of faces / sub-faces
+ *   12     number of them whose flux has a non-finite component; these add nothing to slots 1-10
+ *   13-15  0 (reserved)
+ * Products with A and all accumulation in double for both float types. Ranks combine blocks with one SUM. A group without
+ * faces, and num_boundary_faces = 0, give zeros. accumulate = 0: result is overwritten. accumulate != 0: slots 0-10 become
+ * result + weight * value (one thread per slot; a loop integrates in time on the device), slots 11-15 are overwritten.
+ * Two launches on `stream` (one workgroup per contiguous chunk of one group's faces, then one workgroup per group folding
+ * the chunk partials in a fixed tree), no atomics: the same data gives the same bits. Nothing is allocated, nothing waits.
+ * workspace = t8gpu_hip_boundary_fluxes_workspace_bytes(B, num_groups) device bytes. hipErrorInvalidValue for a flux_kind
+ * outside 0..2, normal_dim / rank outside {2, 3}, num_groups outside 1..32, offsets that do not run from 0 to B in
+ * ascending order, or a null result (with B > 0: a null workspace, face_order or face array). */
+#define T8GPU_BOUNDARY_SLOTS 16
+#define T8GPU_BOUNDARY_GROUPS_MAX 32
+size_t t8gpu_hip_boundary_fluxes_workspace_bytes(int num_boundary_faces, int num_groups);
+int t8gpu_hip_boundary_fluxes_f32(int flux_kind, int num_faces, int num_boundary_faces, int normal_dim, const int32_t* face_neighbors,
+                                  const uint8_t* boundary_kinds, const float* inflow_table, const float* face_normals,
+                                  const float* face_surfaces, T8gpuVars_f32 state, int num_groups, const int32_t* face_order,
+                                  const int32_t* group_offsets, void* workspace, double* result /* [num_groups][16] */,
+                                  int accumulate, double weight, void* stream);
+int t8gpu_hip_boundary_fluxes_f64(int flux_kind, int num_faces, int num_boundary_faces, int normal_dim, const int32_t* face_neighbors,
+                                  const uint8_t* boundary_kinds, const double* inflow_table, const double* face_normals,
+                                  const double* face_surfaces, T8gpuVars_f64 state, int num_groups, const int32_t* face_order,
+                                  const int32_t* group_offsets, void* workspace, double* result /* [num_groups][16] */,
+                                  int accumulate, double weight, void* stream);
+/* Subgrid<4,4> (rank 2) and Subgrid<4,4,4> (rank 3) blocks: one lane per sub-face with the indexing of
+ * t8gpu_hip_subgrid_boundary_far_* (the inside subcell of the sub-face map, the block face's outward normal). */
+int t8gpu_hip_subgrid_boundary_fluxes_f32(int flux_kind, int rank, int num_faces, int num_boundary_faces,
+                                          const int32_t* face_neighbors, const uint8_t* boundary_kinds, const float* inflow_table,
+                                          const float* face_normals, const float* face_surfaces, T8gpuVars_f32 state, int num_groups,
+                                          const int32_t* face_order, const int32_t* group_offsets, void* workspace,
+                                          double* result /* [num_groups][16] */, int accumulate, double weight, void* stream);
+int t8gpu_hip_subgrid_boundary_fluxes_f64(int flux_kind, int rank, int num_faces, int num_boundary_faces,
+                                          const int32_t* face_neighbors, const uint8_t* boundary_kinds, const double* inflow_table,
+                                          const double* face_normals, const double* face_surfaces, T8gpuVars_f64 state, int num_groups,
+                                          const int32_t* face_order, const int32_t* group_offsets, void* workspace,
+                                          double* result /* [num_groups][16] */, int accumulate, double weight, void* stream);
+
 /* ---- derived output fields: pressure, velocity, Mach, entropy, vorticity, dilatation, schlieren ---------
  * What a run writes to look at itself, formed on the device from the five planes of one step (csrc/hip/fields.hip; the
  * reference writes conserved variables only). All arithmetic in double whatever float_type is, gamma = 1.4,

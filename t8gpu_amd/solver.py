@@ -311,6 +311,33 @@ class _Solver:
                 block[list(slots)] = t.cpu().numpy()[list(slots)]
         return Monitor(block)
 
+    # -- boundary budgets (boundary.py): what crosses the boundary, per group of boundary faces ----------------
+    def boundary_fluxes_device(self, step=None, groups=None, stream=None, out=None, weight=None):
+        """One pass of t8gpu_hip_boundary_fluxes_* over the boundary faces of state(step), enqueued on `stream` with no copy and
+        no sync: the float64 device block [num_groups, 16] of this grouping (slots: boundary.BoundaryFluxes, include/t8gpu_hip.h),
+        overwritten by the next call. groups: None = by boundary kind (group index = kind code), "side" (boundary.side_groups)
+        or a uint8 array [B] with values < 32; anything else raises ValueError. The sorted face list, the offsets and the
+        workspace are made on first use per grouping and kept. `out` (a block of the same shape) receives the result instead;
+        with `weight` as well the call accumulates: out[:, 0:11] += weight * value, slots 11-12 those of this call -- a loop
+        integrates in time on the device. The inflow table is read where set_inflow_states refills it: nothing is rebuilt."""
+        from . import boundary
+        return boundary.boundary_fluxes_device(self, step, groups, stream, out, weight)
+
+    def boundary_fluxes(self, step=None, groups=None, stream=None, dist=None):
+        """The boundary.BoundaryFluxes of state(step): one pass, one pinned copy to the host, one sync. `dist` all-reduces the
+        block with SUM (every slot is a sum), on the GPU for nccl and on the CPU otherwise."""
+        from . import boundary
+        return boundary.boundary_fluxes(self, step, groups, stream, dist)
+
+    def boundary_step_fluxes(self, delta_t, groups=None, stream=None, dist=None):
+        """The boundary flux integrated over the LAST step taken with `delta_t` (iterate, or the last step of iterate_steps), as
+        a boundary.BoundaryFluxes whose slots 0-10 carry the time integral: three accumulating passes over the step's source
+        states prev, STEP1 and STEP2, which the planes still hold, with the weights of the stage formulas
+        (boundary.step_weights). In a closed budget integrals(next) - integrals(prev) = -(flux summed over the
+        groups) to rounding."""
+        from . import boundary
+        return boundary.boundary_step_fluxes(self, delta_t, groups, stream, dist)
+
     def derived_fields(self, names, step=None, stream=None, halo=None):
         """{name: float64 device tensor} of the derived output fields `names` -- "pressure", "velocity", "mach", "entropy",
         "vorticity", "dilatation", "schlieren" (fields.py) -- for the owned cells of state(step) in storage

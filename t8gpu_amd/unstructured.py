@@ -259,6 +259,9 @@ class UnstructuredPartition:
         # boundary_kinds[B]: the mesh's kinds of this rank's boundary faces (None: the mesh has no sides -- every face a wall)
         mk = getattr(mesh, "boundary_kinds", None)
         self.boundary_kinds = None if mk is None else np.ascontiguousarray(mk[keep_b])
+        # boundary_side[B]: the side of the reference cube (0 -x .. 5 +z) of this rank's boundary faces (boundary.side_groups)
+        ms = getattr(mesh, "boundary_side", None)
+        self.boundary_side = None if ms is None else np.ascontiguousarray(ms[keep_b])
         A = np.concatenate([mesh.area_vec[:F][keep_i], mesh.area_vec[F:][keep_b]])
         area = np.linalg.norm(A, axis=1)
         self.areas = area
