@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import _meshes as M
 import _oracle as O
 from _gpu import perturbed_state
 from t8gpu_amd.plan import HostPlainPlan
@@ -190,11 +191,19 @@ def order_of(plan):
                                                      (dict(dim=3, base_level=5, max_level=5, periodic=False), 2, True),
                                                      # every block next to a periodic wrap; walls, coarser neighbours and a partition cut
                                                      (dict(dim=3, base_level=4, max_level=4), 1, True),
-                                                     (dict(dim=3, base_level=3, max_level=5, band=0.12, periodic=False), 2, True)])
+                                                     (dict(dim=3, base_level=3, max_level=5, band=0.12, periodic=False), 2, True),
+                                                     # the shapes of tests/_meshes.py (name, periodic): level interfaces across every
+                                                     # axis, patches with coarser elements across +x as well, cuts through them
+                                                     (("box2", True), 1, True), (("box2", True), 3, True),
+                                                     (("box3", True), 1, True), (("box3", True), 3, True),
+                                                     (("corner3", False), 1, True)])
 def test_plan_reproduces_the_face_loop(mesh_args, ranks, patches):
-    mesh = SynthMesh(**mesh_args)
-    irregular_expected = True if (mesh_args["dim"] == 3 and patches) else (False if patches else None)
-    n_patches = 0
+    named = isinstance(mesh_args, tuple)
+    mesh = M.shape(*mesh_args) if named else SynthMesh(**mesh_args)
+    irregular_expected = True if (mesh.dim == 3 and patches) else (False if patches else None)
+    if named and mesh.dim == 3 and ranks > 1:
+        irregular_expected = None        # (a rank of these small meshes may hold regular patches only: asked of the ranks together)
+    n_patches = n_irregular = 0
     for rk in range(ranks):
         part = mesh.partition(rk, ranks)
         plan = HostPlainPlan.from_partition(part, tmax=64, fcap=150, patches=patches)
@@ -228,6 +237,7 @@ def test_plan_reproduces_the_face_loop(mesh_args, ranks, patches):
         assert (np.diff(plan.elem_off)[plan.tile_patch] == 256).all()
         assert (np.diff(plan.face_off)[plan.tile_patch & ~irregular] == 0).all() and (np.diff(plan.face_off)[irregular] == 512).all()
         assert irregular.sum() == sum(plan.n_irregular_class) and (irregular.sum() > 0) == (irregular_expected is True or irregular.sum() > 0)
+        n_irregular += int(irregular.sum())
         if irregular_expected is not None:
             assert (irregular.sum() > 0) == irregular_expected
         assert np.array_equal(np.sort(rep), np.arange(part.F + part.B))      # every face has exactly one reporter
@@ -244,6 +254,9 @@ def test_plan_reproduces_the_face_loop(mesh_args, ranks, patches):
             irr = irregular[order[a:b]][:plan.n_patch_class[c]]
             assert not irr[:plan.n_patch_class[c] - plan.n_irregular_class[c]].any() and irr[plan.n_patch_class[c] - plan.n_irregular_class[c]:].all()
     assert (n_patches > 0) == patches
+    if named:
+        assert sum(M.hanging_by_axis(mesh.partition())[:-1]) > 0          # level interfaces the band meshes do not have
+        assert (n_irregular > 0) == (mesh.dim == 3)
 
 
 def test_plan_rejects_oversized_tiles():
