@@ -365,8 +365,8 @@ int t8gpu_hip_halo_exchange_f64(const T8gpuHalo* halo, T8gpuVars_f64 state, void
  * allocation (26 planes of `stride`, plane = step*5+var, volume = plane 25; memory_manager.h:460), prev /
  * next the step ids AFTER the caller's std::swap (solver.cu:76). Enqueues, per stage, the exchange and the
  * ghost-reading tiles on an internal second stream beside the interior tiles on `stream` (two lanes, each waiting
- * only for the other lane's PREVIOUS stage; the comm lane is enqueued by a host thread of the stepper's own --
- * T8GPU_STEPPER_THREADS=0: by the caller's thread; csrc/hip/stepper.hip) and returns; no host sync. Work queued on
+ * only for the other lane's PREVIOUS stage; the caller's thread enqueues both lanes, stage by stage;
+ * csrc/hip/stepper.hip, with the exchange itself in csrc/hip/transport.hip) and returns; no host sync. Work queued on
  * `stream` before the call is seen by it, work queued after the call sees its result. For plain 2D / tile plans
  * the ghost-reading tiles read the receive buffer and fill the send buffer themselves (T8gpuPlainPlan "ghost
  * window"): the ghost mirror slots [N, N+G) of the planes are then NOT refreshed by this driver -- code that reads

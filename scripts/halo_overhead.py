@@ -103,7 +103,7 @@ def main():
     print(f"projected strong-scaling speedup at {world} ranks if every rank behaves like this one: "
           f"{one / tb:.2f}x direct enqueue per step, {one / tc:.2f}x all steps in one call"
           f" (no exchange: {one / ta:.2f}x) against {one} ms/step on one GPU -- a PROJECTION from one GPU: no byte crosses xGMI here", flush=True)
-    del a, b                                        # (T8GPU_STEPPER_PROFILE=1: the steppers print their host-cost profile here)
+    del a, b
     import gc
     gc.collect()
     comm.destroy()

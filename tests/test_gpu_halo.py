@@ -274,19 +274,21 @@ def test_native_stepper_with_rccl_self_exchange_on_a_symmetric_problem(dtype, ca
     local = st[:, gidx].copy()
     local[:, half.N:] = np.nan                                            # ghosts must arrive through RCCL
     g = PlainSolver(half, dtype, mode="fused", state=local, plan_options=dict(tmax=min(caps[0], 256), fcap=caps[1], two_classes=classes == 2),
-                    capacity=half.N + half.G + 3)                        # (three extra ghost slots: see `fake` below)
+                    capacity=half.N + half.G + 4)                        # (four extra ghost slots: see `fake` below)
     if caps[0] == 4000:                                                   # no class information: the driver must cope
         g.plan.c.n_deep_tiles = 0
     hp = g.plan.host
     print("tiles C / B / A:", hp.n_deep, hp.n_interior - hp.n_deep, hp.ntiles - hp.n_interior)
     comm = native.NativeComm(0, 1, lambda b, src: b)
     # a second message to the same "peer": the first three send elements once more, received into three extra ghost slots
-    # nobody reads -- two messages per peer inside one RCCL group, and elements with two send slots (the driver's send_list)
+    # nobody reads -- two messages per peer inside one RCCL group, and elements with two send slots (the driver's send_list).
+    # A third message sends the first element a third time into one more spare slot: a run of send_list longer than two.
     extra = 3
-    fake = types.SimpleNamespace(N=half.N, G=half.G + extra, cells_per_element=1, peers=np.zeros(2, np.int32),
-                                 send_off=np.append(half.send_off, half.send_off[-1] + extra).astype(np.int32),
-                                 recv_off=np.append(half.recv_off, half.recv_off[-1] + extra).astype(np.int32),
-                                 send_idx=np.append(half.send_idx, half.send_idx[:extra]).astype(np.int32))
+    tails = [half.send_off[-1] + extra, half.send_off[-1] + extra + 1]
+    fake = types.SimpleNamespace(N=half.N, G=half.G + extra + 1, cells_per_element=1, peers=np.zeros(3, np.int32),
+                                 send_off=np.append(half.send_off, tails).astype(np.int32),
+                                 recv_off=np.append(half.recv_off, [half.recv_off[-1] + extra, half.recv_off[-1] + extra + 1]).astype(np.int32),
+                                 send_idx=np.concatenate([half.send_idx, half.send_idx[:extra], half.send_idx[:1]]).astype(np.int32))
     nh = native.NativeHalo(fake, dtype, comm)
     g.use_native_stepper(nh)
     dt = 0.1 * 2.0 ** -mesh.finest_level
@@ -309,6 +311,10 @@ def test_native_stepper_with_rccl_self_exchange_on_a_symmetric_problem(dtype, ca
     n0 = half.send_idx.size
     assert np.array_equal(sb[n0:n0 + extra], sb[:extra])
     assert np.array_equal(sb[:extra], got[:, half.send_idx[:extra]].T)
+    # ... and so does the third slot of the element that is sent three times
+    assert sb.shape[0] == n0 + extra + 1
+    assert np.array_equal(sb[n0 + extra], sb[0]) and np.array_equal(sb[n0 + extra], sb[n0])
+    assert np.array_equal(sb[n0 + extra], got[:, half.send_idx[0]])
     g.stepper = None
     comm.destroy()
 
