@@ -46,6 +46,11 @@ def main():
                     help="save N x N images of schlieren and density, sampled on the device (sample_grid), as .npy files beside the "
                          "VTK output (prefix --vtk, or kh): at the end, and every --image-every steps")
     ap.add_argument("--image-every", type=int, default=None, metavar="K")
+    ap.add_argument("--stats", action="store_true",
+                    help="time-averaged statistics on the device (solver.statistics()): accumulated every --stats-every steps, "
+                         "carried through every adapt; mean_density, mean_velocity, tke and pressure_rms go to the VTK output, a "
+                         "tke image beside the others with --image")
+    ap.add_argument("--stats-every", type=int, default=1, metavar="K", help="accumulate every K steps with weight K dt (default 1)")
     args = ap.parse_args()
     indicator, coarsen = None, None
     if args.indicator == "loehner":
@@ -68,12 +73,14 @@ def main():
         hostmem.use_pinned_uploads()   # ... and uploaded through one pinned staging buffer
     say = print if rank == 0 else (lambda *a, **k: None)
 
-    def adapt(s):
+    def adapt(s, carry=()):
         if world == 1:
-            return amr.adapt(s, args.threshold, args.min_level, args.max_level, indicator=indicator, coarsen_below=coarsen)[0]
+            return amr.adapt(s, args.threshold, args.min_level, args.max_level, indicator=indicator, coarsen_below=coarsen,
+                             carry=carry)[0]
         # refreshes the ghost slots of the current state itself (the indicator reads them), through the run's halo object
         return amr.adapt_partitioned(s, dist, host_staged=rehearsal, halo=halo_of.get(id(s)), threshold=args.threshold,
-                                     min_level=args.min_level, max_level=args.max_level, indicator=indicator, coarsen_below=coarsen)
+                                     min_level=args.min_level, max_level=args.max_level, indicator=indicator, coarsen_below=coarsen,
+                                     carry=carry)
 
     def total(x, op="sum"):
         if world == 1:
@@ -94,6 +101,13 @@ def main():
                 dist.all_reduce(image)
             if rank == 0:
                 np.save(f"{prefix}_{name}_{it:06d}.npy", image.cpu().numpy())
+        if stats is not None and stats.weight > 0:
+            image = stats.sample_grid(["tke"], (args.image, args.image), fill=0.0)["tke"]
+            if world > 1:
+                image = image.cpu() if rehearsal else image
+                dist.all_reduce(image)
+            if rank == 0:
+                np.save(f"{prefix}_tke_{it:06d}.npy", image.cpu().numpy())
         say(f"images at it {it}: {prefix}_{{schlieren,density}}_{it:06d}.npy", flush=True)
 
     mesh = SynthMesh(2, args.min_level, args.min_level)
@@ -109,6 +123,7 @@ def main():
     halo_of = {id(solver): halo}
     if world == 1:
         solver.use_native_stepper()
+    stats = solver.statistics() if args.stats else None      # running sums on the device; they follow the run through adapt
     mass0 = solver.monitor(dist=dist).integrals      # the state monitor: one device pass, one all-reduced block of 16 doubles
     t_iter = t_adapt = 0.0
     cells = 0
@@ -116,7 +131,7 @@ def main():
         if it % args.adapt_every == 0 and it > 0:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            solver = adapt(solver)
+            solver = adapt(solver, carry=(stats,) if stats is not None else ())
             say(f"adapt at it {it}: criteria sum {solver.last_adapt_criteria_sum:.12e}  elements {int(total(solver.N))}", flush=True)
             if world > 1:
                 halo = HaloExchange(solver.part, dtype, dist, stage_through_host=rehearsal)
@@ -135,6 +150,8 @@ def main():
         torch.cuda.synchronize()
         t_iter += time.perf_counter() - t0
         cells += solver.N
+        if stats is not None and (it + 1) % args.stats_every == 0:
+            stats.accumulate(args.stats_every * dt)              # the time the sample stands for: K steps of dt
         if args.image and args.image_every and (it + 1) % args.image_every == 0 and it + 1 < args.steps:
             save_images(solver, it + 1)
         if it % 100 == 0:
@@ -155,6 +172,9 @@ def main():
         fields += [vtk.get_host_derived_variable(solver, name, halo=halo) for name in ("pressure", "mach", "vorticity")]
         if indicator is not None:
             fields.append(vtk.get_host_indicator_variable(solver, indicator, halo=halo))
+        if stats is not None and stats.weight > 0:
+            fields += [vtk.get_host_statistics_variable(stats, name)
+                       for name in ("mean_density", "mean_velocity", "tke", "pressure_rms")]
         say("wrote", vtk.save_variables_to_vtk(solver, fields, args.vtk, dist=dist))
     say(f"iterate: {total(cells) / total(t_iter, 'max') / 1e6:.1f} M cell-updates/s (host-synchronised per step), "
         f"adapt: {t_adapt:.2f} s total, iterate: {t_iter:.2f} s total")

@@ -705,6 +705,42 @@ int t8gpu_hip_sample_uniform_f64(int dim, int level, const uint64_t* keys, const
                                  int cells_per_axis, int num_planes, T8gpuSamplePlanes_f64 planes, double fill, double* sums,
                                  double* weights, void* stream);
 
+/* ---- time-averaged flow statistics: running sums and what they give (csrc/hip/stats.hip) -------------
+ * t8gpu_hip_stats_accumulate: for every owned cell i and slot k, sums[k plane_stride + i] += weight q_k(i), all arithmetic in
+ * double whatever float_type is, gamma = 1.4, with m = (m_x, m_y, m_z):
+ *    0      rho                          6      rho^2
+ *    1-3    m_x, m_y, m_z                7      p^2
+ *    4      E                            8-10   m_x m_x / rho, m_y m_y / rho, m_z m_z / rho
+ *    5      p = 0.4 (E - |m|^2 / (2 rho))   11-13  m_x m_y / rho, m_x m_z / rho, m_y m_z / rho
+ *                                        14     Mach = (|m| / rho) / sqrt(1.4 p / rho)
+ * One launch on `stream`: no host sync, no allocation, no atomics; every state value is read once, every accumulator value
+ * read once and written once. Cells [0, num_cells) only: ghost slots and spare capacity are neither read nor written.
+ * Nothing is filtered: a non-finite or non-physical cell makes that cell's sums non-finite (the state monitor is the guard).
+ * Two cells per lane -- 16-byte accesses of the accumulator rows and of fp64 state planes, 8-byte ones of fp32 state planes --
+ * when the five state planes and sums are 16-byte aligned and plane_stride is even, a scalar form otherwise; both give the
+ * same bits. The usual weight is the step size; the sums are time integrals of per-volume quantities, so the
+ * AMR transfer (child = parent, coarsened = mean of the family) carries them exactly.
+ * t8gpu_hip_stats_results: with W = total_weight and A_k = sums[k plane_stride + i], one launch that writes the planes of
+ * `out` that are not NULL (doubles, one value per owned cell) and nothing else:
+ *    0      mean_density     A0 / W                  10     density_rms   sqrt(max(0, A6 / W - (A0 / W)^2))
+ *    1-3    mean_momentum    A1..3 / W               11     pressure_rms  sqrt(max(0, A7 / W - (A5 / W)^2))
+ *    4      mean_energy      A4 / W                  12-17  reynolds_stress xx yy zz xy xz yz:
+ *    5      mean_pressure    A5 / W                         A_(8+k) / W - A_i A_j / (A0 W), the mean of rho u_i'' u_j''
+ *    6      mean_mach        A14 / W                 18     tke           0.5 (R_xx + R_yy + R_zz) / (A0 / W)
+ *    7-9    mean_velocity    A1..3 / A0 (the Favre mean)
+ * The second moments are raw sums: an rms far below about 1e-7 of the mean is rounding.
+ * Return 0 without a launch for num_cells = 0; hipErrorInvalidValue, before any launch, for a NULL state plane or sums,
+ * plane_stride < num_cells, or a total_weight that is not finite and > 0. */
+#define T8GPU_STATS_PLANES 15
+#define T8GPU_STATS_RESULT_PLANES 19
+typedef struct T8gpuStatsPlanes { double* p[19]; } T8gpuStatsPlanes;
+int t8gpu_hip_stats_accumulate_f32(size_t num_cells, T8gpuVars_f32 state, double weight, double* sums, size_t plane_stride,
+                                   void* stream);
+int t8gpu_hip_stats_accumulate_f64(size_t num_cells, T8gpuVars_f64 state, double weight, double* sums, size_t plane_stride,
+                                   void* stream);
+int t8gpu_hip_stats_results(size_t num_cells, const double* sums, size_t plane_stride, double total_weight, T8gpuStatsPlanes out,
+                            void* stream);
+
 /* ---- scale-free refinement indicator (csrc/hip/indicator.hip) ------------------------------
  * Loehner's estimator without cross terms, per axis, with a noise filter and a boundary closure. For cell c (an element, or a
  * subcell of a Subgrid block) and a scalar q, over the INTERIOR (sub-)faces s of c -- o the cell across, n_s the unit normal

@@ -123,12 +123,57 @@ def _criteria(solver, indicator, halo=None):
     return subgrid_refinement_criteria(solver) if hasattr(solver, "S") else refinement_criteria(solver)
 
 
+def _check_carry(carry, solver):
+    """`carry` as a tuple of objects with .sums (float64 device tensor [P, owned_cells]) and .solver (this solver): per-cell
+    payload that rides through the adapt beside the state, e.g. a stats.Statistics. ValueError otherwise."""
+    carry = tuple(carry)
+    for c in carry:
+        if c.solver is not solver:
+            raise ValueError("a carried object must belong to the solver that is adapted")
+        t = c.sums
+        if not (t.is_cuda and t.dtype == torch.float64 and t.dim() == 2 and t.shape[1] == solver.owned_cells):
+            raise ValueError(f"carried sums must be a float64 device tensor [P, {solver.owned_cells}], got {tuple(t.shape)} {t.dtype}")
+    return carry
+
+
+def _transfer_carry(sums, adapt_dev, n_new, dim, S=1):
+    """sums [P, n_old S] -> [P, n_new S] by the state's own transfer (child = parent, coarsened = mean of the family, kept =
+    copy; S > 1: the subcell rule of Subgrid blocks) through the _f64 transfer entries, five planes a call. The entries'
+    volume arguments get scratch; a last group of fewer than five planes is filled up with scratch planes."""
+    P, n_old = sums.shape[0], sums.shape[1] // S
+    groups = (P + 4) // 5
+    old = sums.contiguous()
+    if 5 * groups != P:
+        old = torch.cat([old, torch.zeros((5 * groups - P, old.shape[1]), dtype=torch.float64, device=old.device)])
+    new = torch.zeros((5 * groups, n_new * S), dtype=torch.float64, device=old.device)
+    if n_new > 0 and P > 0:
+        vol_old = torch.ones(max(1, n_old), dtype=torch.float64, device=old.device)
+        vol_new = torch.empty(n_new, dtype=torch.float64, device=old.device)
+        for g in range(groups):
+            if S == 1:
+                hip.call("t8gpu_hip_adapt_variables_and_volume", torch.float64, n_new, dim, hip.ptr(adapt_dev), hip.vars_of(old, g),
+                         hip.vars_of(new, g), hip.ptr(vol_old), hip.ptr(vol_new), hip.stream_ptr())
+            else:
+                hip.call("t8gpu_hip_subgrid_adapt_variables_and_volume", torch.float64, dim, n_new, hip.ptr(adapt_dev),
+                         hip.vars_of(old, g), hip.vars_of(new, g), hip.ptr(vol_old), hip.ptr(vol_new), hip.stream_ptr())
+    return new[:P]
+
+
+def _hand_over(carry, new_sums, new_solver):
+    """each carried object now refers to the new solver and holds its transferred sums"""
+    for c, t in zip(carry, new_sums):
+        c.sums, c.solver = t, new_solver
+
+
 def adapt(solver, threshold=10.0, min_level=1, max_level=4, family_members_averaged=4, volume_dim=None, indicator=None,
-          coarsen_below=None):
+          coarsen_below=None, carry=()):
     """Refine / coarsen the mesh of a single-rank PlainSolver by the reference's criterion and transfer the
     current solution. Returns the new solver (same dtype, flux, kernel tier, step bookkeeping).
     indicator (a Loehner): its criteria instead of the reference's, `threshold` the refine threshold; coarsen_below: the
-    coarsen threshold of the two-threshold marks (None: `threshold`, the reference's walk)."""
+    coarsen threshold of the two-threshold marks (None: `threshold`, the reference's walk).
+    carry: objects with .sums (float64 device tensor [P, owned_cells]) and .solver, e.g. a stats.Statistics: their sums are
+    transferred like the state and they refer to the new solver afterwards. The return values do not change."""
+    carry = _check_carry(carry, solver)
     import time
     part = solver.part
     assert part.nranks == 1, "multi-rank adaptation goes through amr.adapt_partitioned"
@@ -149,6 +194,7 @@ def adapt(solver, threshold=10.0, min_level=1, max_level=4, family_members_avera
     hip.call("t8gpu_hip_adapt_variables_and_volume", solver.dtype, new_part.N, dim, hip.ptr(ad),
              solver.get_own_variables(solver.next), new.get_own_variables(new.next), hip.ptr(solver.planes[25]),
              hip.ptr(new.planes[25]), hip.stream_ptr())
+    _hand_over(carry, [_transfer_carry(c.sums, ad, new_part.N, dim) for c in carry], new)
     torch.cuda.synchronize()
     if getattr(solver, "stepper", None) is not None:
         new.use_native_stepper()
@@ -203,24 +249,72 @@ class _Repartition:
         """first element of the temporary planes that stays on this rank (its receive from itself)"""
         return [f for p, f, m in self.sends if p == self.rank][0]
 
-    def transport(self, dist, host_staged=False):
-        """host_staged: move the messages through host memory (gloo, which cannot send device buffers)."""
-        torch.cuda.synchronize()
-        rbuf = {q: (b.cpu() if host_staged else b) for q, b in self.recvbufs.items()}
-        sbuf = {q: (b.cpu() if host_staged else b) for q, b in self.sendbufs.items()}
-        ops = []
+    def _pack_carry(self, carry, dim, S=1):
+        """The carried payload of the constructor's `carry` (_check_carry): every object's sums transferred on this rank's own
+        elements into temporary planes [P, n_have S], and one extra message per peer beside the state's --
+        carry_sendbufs[q] / carry_recvbufs[q], float64, the objects' runs [P, n S] one after the other. sendbufs / recvbufs
+        keep their contents and sizes."""
+        self.carry = _check_carry(carry, self.solver)
+        self.carry_S = S
+        self.carry_tmp, self.carry_sendbufs, self.carry_recvbufs = [], {}, {}
+        if not self.carry:
+            return
+        dev = self.solver.planes.device
+        ad_local = torch.from_numpy(self.adapt_local).to(dev)
+        self.carry_tmp = [_transfer_carry(c.sums, ad_local, self.n_have, dim, S) for c in self.carry]
+        width = sum(t.shape[0] for t in self.carry_tmp) * S
+        for q, first, n in self.sends:
+            if q != self.rank:
+                self.carry_sendbufs[q] = torch.cat([t[:, first * S:(first + n) * S].reshape(-1) for t in self.carry_tmp])
         for q, _, n in self.recvs:
             if q != self.rank:
-                ops.append(dist.P2POp(dist.irecv, rbuf[q], q))
-        for q, _, n in self.sends:
-            if q != self.rank:
-                ops.append(dist.P2POp(dist.isend, sbuf[q], q))
+                self.carry_recvbufs[q] = torch.empty(width * n, dtype=torch.float64, device=dev)
+
+    def _unpack_carry(self, new):
+        """the carried objects' new sums [P, owned cells of the new partition] from the kept runs and the received messages;
+        the objects then refer to `new`"""
+        if not self.carry:
+            return
+        S = self.carry_S
+        sums = [torch.zeros((t.shape[0], new.owned_cells), dtype=torch.float64, device=t.device) for t in self.carry_tmp]
+        for q, first, n in self.recvs:
+            if q == self.rank:
+                src_first = self.kept_first()
+                for dst, t in zip(sums, self.carry_tmp):
+                    dst[:, first * S:(first + n) * S] = t[:, src_first * S:(src_first + n) * S]
+            else:
+                buf, at = self.carry_recvbufs[q], 0
+                for dst in sums:
+                    size = dst.shape[0] * n * S
+                    dst[:, first * S:(first + n) * S] = buf[at:at + size].view(dst.shape[0], n * S)
+                    at += size
+        _hand_over(self.carry, sums, new)
+
+    def transport(self, dist, host_staged=False):
+        """host_staged: move the messages through host memory (gloo, which cannot send device buffers). Ships the state's
+        messages and, behind them in the same order, the carried ones."""
+        torch.cuda.synchronize()
+        pairs = [(self.recvbufs, self.sendbufs)]
+        if getattr(self, "carry", ()):
+            pairs.append((self.carry_recvbufs, self.carry_sendbufs))
+        staged, ops = [], []
+        for recvbufs, sendbufs in pairs:
+            rbuf = {q: (b.cpu() if host_staged else b) for q, b in recvbufs.items()}
+            sbuf = {q: (b.cpu() if host_staged else b) for q, b in sendbufs.items()}
+            staged.append((recvbufs, rbuf))
+            for q, _, n in self.recvs:
+                if q != self.rank:
+                    ops.append(dist.P2POp(dist.irecv, rbuf[q], q))
+            for q, _, n in self.sends:
+                if q != self.rank:
+                    ops.append(dist.P2POp(dist.isend, sbuf[q], q))
         if ops:
             for req in dist.batch_isend_irecv(ops):
                 req.wait()
         if host_staged:
-            for q, b in self.recvbufs.items():
-                b.copy_(rbuf[q])
+            for recvbufs, rbuf in staged:
+                for q, b in recvbufs.items():
+                    b.copy_(rbuf[q])
 
 
 class PartitionedAdapt(_Repartition):
@@ -229,9 +323,10 @@ class PartitionedAdapt(_Repartition):
     packed by a gather kernel."""
 
     def __init__(self, solver, all_criteria, threshold=10.0, min_level=1, max_level=4, family_members_averaged=4, indicator=None,
-                 coarsen_below=None):
+                 coarsen_below=None, carry=()):
         """indicator: where all_criteria came from (adapt_partitioned evaluates it; nothing here depends on it);
-        coarsen_below: the coarsen threshold of the two-threshold marks (None: `threshold`)"""
+        coarsen_below: the coarsen threshold of the two-threshold marks (None: `threshold`); carry: as for adapt(), shipped
+        in carry_sendbufs / carry_recvbufs (_pack_carry) and handed over by finish()"""
         part = solver.part
         super().__init__(solver, _marks(part.mesh, all_criteria, threshold, min_level, max_level, family_members_averaged, coarsen_below))
         dtype, dev = solver.dtype, solver.planes.device
@@ -259,6 +354,7 @@ class PartitionedAdapt(_Repartition):
             if q != self.rank:
                 hip.call("t8gpu_hip_gather_elements", dtype, n, first, hip.vars_of(self.tmp), hip.ptr(self.tmp[5]),
                          hip.ptr(self.sendbufs[q]), s)
+        self._pack_carry(carry, part.mesh.dim)
 
     def finish(self):
         new, dtype = self.new_solver, self.solver.dtype
@@ -271,6 +367,7 @@ class PartitionedAdapt(_Repartition):
                 new.planes[25, first:first + n] = self.tmp[5, src_first:src_first + n]
             else:
                 hip.call("t8gpu_hip_scatter_elements", dtype, n, first, hip.ptr(self.recvbufs[q]), nv, hip.ptr(new.planes[25]), s)
+        self._unpack_carry(new)
         torch.cuda.synchronize()
         return new
 
@@ -296,8 +393,9 @@ def adapt_partitioned(solver, dist, host_staged=False, halo=None, **kw):
     step driver refreshes those slots -- a stage only exchanges the ghosts of its SOURCE state, so after a step the
     last stage's output carries ghost values two stages old. The exchange is therefore part of this function (through
     `halo`, the run's HaloExchange of this partition, or a temporary one): refinement marks must not depend on the
-    number of ranks. indicator= (a Loehner) and coarsen_below= go to PartitionedAdapt; the indicator's buffer passes exchange
-    the ghost entries of the criteria through the same `halo`."""
+    number of ranks. indicator= (a Loehner), coarsen_below= and carry= go to PartitionedAdapt; the indicator's buffer passes
+    exchange the ghost entries of the criteria through the same `halo`. carry: as for adapt(): every rank's carried objects
+    travel with its elements and refer to its new solver afterwards."""
     if solver.part.nranks > 1:
         if halo is None:
             from .halo import HaloExchange
@@ -319,11 +417,14 @@ def subgrid_refinement_criteria(solver):
     return crit
 
 
-def adapt_subgrid(solver, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4, indicator=None, coarsen_below=None):
+def adapt_subgrid(solver, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4, indicator=None, coarsen_below=None,
+                  carry=()):
     """SubgridCompressibleEulerSolver::adapt (examples/subgrid/solver.inl:327-345) for a single-rank SubgridSolver:
     H1-seminorm indicator, the forest adapt, block-wise data transfer (subgrid_mesh_manager.inl:246-425).
-    indicator (a Loehner): its block maxima instead, `threshold` the refine threshold; coarsen_below: as for adapt()."""
+    indicator (a Loehner): its block maxima instead, `threshold` the refine threshold; coarsen_below and carry: as for
+    adapt(); carried sums follow the subcell rule of the block transfer."""
     from .solver import SubgridSolver
+    carry = _check_carry(carry, solver)
     part = solver.part
     assert part.nranks == 1
     mesh = part.mesh
@@ -340,6 +441,7 @@ def adapt_subgrid(solver, threshold=0.02, min_level=1, max_level=6, family_membe
     hip.call("t8gpu_hip_subgrid_adapt_variables_and_volume", solver.dtype, solver.rank, new_part.N, hip.ptr(ad),
              solver.get_own_variables(solver.next), new.get_own_variables(new.next), hip.ptr(solver.volumes),
              hip.ptr(new.volumes), hip.stream_ptr())
+    _hand_over(carry, [_transfer_carry(c.sums, ad, new_part.N, solver.rank, S) for c in carry], new)
     torch.cuda.synchronize()
     return new, marks, adapt_data
 
@@ -351,8 +453,8 @@ class PartitionedSubgridAdapt(_Repartition):
     blocks is contiguous in every variable plane, so a message is six slices; no gather kernel is needed."""
 
     def __init__(self, solver, all_criteria, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4, indicator=None,
-                 coarsen_below=None):
-        """indicator / coarsen_below: as for PartitionedAdapt"""
+                 coarsen_below=None, carry=()):
+        """indicator / coarsen_below / carry: as for PartitionedAdapt"""
         from .solver import SubgridSolver
         part = solver.part
         super().__init__(solver, _marks(part.mesh, all_criteria, threshold, min_level, max_level, family_members_averaged, coarsen_below))
@@ -382,6 +484,7 @@ class PartitionedSubgridAdapt(_Repartition):
         for q, _, n in self.recvs:
             if q != self.rank:
                 self.recvbufs[q] = torch.empty(w * n, dtype=dtype, device=dev)
+        self._pack_carry(carry, solver.rank, S)
 
     def finish(self):
         new, S = self.new_solver, self.S
@@ -395,6 +498,7 @@ class PartitionedSubgridAdapt(_Repartition):
                 buf = self.recvbufs[q]
                 dst[:, first * S:(first + n) * S] = buf[: 5 * S * n].view(5, n * S)
                 new.volumes[first:first + n] = buf[5 * S * n:]
+        self._unpack_carry(new)
         torch.cuda.synchronize()
         return new
 
@@ -403,7 +507,7 @@ def adapt_subgrid_partitioned(solver, dist, host_staged=False, halo=None, **kw):
     """Collective: every rank calls it with its own SubgridSolver; returns the rank's new solver.
     The reference's criterion reads no other block, so without indicator= nothing is exchanged. A Loehner indicator reads the
     ghost blocks of the `next` state: they are exchanged first, through `halo` (the run's HaloExchange of this partition) or a
-    temporary one, as in adapt_partitioned."""
+    temporary one, as in adapt_partitioned. carry= goes to PartitionedSubgridAdapt, as there."""
     indicator = kw.get("indicator")
     if indicator is not None and solver.part.nranks > 1:
         if halo is None:

@@ -34,16 +34,36 @@ class SampleGrid(C.Structure):
     _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("n", C.c_int32 * 3), ("pad", C.c_int32)]
 
 
-def check_names(names):
-    """`names` (one name or several) as a list without repeats; an unknown name raises ValueError listing the valid ones"""
+def check_names(names, extra=None):
+    """`names` (one name or several) as a list without repeats; an unknown name raises ValueError listing the valid ones.
+    extra: the caller's own planes (check_extra), whose names are valid too"""
     names = [names] if isinstance(names, str) else list(names)
+    valid = NAMES + tuple(extra or ())
     for name in names:
-        if name not in NAMES:
-            raise ValueError(f"unknown field {name!r}: one of {', '.join(NAMES)}")
+        if name not in valid:
+            raise ValueError(f"unknown field {name!r}: one of {', '.join(valid)}")
     return list(dict.fromkeys(names))
 
 
-def plane_count(name):
+def check_extra(extra, cells):
+    """{name: tensor [planes, cells]} of extra = {name: float64 device tensor over the owned cells, [cells] or [C, cells]}
+    (None: {}). A name of the built-in ones, another dtype, device or length raises ValueError."""
+    import torch
+    out = {}
+    for name, t in (extra or {}).items():
+        if name in NAMES:
+            raise ValueError(f"extra field {name!r} has the name of a built-in one")
+        ok = isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() in (1, 2) and t.shape[-1] == cells
+        if not ok:
+            raise ValueError(f"extra field {name!r} must be a float64 device tensor [{cells}] or [C, {cells}]")
+        t = t.reshape(-1, cells)
+        out[name] = t if t.stride(1) == 1 or cells == 0 else t.contiguous()
+    return out
+
+
+def plane_count(name, extra=None):
+    if extra and name in extra:
+        return int(extra[name].shape[0])
     return (STATE.get(name) or fields.FIELDS[name])[1]
 
 
@@ -130,7 +150,8 @@ class Sampler:
     """Keys and levels of a solver's owned elements on the device, built and uploaded once, and the sampling calls on them.
     Made on first use by `sampler(solver)` and kept on the solver (a solver's mesh never changes; an adapt makes a new
     solver). Every call is enqueued on `stream` (default: the current stream) without a host sync; a rank of a partitioned
-    run samples its owned cells only and returns cell -1 / `fill` / weight 0 for the rest."""
+    run samples its owned cells only and returns cell -1 / `fill` / weight 0 for the rest. extra = {name: float64 device
+    tensor over the owned cells, [cells] or [C, cells]} adds names of the caller's own (check_extra), read as double planes."""
 
     def __init__(self, solver):
         import torch
@@ -160,11 +181,11 @@ class Sampler:
             raise ValueError(f"points must have shape [M, {self.dim}], got {tuple(p.shape)}")
         return p.contiguous()
 
-    def _sources(self, names, step, stream, halo):
+    def _sources(self, names, step, stream, halo, extra=None):
         """(names, SamplePlanes, number of planes, what to keep alive): state planes by pointer, derived names through one
-        derived_fields pass over the owned cells"""
-        names = check_names(names)
-        total = sum(plane_count(n) for n in names)
+        derived_fields pass over the owned cells, the names of `extra` (check_extra) from the caller's double planes"""
+        names = check_names(names, extra)
+        total = sum(plane_count(n, extra) for n in names)
         if total > MAX_PLANES:
             raise ValueError(f"{total} planes asked for, one call takes {MAX_PLANES}")
         s = self.solver.next if step is None else step
@@ -172,7 +193,11 @@ class Sampler:
         got = self.solver.derived_fields(derived, s, stream, halo) if derived else {}
         src, k = SamplePlanes(), 0
         for name in names:
-            if name in STATE:
+            if extra and name in extra:
+                count = plane_count(name, extra)
+                for j in range(count):
+                    src.d[k + j] = extra[name][j].data_ptr()
+            elif name in STATE:
                 first, count = STATE[name]
                 for j in range(count):
                     src.q[k + j] = self.solver.planes[5 * s + first + j].data_ptr()
@@ -182,14 +207,14 @@ class Sampler:
                 for j in range(count):
                     src.d[k + j] = planes[j].data_ptr()
             k += count
-        return names, src, total, got
+        return names, src, total, (got, extra)
 
     @staticmethod
-    def _split(names, out, shape):
-        """{name: view of out[planes, ...]} in the shape of one plane, [3, ...] for a vector"""
+    def _split(names, out, shape, extra=None):
+        """{name: view of out[planes, ...]} in the shape of one plane, [3, ...] for a vector ([C, ...] for C extra planes)"""
         res, k = {}, 0
         for name in names:
-            count = plane_count(name)
+            count = plane_count(name, extra)
             res[name] = out[k].view(shape) if count == 1 else out[k:k + count].view((count,) + tuple(shape))
             k += count
         return res
@@ -215,24 +240,27 @@ class Sampler:
         with torch.cuda.stream(stream):
             return self._locate(self._points(points), stream)
 
-    def sample_points(self, points, names, step=None, stream=None, halo=None, fill=math.nan):
+    def sample_points(self, points, names, step=None, stream=None, halo=None, fill=math.nan, extra=None):
         import torch
         stream = self._stream(stream)
+        extra = check_extra(extra, self.solver.owned_cells)
         with torch.cuda.stream(stream):
             p = self._points(points)
             m = p.shape[0]
-            names = check_names(names)
+            names = check_names(names, extra)
             if m == 0:
-                return self._split(names, torch.empty((sum(map(plane_count, names)), 0), dtype=torch.float64, device="cuda"), (0,))
-            names, src, total, keep = self._sources(names, step, stream, halo)
+                planes = sum(plane_count(n, extra) for n in names)
+                return self._split(names, torch.empty((planes, 0), dtype=torch.float64, device="cuda"), (0,), extra)
+            names, src, total, keep = self._sources(names, step, stream, halo, extra)
             cells = self._locate(p, stream)
             out = torch.empty((total, m), dtype=torch.float64, device="cuda")
             self._hip.call("t8gpu_hip_sample_gather", self.solver.dtype, C.c_size_t(m), self._hip.ptr(cells), total, src,
                            C.c_double(fill), self._hip.ptr(out), self._hip.stream_ptr(stream))
             del keep
-        return self._split(names, out, (m,))
+        return self._split(names, out, (m,), extra)
 
-    def sample_grid(self, names, shape, lo=None, hi=None, step=None, stream=None, halo=None, fill=math.nan, cells=False):
+    def sample_grid(self, names, shape, lo=None, hi=None, step=None, stream=None, halo=None, fill=math.nan, cells=False,
+                    extra=None):
         import torch
         dim = self.dim
         shape = tuple(int(n) for n in shape)
@@ -242,15 +270,17 @@ class Sampler:
             raise ValueError(f"shape, lo and hi need {dim} entries each")
         if any(n < 0 for n in shape):
             raise ValueError(f"negative grid extent in {shape}")
-        names = check_names(names)
+        extra = check_extra(extra, self.solver.owned_cells)
+        names = check_names(names, extra)
         image, pixels = shape[::-1], math.prod(shape)
         stream = self._stream(stream)
         with torch.cuda.stream(stream):
             cell = torch.empty(image, dtype=torch.int32, device="cuda") if cells else None
             if pixels == 0:
-                res = self._split(names, torch.empty((sum(map(plane_count, names)), 0), dtype=torch.float64, device="cuda"), image)
+                planes = sum(plane_count(n, extra) for n in names)
+                res = self._split(names, torch.empty((planes, 0), dtype=torch.float64, device="cuda"), image, extra)
             else:
-                names, src, total, keep = self._sources(names, step, stream, halo)
+                names, src, total, keep = self._sources(names, step, stream, halo, extra)
                 g = SampleGrid()
                 for a in range(dim):
                     g.lo[a], g.hi[a], g.n[a] = lo[a], hi[a], shape[a]
@@ -258,20 +288,21 @@ class Sampler:
                 self._hip.call("t8gpu_hip_sample_grid", self.solver.dtype, dim, g, *self._forest(), total, src, C.c_double(fill),
                                self._hip.ptr(out), self._hip.ptr(cell), self._hip.stream_ptr(stream))
                 del keep
-                res = self._split(names, out, image)
+                res = self._split(names, out, image, extra)
         if cells:
             res["cell"] = cell
         return res
 
-    def resample_uniform(self, names, level, step=None, stream=None, halo=None, fill=math.nan, partial=False):
+    def resample_uniform(self, names, level, step=None, stream=None, halo=None, fill=math.nan, partial=False, extra=None):
         import torch
         level = int(level)
         if not 0 <= level <= DEPTH:
             raise ValueError(f"level must lie in 0..{DEPTH}, got {level}")
         image = (1 << level,) * self.dim
         stream = self._stream(stream)
+        extra = check_extra(extra, self.solver.owned_cells)
         with torch.cuda.stream(stream):
-            names, src, total, keep = self._sources(names, step, stream, halo)
+            names, src, total, keep = self._sources(names, step, stream, halo, extra)
             if total == 0:
                 raise ValueError("resample_uniform needs at least one name")
             out = torch.empty((total, 1 << (self.dim * level)), dtype=torch.float64, device="cuda")
@@ -279,7 +310,7 @@ class Sampler:
             self._hip.call("t8gpu_hip_sample_uniform", self.solver.dtype, self.dim, level, *self._forest(), total, src,
                            C.c_double(fill), self._hip.ptr(out), self._hip.ptr(weights), self._hip.stream_ptr(stream))
             del keep
-        res = self._split(names, out, image)
+        res = self._split(names, out, image, extra)
         return (res, weights) if partial else res
 
 

@@ -346,6 +346,14 @@ class _Solver:
         from . import fields
         return fields.derived_fields(self, names, step, stream, halo)
 
+    def statistics(self):
+        """A stats.Statistics of this solver (stats.py): float64 running sums [15, owned_cells] on the device,
+        zeroed, and the calls on them -- accumulate(weight) after a step, results(names) for means, rms values, Reynolds
+        stresses and tke, reset(). Needs no geometry: every mesh class. Hand it to the adapt functions of amr.py as
+        carry=(stats,) and it follows the run onto the new mesh."""
+        from . import stats
+        return stats.Statistics(self)
+
     # -- sampling on Cartesian forests (sample.py, DESIGN.md §12): cell values cast to double, never interpolated ----------------
     def locate(self, points, stream=None):
         """int32 device tensor [M]: the storage index among the owned cells of the cell that holds each of points[M, dim] (a host
@@ -354,27 +362,30 @@ class _Solver:
         from . import sample
         return sample.sampler(self).locate(points, stream)
 
-    def sample_points(self, points, names, step=None, stream=None, halo=None, fill=float("nan")):
+    def sample_points(self, points, names, step=None, stream=None, halo=None, fill=float("nan"), extra=None):
         """{name: float64 device tensor [M] or [3, M]} of `names` -- "density", "momentum", "energy" of state(step) and every name
         of derived_fields -- at points[M, dim]: the value of the holding cell, `fill` where locate gives -1. Derived names cost
-        one derived_fields pass over the owned cells first, with `halo` handed on."""
+        one derived_fields pass over the owned cells first, with `halo` handed on. extra = {name: float64 device tensor over
+        the owned cells, [cells] or [C, cells]}: names of the caller's own that may be asked for beside the built-in ones (here
+        and in sample_grid / resample_uniform), e.g. the results of a stats.Statistics."""
         from . import sample
-        return sample.sampler(self).sample_points(points, names, step, stream, halo, fill)
+        return sample.sampler(self).sample_points(points, names, step, stream, halo, fill, extra)
 
-    def sample_grid(self, names, shape, lo=None, hi=None, step=None, stream=None, halo=None, fill=float("nan"), cells=False):
+    def sample_grid(self, names, shape, lo=None, hi=None, step=None, stream=None, halo=None, fill=float("nan"), cells=False,
+                    extra=None):
         """sample_points on the pixel centres lo + (i + 0.5) (hi - lo) / n of a grid of shape (nx, ny[, nz]) over the box lo..hi
         (default: the whole domain), in one fused launch that forms no point array: tensors [ny, nx], [nz, ny, nx] or [3, ...],
         x fastest. An axis with lo == hi is a slice plane at that coordinate. cells=True adds "cell": the int32 indices."""
         from . import sample
-        return sample.sampler(self).sample_grid(names, shape, lo, hi, step, stream, halo, fill, cells)
+        return sample.sampler(self).sample_grid(names, shape, lo, hi, step, stream, halo, fill, cells, extra)
 
-    def resample_uniform(self, names, level, step=None, stream=None, halo=None, fill=float("nan"), partial=False):
+    def resample_uniform(self, names, level, step=None, stream=None, halo=None, fill=float("nan"), partial=False, extra=None):
         """Conservative resampling onto the 2^level pixels per axis of a uniform level, shapes as sample_grid: per pixel
         sum(w q) / sum(w) over the owned cells that meet it, w = 2^(-dim level of the smaller of pixel and cell), summed in
         ascending storage order in double; `fill` where no owned cell meets the pixel. partial=True: ({name: sums}, weights)
         instead, for ranks to add up and divide once."""
         from . import sample
-        return sample.sampler(self).resample_uniform(names, level, step, stream, halo, fill, partial)
+        return sample.sampler(self).resample_uniform(names, level, step, stream, halo, fill, partial, extra)
 
     def cfl_timestep(self, cfl=0.7, step=None, dist=None):
         """cfl / max over the cells of (|v| + c) / h, h = vol^(1/dim), from the state itself: needs no stage to have run (a new

@@ -88,6 +88,27 @@ def get_host_derived_variable(solver, name, step=None, halo=None):
     return HostVariableInfo(VECTOR, out.cpu().numpy().reshape(n, 3), name)
 
 
+def get_host_statistics_variable(stats, name):
+    """One result of a stats.Statistics (stats.RESULTS: "mean_density", "mean_velocity", "tke", ...) as doubles on the host,
+    ready for save_variables_to_vtk: a scalar as it is, a 3-vector interleaved xyz; the 6-component "reynolds_stress" as a
+    list of six scalars reynolds_stress_xx .. _yz (the writer knows scalars and 3-vectors). For a Subgrid solver every
+    plane in z-order first."""
+    from . import stats as st
+    solver = stats.solver
+    t = stats.results([name])[name]
+    planes = [t] if t.dim() == 1 else [t[k] for k in range(t.shape[0])]
+    if hasattr(solver, "S"):
+        planes = [column_major_to_z_order(solver, p.contiguous()) for p in planes]
+    n = _own_cells(solver)
+    if len(planes) == 3:
+        out = torch.empty(3 * n, dtype=torch.float64, device="cuda")
+        hip.call("t8gpu_hip_host_vector_variable", torch.float64, C.c_size_t(n), hip.ptr(planes[0]), hip.ptr(planes[1]),
+                 hip.ptr(planes[2]), hip.ptr(out), hip.stream_ptr())
+        return HostVariableInfo(VECTOR, out.cpu().numpy().reshape(n, 3), name)
+    infos = [HostVariableInfo(SCALAR, p.cpu().numpy(), label) for p, label in zip(planes, st.plane_names(name))]
+    return infos[0] if len(infos) == 1 else infos
+
+
 def get_host_indicator_variable(solver, indicator, name="indicator", halo=None, step=None):
     """The per-cell values of a refinement indicator (amr.Loehner.cell_values) as doubles on the host, ready for
     save_variables_to_vtk; for a Subgrid solver in z-order, as get_host_derived_variable."""
