@@ -19,10 +19,16 @@
 //    kernel BODIES (plain and Subgrid flux kernels with the 2:1 hanging map,
 //    walls, the six RK stages) run on tiny AMR meshes:
 //    tests/test_oracle_reference_kernels.py, bit for bit;
+//  * the executed AMR vectors -- the plain and Subgrid transfer kernels of
+//    adapt(), both refinement criteria and estimate_gradient, run on real
+//    forests (a coarsened and a refined family at element 0, a new mesh of one
+//    element): tests/test_oracle_reference_amr_kernels.py, bit for bit;
 //  * the HIP tiers meet those same arrays directly, not only through this file:
 //    tests/test_gpu_reference_kernels.py (compat kernels one by one, the
-//    element -> slot map, one fused stage per kernel form).
-// Both fixtures come from host compilations behind stand-ins for the CUDA
+//    element -> slot map, one fused stage per kernel form) and
+//    tests/test_gpu_reference_amr_kernels.py (transfer, criteria, gradient,
+//    z-order, gather / scatter / repartition, amr.adapt and amr.adapt_subgrid).
+// All three fixtures come from host compilations behind stand-ins for the CUDA
 // qualifiers and built-ins, so by the project's rules
 // parity formally stays "unpinned".
 #pragma once
