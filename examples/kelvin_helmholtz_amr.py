@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from t8gpu_amd import amr, hostmem, vtk  # noqa: E402
+from t8gpu_amd import amr, hostmem, tracers, vtk  # noqa: E402
 from t8gpu_amd.halo import HaloExchange  # noqa: E402
 from t8gpu_amd.solver import PlainSolver  # noqa: E402
 from t8gpu_amd.synth import SynthMesh  # noqa: E402
@@ -51,6 +51,11 @@ def main():
                          "carried through every adapt; mean_density, mean_velocity, tke and pressure_rms go to the VTK output, a "
                          "tke image beside the others with --image")
     ap.add_argument("--stats-every", type=int, default=1, metavar="K", help="accumulate every K steps with weight K dt (default 1)")
+    ap.add_argument("--tracers", type=int, default=None, metavar="N",
+                    help="advect an N x N lattice of tracer particles with the flow (solver.tracers: predict before every step, "
+                         "correct after it, rebind after every adapt; on several ranks every rank holds all particles and the "
+                         "velocities are summed, one all_reduce per phase): positions and status are saved as .npy files beside "
+                         "the images (prefix --vtk, or kh) at the end, and every --image-every steps")
     args = ap.parse_args()
     indicator, coarsen = None, None
     if args.indicator == "loehner":
@@ -110,6 +115,14 @@ def main():
                 np.save(f"{prefix}_tke_{it:06d}.npy", image.cpu().numpy())
         say(f"images at it {it}: {prefix}_{{schlieren,density}}_{it:06d}.npy", flush=True)
 
+    def save_tracers(it):
+        if rank == 0:                                    # (every rank holds the same particles)
+            prefix = args.vtk or "kh"
+            os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
+            h = tr.host()
+            np.save(f"{prefix}_tracers_x_{it:06d}.npy", h["x"])
+            np.save(f"{prefix}_tracers_status_{it:06d}.npy", h["status"])
+
     mesh = SynthMesh(2, args.min_level, args.min_level)
     solver = PlainSolver(mesh.partition(rank, world), dtype, mode="fused")
     # refine the initial mesh around the shear layers before starting (the reference adapts at step 0)
@@ -123,6 +136,7 @@ def main():
     halo_of = {id(solver): halo}
     if world == 1:
         solver.use_native_stepper()
+    tr = solver.tracers(tracers.lattice(2, args.tracers)) if args.tracers else None
     stats = solver.statistics() if args.stats else None      # running sums on the device; they follow the run through adapt
     mass0 = solver.monitor(dist=dist).integrals      # the state monitor: one device pass, one all-reduced block of 16 doubles
     t_iter = t_adapt = 0.0
@@ -138,6 +152,8 @@ def main():
                 halo_of = {id(solver): halo}
             else:
                 solver.use_native_stepper()
+            if tr is not None:
+                tr.rebind(solver)                        # particles are coordinates: an adapt does not touch them
             torch.cuda.synchronize()
             t_adapt += time.perf_counter() - t0
         if it == 0 or it % args.adapt_every == 0:
@@ -146,7 +162,11 @@ def main():
             dt = solver.compute_timestep(cfl=0.35, dist=dist)                 # CFL step from the device-side max speed
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        if tr is not None:
+            tr.predict(dt, dist=dist)                    # k1 = u^n(x), xs = x + dt k1
         solver.iterate(dt, halo=halo)
+        if tr is not None:
+            tr.correct(dt, dist=dist)                    # x += dt / 2 (k1 + u^(n+1)(xs))
         torch.cuda.synchronize()
         t_iter += time.perf_counter() - t0
         cells += solver.N
@@ -154,6 +174,8 @@ def main():
             stats.accumulate(args.stats_every * dt)              # the time the sample stands for: K steps of dt
         if args.image and args.image_every and (it + 1) % args.image_every == 0 and it + 1 < args.steps:
             save_images(solver, it + 1)
+        if tr is not None and args.image_every and (it + 1) % args.image_every == 0 and it + 1 < args.steps:
+            save_tracers(it + 1)
         if it % 100 == 0:
             mon = solver.monitor(dist=dist)
             drift = float(abs(mon.integrals - mass0).max())
@@ -162,6 +184,10 @@ def main():
     assert bool(torch.isfinite(solver.state()).all())
     if args.image:
         save_images(solver, args.steps)
+    if tr is not None:
+        save_tracers(args.steps)
+        active, left, lost = tr.counts()
+        say(f"tracers: {tr.M} particles, {active} active, {lost} lost")
     if args.vtk:
         # CompressibleEulerSolver::save_conserved_variables_to_vtk (examples/compressible_euler/solver.cu:177-186)
         os.makedirs(os.path.dirname(os.path.abspath(args.vtk)), exist_ok=True)

@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from t8gpu_amd import amr, boundary, vtk  # noqa: E402
+from t8gpu_amd import amr, boundary, tracers, vtk  # noqa: E402
 from t8gpu_amd.solver import PlainSolver  # noqa: E402
 from t8gpu_amd.synth import SynthMesh  # noqa: E402
 
@@ -56,6 +56,10 @@ def main():
     ap.add_argument("--budget", action="store_true",
                     help="print, every 50 steps and at the end, the change of mass and energy (monitor()) against the "
                          "boundary flux integrated in time on the device (boundary.Budget), and their difference")
+    ap.add_argument("--tracers", type=int, default=None, metavar="N",
+                    help="advect an N x N lattice of tracer particles with the flow (solver.tracers: predict before every step, "
+                         "correct after it, rebind after every adapt), print how many left through the open sides, and save "
+                         "positions and status as riemann2d_tracers_{x,status}.npy in --out (default: the working directory)")
     args = ap.parse_args()
     if args.toy:
         args.min_level, args.max_level, args.t_end, args.adapt_every = 3, 5, 0.05, 5
@@ -80,12 +84,15 @@ def main():
         solver.planes[5 * solver.next:5 * solver.next + 5] = ic
     solver.use_native_stepper()
     budget = boundary.Budget(solver) if args.budget else None
+    tr = solver.tracers(tracers.lattice(2, args.tracers)) if args.tracers else None
     t, it, cells, t_iter = 0.0, 0, 0, 0.0
     while t < args.t_end - 1e-12:
         fresh = it % args.adapt_every == 0 and it > 0
         if fresh:
             solver = adapt(solver)
             solver.use_native_stepper()
+            if tr is not None:
+                tr.rebind(solver)                                  # particles are coordinates: an adapt does not touch them
         if it == 0:
             dt = 0.1 * 2.0 ** -solver.part.mesh.finest_level
         elif fresh:
@@ -95,7 +102,11 @@ def main():
         dt = min(dt, args.t_end - t)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        if tr is not None:
+            tr.predict(dt)                                         # k1 = u^n(x), xs = x + dt k1
         solver.iterate(dt)
+        if tr is not None:
+            tr.correct(dt)                                         # x += dt / 2 (k1 + u^(n+1)(xs))
         torch.cuda.synchronize()
         t_iter += time.perf_counter() - t0
         if budget is not None:
@@ -112,6 +123,13 @@ def main():
         print(budget.line(solver))
     assert bool(torch.isfinite(solver.state()).all())
     print(f"t = {t:.4f} after {it} steps, {solver.N} elements; {cells / t_iter / 1e6:.1f} M cell-updates/s (host-synchronised)")
+    if tr is not None:
+        active, left, lost = tr.counts()
+        print(f"tracers: {tr.M} particles, {left} left through the open sides, {lost} lost, {active} still inside")
+        os.makedirs(args.out or ".", exist_ok=True)
+        h = tr.host()
+        for name in ("x", "status"):
+            np.save(os.path.join(args.out or ".", f"riemann2d_tracers_{name}.npy"), h[name])
     if args.lineout:
         n = 2 ** (solver.part.mesh.finest_level + 1)               # two points per finest cell: cell values, not interpolated
         s = (np.arange(n) + 0.5) / n

@@ -705,6 +705,59 @@ int t8gpu_hip_sample_uniform_f64(int dim, int level, const uint64_t* keys, const
                                  int cells_per_axis, int num_planes, T8gpuSamplePlanes_f64 planes, double fill, double* sums,
                                  double* weights, void* stream);
 
+/* ---- tracer particles on Cartesian forests, advected by Heun's method (csrc/hip/tracers.hip) ---------------
+ * A particle is a coordinate x[dim] in double, not a member of a cell. The forest arguments (keys, levels, num_elements,
+ * cells_per_axis) and the holding cell c of a point are those of the sampling section above. All arithmetic in double, every
+ * operation rounded on its own (no fused multiply-add); the numpy functions host_velocity / host_map / host_predict /
+ * host_correct of t8gpu_amd/tracers.py state the same arithmetic and are the definition.
+ * Velocity at a point p: u_a = double(state.p[1 + a][c]) / double(state.p[0][c]) for a < dim and held = 1, or u = +0 and
+ * held = 0 when no owned cell holds p. Never interpolated.
+ * map(p), per axis a with the kinds sides.kind[2 a] (lower side) and sides.kind[2 a + 1] (upper side):
+ *    periodic   y = p - floor(p), and y = 0 when that is >= 1
+ *    wall       p < 0: y = -p (lower side);  p >= 1: y = 2 - p (upper side);  a result of exactly 1 becomes the largest double
+ *               below 1
+ *    open       p < 0 or p >= 1 on any axis: the particle has LEFT, y = p on every axis
+ * and the particle is LOST when p is non-finite on any axis (this first), or, not having left, when some y is outside [0, 1).
+ * Phases, for the particles with status ACTIVE only -- a LEFT or LOST particle is neither read nor written again:
+ *    PREDICT  k1 = k.  held = 0: LOST, xs = x.  Else raw = x + dt k1 and xs = map(raw), flag = 0;  left: xs = raw, flag = 1
+ *             (the status changes in CORRECT);  lost: status = LOST, xs = x, flag = 0.
+ *    CORRECT  k2 = flag ? k1 : k.  flag = 0 and held = 0: LOST (x stays).  Else x = map(x + (0.5 dt) (k1 + k2)), the sum first;
+ *             left: status = LEFT, x = the raw point;  lost: status = LOST, x stays.
+ * t8gpu_hip_tracers_velocity: k[i dim + a], held[i] for points[i dim ..), every point whatever its status. hint[num_points]
+ * (may be NULL) is one in/out element index per point: when it lies in [0, num_elements) and that element covers the point,
+ * the binary search is skipped; it is range-checked before it is used, the result does not depend on what it held, and the
+ * element found (-1: none) is written back.
+ * t8gpu_hip_tracers_move: one phase from given k and held (e.g. summed over the ranks of a partitioned run: one rank holds a
+ * point and contributes, the others contribute +0).
+ * t8gpu_hip_tracers_step: both in one launch, from the same device functions: velocity at x (PREDICT) or xs (CORRECT) of the
+ * ACTIVE particles, then the phase. `hint` as above, one array per phase.
+ * One lane per particle, 256-lane workgroups, no atomics, no LDS. Return 0 without a launch for num_points = 0;
+ * hipErrorInvalidValue, before any launch, for what the sampling calls refuse, a phase or side kind outside the codes below, a
+ * periodic side whose opposite side is not periodic, a non-finite dt, a NULL array that would be used. */
+#define T8GPU_TRACER_ACTIVE 0
+#define T8GPU_TRACER_LEFT 1
+#define T8GPU_TRACER_LOST 2
+#define T8GPU_TRACER_PERIODIC 0
+#define T8GPU_TRACER_WALL 1
+#define T8GPU_TRACER_OPEN 2
+#define T8GPU_TRACER_PREDICT 0
+#define T8GPU_TRACER_CORRECT 1
+typedef struct T8gpuTracerSides { int32_t kind[6]; } T8gpuTracerSides;
+int t8gpu_hip_tracers_velocity_f32(int dim, size_t num_points, const double* points, const uint64_t* keys, const int32_t* levels,
+                                   int num_elements, int cells_per_axis, T8gpuVars_f32 state, int32_t* hint, double* k, int32_t* held,
+                                   void* stream);
+int t8gpu_hip_tracers_velocity_f64(int dim, size_t num_points, const double* points, const uint64_t* keys, const int32_t* levels,
+                                   int num_elements, int cells_per_axis, T8gpuVars_f64 state, int32_t* hint, double* k, int32_t* held,
+                                   void* stream);
+int t8gpu_hip_tracers_move(int dim, int phase, size_t num_points, double dt, T8gpuTracerSides sides, const double* k,
+                           const int32_t* held, double* x, double* xs, double* k1, uint8_t* flag, uint8_t* status, void* stream);
+int t8gpu_hip_tracers_step_f32(int dim, int phase, size_t num_points, double dt, T8gpuTracerSides sides, const uint64_t* keys,
+                               const int32_t* levels, int num_elements, int cells_per_axis, T8gpuVars_f32 state, int32_t* hint,
+                               double* x, double* xs, double* k1, uint8_t* flag, uint8_t* status, void* stream);
+int t8gpu_hip_tracers_step_f64(int dim, int phase, size_t num_points, double dt, T8gpuTracerSides sides, const uint64_t* keys,
+                               const int32_t* levels, int num_elements, int cells_per_axis, T8gpuVars_f64 state, int32_t* hint,
+                               double* x, double* xs, double* k1, uint8_t* flag, uint8_t* status, void* stream);
+
 /* ---- time-averaged flow statistics: running sums and what they give (csrc/hip/stats.hip) -------------
  * t8gpu_hip_stats_accumulate: for every owned cell i and slot k, sums[k plane_stride + i] += weight q_k(i), all arithmetic in
  * double whatever float_type is, gamma = 1.4, with m = (m_x, m_y, m_z):

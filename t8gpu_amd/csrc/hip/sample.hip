@@ -21,84 +21,12 @@
 // pixel centres must come out as numpy forms lo + (i + 0.5) (hi - lo) / n: no contraction into fused multiply-adds
 #pragma clang fp contract(off)
 
-namespace t8gpu_hip {
+#include "forest/locate.hpp"      // keys, searches, locate_cell, bad_forest: shared with tracers.hip
 
-constexpr int SAMPLE_D = T8GPU_SAMPLE_DEPTH;
+namespace t8gpu_hip {
 
 template <class T>
 using sample_planes_t = std::conditional_t<std::is_same<T, float>::value, T8gpuSamplePlanes_f32, T8gpuSamplePlanes_f64>;
-
-// ---- keys ---------------------------------------------------------------------------------------------------------------
-// bit b of v (b < 21) to bit 2 b / 3 b
-__device__ __forceinline__ uint64_t spread2(uint32_t v) {
-  uint64_t x = v;
-  x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
-  x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
-  x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
-  x = (x | (x << 2)) & 0x3333333333333333ull;
-  x = (x | (x << 1)) & 0x5555555555555555ull;
-  return x;
-}
-__device__ __forceinline__ uint64_t spread3(uint32_t v) {
-  uint64_t x = v & 0x1FFFFFu;
-  x = (x | (x << 32)) & 0x001F00000000FFFFull;
-  x = (x | (x << 16)) & 0x001F0000FF0000FFull;
-  x = (x | (x << 8)) & 0x100F00F00F00F00Full;
-  x = (x | (x << 4)) & 0x10C30C30C30C30C3ull;
-  x = (x | (x << 2)) & 0x1249249249249249ull;
-  return x;
-}
-template <int DIM>
-__device__ __forceinline__ uint64_t key_of(uint32_t ix, uint32_t iy, uint32_t iz) {
-  if constexpr (DIM == 2)
-    return spread2(ix) | (spread2(iy) << 1);
-  else
-    return spread3(ix) | (spread3(iy) << 1) | (spread3(iz) << 2);
-}
-
-// keys a cell of level l covers
-template <int DIM>
-__device__ __forceinline__ uint64_t span_of(int level) {
-  return 1ull << (DIM * (SAMPLE_D - level));
-}
-
-// number of keys[0, n) that are <= key (STRICT = false: upper bound) or < key (STRICT = true: lower bound). Branch-free: every
-// lane runs the same ceil(log2 n) rounds, and every read is inside [0, n).
-template <bool STRICT>
-__device__ __forceinline__ int count_before(const uint64_t* __restrict__ keys, int n, uint64_t key) {
-  if (n <= 0) return 0;
-  int base = 0, len = n;
-  while (len > 1) {
-    const int      half = len >> 1;
-    const uint64_t k    = keys[base + half];
-    base = (STRICT ? k < key : k <= key) ? base + half : base;
-    len -= half;
-  }
-  const uint64_t k = keys[base];
-  return base + ((STRICT ? k < key : k <= key) ? 1 : 0);
-}
-
-// the in-range test on the doubles themselves: NaN, +-inf, 1e300 and -1e-300 all fail it, and only what passes is converted
-__device__ __forceinline__ bool inside_unit(double x) { return x >= 0.0 && x < 1.0; }
-
-// storage index of the owned cell that holds (x, y, z) under the half-open rule, or -1. SUB: cells per block axis (1 or 4).
-template <int DIM>
-__device__ __forceinline__ int32_t locate_cell(double x, double y, double z, const uint64_t* __restrict__ keys,
-                                               const int32_t* __restrict__ levels, int n, int sub) {
-  if (!(inside_unit(x) && inside_unit(y) && (DIM == 2 || inside_unit(z)))) return -1;
-  const double   scale = (double)(1u << SAMPLE_D);
-  const uint32_t ix = (uint32_t)(x * scale), iy = (uint32_t)(y * scale), iz = DIM == 3 ? (uint32_t)(z * scale) : 0u;
-  const uint64_t key = key_of<DIM>(ix, iy, iz);
-  const int      e   = count_before<false>(keys, n, key) - 1;
-  if (e < 0) return -1;
-  const int l = levels[e];
-  if (key - keys[e] >= span_of<DIM>(l)) return -1;          // (past this rank's last element, or in a gap of its range)
-  if (sub == 1) return e;
-  const int sh = SAMPLE_D - l - 2;
-  int       c  = (int)((ix >> sh) & 3u) + 4 * (int)((iy >> sh) & 3u);
-  if constexpr (DIM == 3) c += 16 * (int)((iz >> sh) & 3u);
-  return e * (DIM == 3 ? 64 : 16) + c;
-}
 
 template <class T>
 __device__ __forceinline__ double plane_value(const sample_planes_t<T>& src, int k, size_t cell) {
@@ -221,11 +149,6 @@ __global__ __launch_bounds__(64) void k_sample_uniform(int L, const uint64_t* __
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
-inline bool bad_forest(int dim, int n, const uint64_t* keys, const int32_t* levels, int sub) {
-  return (dim != 2 && dim != 3) || n < 0 || (sub != 1 && sub != 4) || (n > 0 && (!keys || !levels)) ||
-         (double)n * (sub == 1 ? 1.0 : (dim == 3 ? 64.0 : 16.0)) >= 2147483648.0;
-}
-
 template <class T>
 bool bad_planes(int n_planes, const sample_planes_t<T>& src) {
   if (n_planes < 0 || n_planes > T8GPU_SAMPLE_PLANES) return true;

@@ -387,6 +387,15 @@ class _Solver:
         from . import sample
         return sample.sampler(self).resample_uniform(names, level, step, stream, halo, fill, partial, extra)
 
+    # -- tracer particles (tracers.py): coordinates advected by Heun's method around the flow step --------------
+    def tracers(self, points, stream=None):
+        """A tracers.Tracers of points[M, dim] (a host or device array, taken to float64) on this solver's mesh: predict(dt)
+        before the flow step and correct(dt) after it move them with the velocity m / rho of the holding cell; rebind(new
+        solver) after an adapt. All device arrays are made here, later calls are enqueued without allocation or sync. A mesh that
+        is no SynthMesh raises TypeError, another shape ValueError."""
+        from . import tracers
+        return tracers.Tracers(self, points, stream)
+
     def cfl_timestep(self, cfl=0.7, step=None, dist=None):
         """cfl / max over the cells of (|v| + c) / h, h = vol^(1/dim), from the state itself: needs no stage to have run (a new
         solver, a solver fresh from an adapt). On Cartesian cells h is the edge; on curved cells it is cbrt(volume), not an
