@@ -1,17 +1,25 @@
-"""Adaptation of a running plain-element solver: CompressibleEulerSolver::adapt
-(examples/compressible_euler/solver.cu:243-277) + MeshManager::adapt (t8gpu/mesh/mesh_manager.inl:196-330).
+"""Adaptation of a running solver: CompressibleEulerSolver::adapt (examples/compressible_euler/solver.cu:243-277) +
+MeshManager::adapt (t8gpu/mesh/mesh_manager.inl:196-330), and their Subgrid counterparts (examples/subgrid/solver.inl:327-345,
+t8gpu/mesh/subgrid_mesh_manager.inl).
 
 Indicator and data transfer are HIP kernels behind the C-ABI (estimate_gradient, refinement criteria,
 adapt_variables_and_volume); the forest operations (adapt callback, refine / coarsen, 2:1 balance, the
 old->new correspondence) run on the host in the mesh provider, where the reference calls t8code.
+
+Plain and Subgrid solvers go through one single-rank body (_adapt), one repartition (_Repartition) and one collective body
+(_adapt_collective). The solver supplies what differs between them: like(part), the empty solver of its configuration on
+the new partition, and cell_geometry(), the (dim, cells per element, volumes) that pick and feed the transfer kernel
+(_transfer). The public functions add their defaults and reference criterion, the two Partitioned classes the wire format
+of their state message.
 """
 import ctypes as C
+import time
 
 import numpy as np
 import torch
 
 from . import hip
-from .solver import FLUXES, PlainSolver
+from .solver import FLUXES
 
 
 def refinement_criteria(solver):
@@ -23,6 +31,14 @@ def refinement_criteria(solver):
     crit = torch.empty(solver.N, dtype=solver.dtype, device="cuda")
     hip.call("t8gpu_hip_refinement_criteria", solver.dtype, solver.N, hip.ptr(grad), hip.ptr(solver.planes[25]), hip.ptr(crit), s)
     grad[:solver.N + solver.G].zero_()        # solver.cu:269-270
+    return crit
+
+
+def subgrid_refinement_criteria(solver):
+    """compute_refinement_criteria<Subgrid> (examples/subgrid/solver.inl:329-340); device tensor [N]."""
+    crit = torch.empty(solver.N, dtype=solver.dtype, device="cuda")
+    hip.call("t8gpu_hip_subgrid_refinement_criteria", solver.dtype, solver.rank, solver.N, hip.ptr(solver.planes[5 * solver.next]),
+             hip.ptr(solver.volumes), hip.ptr(crit), hip.stream_ptr())
     return crit
 
 
@@ -108,19 +124,12 @@ class Loehner:
         return cur[:N]
 
 
-def _marks(mesh, crit, threshold, min_level, max_level, family_members_averaged, coarsen_below):
-    """the one-threshold walk of the reference, or (coarsen_below given) the two-threshold one"""
-    if coarsen_below is None:
-        return mesh.marks_from_criteria(crit, threshold, min_level, max_level, family_members_averaged)
-    return mesh.marks_from_criteria(crit, threshold, min_level, max_level, family_members_averaged, coarsen_below=coarsen_below)
-
-
-def _criteria(solver, indicator, halo=None):
-    """the criteria [N] on the device: the reference's (indicator None) or indicator.criteria(); with a `halo` the caller has
+def _criteria(solver, reference, indicator, halo=None):
+    """the criteria [N] on the device: reference(solver) (indicator None) or indicator.criteria(); with a `halo` the caller has
     exchanged the state's ghosts already"""
     if indicator is not None:
         return indicator.criteria(solver, halo, ghosts_current=halo is not None)
-    return subgrid_refinement_criteria(solver) if hasattr(solver, "S") else refinement_criteria(solver)
+    return reference(solver)
 
 
 def _check_carry(carry, solver):
@@ -136,9 +145,16 @@ def _check_carry(carry, solver):
     return carry
 
 
-def _transfer_carry(sums, adapt_dev, n_new, dim, S=1):
-    """sums [P, n_old S] -> [P, n_new S] by the state's own transfer (child = parent, coarsened = mean of the family, kept =
-    copy; S > 1: the subcell rule of Subgrid blocks) through the _f64 transfer entries, five planes a call. The entries'
+def _transfer(adapt_dev, n_new, dim, S, dtype, old, new, vol_old, vol_new):
+    """adapt_variables_and_volume of five planes onto n_new new elements (child = parent, coarsened = mean of the family,
+    kept = copy) for elements of S cells: the plain entry (S == 1) or the block-wise one of Subgrid. old / new: T8gpuVars."""
+    name, sizes = (("t8gpu_hip_adapt_variables_and_volume", (n_new, dim)) if S == 1 else
+                   ("t8gpu_hip_subgrid_adapt_variables_and_volume", (dim, n_new)))
+    hip.call(name, dtype, *sizes, hip.ptr(adapt_dev), old, new, hip.ptr(vol_old), hip.ptr(vol_new), hip.stream_ptr())
+
+
+def _transfer_carry(sums, adapt_dev, n_new, dim, S):
+    """sums [P, n_old S] -> [P, n_new S] by the state's own transfer through the _f64 entries, five planes a call. The entries'
     volume arguments get scratch; a last group of fewer than five planes is filled up with scratch planes."""
     P, n_old = sums.shape[0], sums.shape[1] // S
     groups = (P + 4) // 5
@@ -150,12 +166,7 @@ def _transfer_carry(sums, adapt_dev, n_new, dim, S=1):
         vol_old = torch.ones(max(1, n_old), dtype=torch.float64, device=old.device)
         vol_new = torch.empty(n_new, dtype=torch.float64, device=old.device)
         for g in range(groups):
-            if S == 1:
-                hip.call("t8gpu_hip_adapt_variables_and_volume", torch.float64, n_new, dim, hip.ptr(adapt_dev), hip.vars_of(old, g),
-                         hip.vars_of(new, g), hip.ptr(vol_old), hip.ptr(vol_new), hip.stream_ptr())
-            else:
-                hip.call("t8gpu_hip_subgrid_adapt_variables_and_volume", torch.float64, dim, n_new, hip.ptr(adapt_dev),
-                         hip.vars_of(old, g), hip.vars_of(new, g), hip.ptr(vol_old), hip.ptr(vol_new), hip.stream_ptr())
+            _transfer(adapt_dev, n_new, dim, S, torch.float64, hip.vars_of(old, g), hip.vars_of(new, g), vol_old, vol_new)
     return new[:P]
 
 
@@ -165,38 +176,31 @@ def _hand_over(carry, new_sums, new_solver):
         c.sums, c.solver = t, new_solver
 
 
-def adapt(solver, threshold=10.0, min_level=1, max_level=4, family_members_averaged=4, volume_dim=None, indicator=None,
-          coarsen_below=None, carry=()):
-    """Refine / coarsen the mesh of a single-rank PlainSolver by the reference's criterion and transfer the
-    current solution. Returns the new solver (same dtype, flux, kernel tier, step bookkeeping).
-    indicator (a Loehner): its criteria instead of the reference's, `threshold` the refine threshold; coarsen_below: the
-    coarsen threshold of the two-threshold marks (None: `threshold`, the reference's walk).
-    carry: objects with .sums (float64 device tensor [P, owned_cells]) and .solver, e.g. a stats.Statistics: their sums are
-    transferred like the state and they refer to the new solver afterwards. The return values do not change."""
+def _adapt(solver, reference, keep_stepper, threshold, min_level, max_level, family_members_averaged, volume_dim, indicator,
+           coarsen_below, carry):
+    """adapt() and adapt_subgrid(): criteria, marks, forest adapt, the new partition and its empty solver, the transfer
+    straight into that solver's planes and volumes, the carried sums, one sync."""
     carry = _check_carry(carry, solver)
-    import time
     part = solver.part
-    assert part.nranks == 1, "multi-rank adaptation goes through amr.adapt_partitioned"
+    assert part.nranks == 1, "multi-rank adaptation goes through amr.adapt_partitioned / amr.adapt_subgrid_partitioned"
     mesh = part.mesh
     t0 = time.perf_counter()
-    crit = _criteria(solver, indicator).double().cpu().numpy()
+    crit = _criteria(solver, reference, indicator).double().cpu().numpy()
     t1 = time.perf_counter()
-    marks = _marks(mesh, crit, threshold, min_level, max_level, family_members_averaged, coarsen_below)
+    marks = mesh.marks_from_criteria(crit, threshold, min_level, max_level, family_members_averaged, coarsen_below=coarsen_below)
     new_mesh, adapt_data = mesh.adapt(marks)
-    new_part = new_mesh.partition(0, 1, subgrid=False, normal_dim=part.normal_dim)
+    new_part = new_mesh.partition(0, 1, subgrid=part.subgrid, normal_dim=part.normal_dim)
     t2 = time.perf_counter()
-    dim = mesh.dim if volume_dim is None else volume_dim
-    new = PlainSolver(new_part, solver.dtype, flux_kind=solver.kind, mode=solver.mode, state="zeros",
-                      plan_options=None if solver.plan is None else solver.plan.inherited_options(), inflow_states=solver.inflow_states)
+    new = solver.like(new_part)
     t3 = time.perf_counter()
-    new.next, new.prev = solver.next, solver.prev
+    dim, S, volumes = solver.cell_geometry()
+    dim = dim if volume_dim is None else volume_dim
     ad = torch.from_numpy(adapt_data).cuda()
-    hip.call("t8gpu_hip_adapt_variables_and_volume", solver.dtype, new_part.N, dim, hip.ptr(ad),
-             solver.get_own_variables(solver.next), new.get_own_variables(new.next), hip.ptr(solver.planes[25]),
-             hip.ptr(new.planes[25]), hip.stream_ptr())
-    _hand_over(carry, [_transfer_carry(c.sums, ad, new_part.N, dim) for c in carry], new)
+    _transfer(ad, new_part.N, dim, S, solver.dtype, solver.get_own_variables(solver.next), new.get_own_variables(new.next),
+              volumes, new.cell_geometry()[2])
+    _hand_over(carry, [_transfer_carry(c.sums, ad, new_part.N, dim, S) for c in carry], new)
     torch.cuda.synchronize()
-    if getattr(solver, "stepper", None) is not None:
+    if keep_stepper and solver.stepper is not None:
         new.use_native_stepper()
     t4 = time.perf_counter()
     new.last_adapt_criteria_sum = float(crit.sum())
@@ -209,20 +213,77 @@ def adapt(solver, threshold=10.0, min_level=1, max_level=4, family_members_avera
     return new, marks, adapt_data
 
 
+def adapt(solver, threshold=10.0, min_level=1, max_level=4, family_members_averaged=4, volume_dim=None, indicator=None,
+          coarsen_below=None, carry=()):
+    """Refine / coarsen the mesh of a single-rank PlainSolver by the reference's criterion and transfer the
+    current solution. Returns the new solver (same dtype, flux, kernel tier, step bookkeeping; the native stepper again if
+    the old one had it), the marks and the old -> new correspondence.
+    indicator (a Loehner): its criteria instead of the reference's, `threshold` the refine threshold; coarsen_below: the
+    coarsen threshold of the two-threshold marks (None: `threshold`, the reference's walk).
+    carry: objects with .sums (float64 device tensor [P, owned_cells]) and .solver, e.g. a stats.Statistics: their sums are
+    transferred like the state and they refer to the new solver afterwards. The return values do not change."""
+    return _adapt(solver, refinement_criteria, True, threshold, min_level, max_level, family_members_averaged, volume_dim,
+                  indicator, coarsen_below, carry)
+
+
+def adapt_subgrid(solver, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4, indicator=None, coarsen_below=None,
+                  carry=()):
+    """SubgridCompressibleEulerSolver::adapt (examples/subgrid/solver.inl:327-345) for a single-rank SubgridSolver:
+    H1-seminorm indicator, the forest adapt, block-wise data transfer (subgrid_mesh_manager.inl:246-425).
+    indicator (a Loehner): its block maxima instead, `threshold` the refine threshold; coarsen_below and carry: as for
+    adapt(); carried sums follow the subcell rule of the block transfer."""
+    return _adapt(solver, subgrid_refinement_criteria, False, threshold, min_level, max_level, family_members_averaged, None,
+                  indicator, coarsen_below, carry)
+
+
+def _runs(planes, first, n, S, per_element=()):
+    """the views of elements [first, first + n) of every tensor of `planes` ([P, elements S]) and of `per_element` ([elements])"""
+    return [t[:, first * S:(first + n) * S] for t in planes] + [t[first:first + n] for t in per_element]
+
+
+def _pieces(buf, runs):
+    """the views of the message `buf` that hold `runs` one after the other"""
+    at, out = 0, []
+    for r in runs:
+        out.append(buf[at:at + r.numel()].view(r.shape))
+        at += r.numel()
+    return out
+
+
+def _pack(runs):
+    """one message of the runs, one after the other"""
+    buf = torch.empty(sum(r.numel() for r in runs), dtype=runs[0].dtype, device=runs[0].device)
+    for piece, r in zip(_pieces(buf, runs), runs):
+        piece.copy_(r)
+    return buf
+
+
+def _unpack(buf, runs):
+    for piece, r in zip(_pieces(buf, runs), runs):
+        r.copy_(piece)
+
+
 class _Repartition:
-    """The forest step and message plan of an SFC-partitioned adapt (MeshManager::adapt followed by MeshManager::partition),
-    one rank per GPU. Every rank holds the (cheap) forest description, so the forest operations are replicated and only the
+    """adapt() + partition() of an SFC-partitioned run (MeshManager::adapt followed by MeshManager::partition), one rank per
+    GPU. Every rank holds the (cheap) forest description, so the forest operations are replicated and only the
     element payloads travel: marks that would split a family over two ranks are dropped, the forest is adapted, each rank
     transfers its own elements on the device into temporary planes and ships contiguous runs of them (one message per
     destination) to their owners in the new equal split -- the reference instead lets the new owner PULL through CUDA-IPC
     pointers (partition_data<<<>>>, mesh_manager.inl:626-643). Split in prepare (the constructor) / transport / finish so that
-    the transport can be RCCL (torch.distributed P2P), gloo (CPU tests) or a loopback (one-GPU tests). A subclass packs and
-    unpacks its payload."""
+    the transport can be RCCL (torch.distributed P2P), gloo (CPU tests) or a loopback (one-GPU tests).
 
-    def __init__(self, solver, marks):
+    sends / recvs: (peer, first, count) in the temporary / the new planes. sendbufs / recvbufs[peer]: the state message,
+    5 S + 1 values per element in the solver's type, in the format of the subclass (_pack_state / _unpack_state).
+    carry_sendbufs / carry_recvbufs[peer]: one more message per peer for the objects of `carry` (_check_carry), float64, the
+    objects' runs [P, count S] one after the other; finish() hands the objects over to the new solver."""
+
+    def __init__(self, solver, all_criteria, threshold, min_level, max_level, family_members_averaged, coarsen_below, carry):
+        self.carry = _check_carry(carry, solver)
         part = solver.part
         self.solver, self.rank, self.world = solver, part.rank, part.nranks
         mesh = part.mesh
+        marks = mesh.marks_from_criteria(all_criteria, threshold, min_level, max_level, family_members_averaged,
+                                         coarsen_below=coarsen_below)
         old_off = mesh.partition_offsets(self.world)
         self.marks = mesh.unmark_split_families(marks, old_off[1:-1])
         self.new_mesh, adapt_data = mesh.adapt(self.marks)
@@ -244,58 +305,40 @@ class _Repartition:
             r0, r1 = max(int(self.have_off[q]), lo_r), min(int(self.have_off[q + 1]), hi_r)
             if r1 > r0:
                 self.recvs.append((q, r0 - lo_r, r1 - r0))               # (peer, first in the new planes, count)
+        # 1. local data transfer into temporary planes: one allocation, the state's five planes and the volumes behind them
+        dim, S, volumes = solver.cell_geometry()
+        dtype, dev, room = solver.dtype, solver.planes.device, max(1, self.n_have)
+        tmp = torch.zeros((5 * S + 1) * room, dtype=dtype, device=dev)
+        self.S, self.tmp, self.tmp_vol = S, tmp[:5 * S * room].view(5, S * room), tmp[5 * S * room:]
+        ad_local = torch.from_numpy(self.adapt_local).to(dev)
+        if self.n_have:
+            _transfer(ad_local, self.n_have, dim, S, dtype, solver.get_own_variables(solver.next), hip.vars_of(self.tmp),
+                      volumes, self.tmp_vol)
+        self.carry_tmp = [_transfer_carry(c.sums, ad_local, self.n_have, dim, S) for c in self.carry]
+        # 2. the new partition and an empty solver for it
+        self.new_part = self.new_mesh.partition(self.rank, self.world, subgrid=part.subgrid, normal_dim=part.normal_dim)
+        self.new_solver = solver.like(self.new_part)
+        # 3. the messages
+        out = [(q, first, n) for q, first, n in self.sends if q != self.rank]
+        into = [(q, n) for q, _, n in self.recvs if q != self.rank]
+        self.sendbufs = {q: self._pack_state(first, n) for q, first, n in out}
+        self.recvbufs = {q: torch.empty((5 * S + 1) * n, dtype=dtype, device=dev) for q, n in into}
+        self.carry_sendbufs, self.carry_recvbufs = {}, {}
+        if self.carry:
+            width = sum(t.shape[0] for t in self.carry_tmp) * S
+            self.carry_sendbufs = {q: _pack(_runs(self.carry_tmp, first, n, S)) for q, first, n in out}
+            self.carry_recvbufs = {q: torch.empty(width * n, dtype=torch.float64, device=dev) for q, n in into}
 
     def kept_first(self):
         """first element of the temporary planes that stays on this rank (its receive from itself)"""
         return [f for p, f, m in self.sends if p == self.rank][0]
-
-    def _pack_carry(self, carry, dim, S=1):
-        """The carried payload of the constructor's `carry` (_check_carry): every object's sums transferred on this rank's own
-        elements into temporary planes [P, n_have S], and one extra message per peer beside the state's --
-        carry_sendbufs[q] / carry_recvbufs[q], float64, the objects' runs [P, n S] one after the other. sendbufs / recvbufs
-        keep their contents and sizes."""
-        self.carry = _check_carry(carry, self.solver)
-        self.carry_S = S
-        self.carry_tmp, self.carry_sendbufs, self.carry_recvbufs = [], {}, {}
-        if not self.carry:
-            return
-        dev = self.solver.planes.device
-        ad_local = torch.from_numpy(self.adapt_local).to(dev)
-        self.carry_tmp = [_transfer_carry(c.sums, ad_local, self.n_have, dim, S) for c in self.carry]
-        width = sum(t.shape[0] for t in self.carry_tmp) * S
-        for q, first, n in self.sends:
-            if q != self.rank:
-                self.carry_sendbufs[q] = torch.cat([t[:, first * S:(first + n) * S].reshape(-1) for t in self.carry_tmp])
-        for q, _, n in self.recvs:
-            if q != self.rank:
-                self.carry_recvbufs[q] = torch.empty(width * n, dtype=torch.float64, device=dev)
-
-    def _unpack_carry(self, new):
-        """the carried objects' new sums [P, owned cells of the new partition] from the kept runs and the received messages;
-        the objects then refer to `new`"""
-        if not self.carry:
-            return
-        S = self.carry_S
-        sums = [torch.zeros((t.shape[0], new.owned_cells), dtype=torch.float64, device=t.device) for t in self.carry_tmp]
-        for q, first, n in self.recvs:
-            if q == self.rank:
-                src_first = self.kept_first()
-                for dst, t in zip(sums, self.carry_tmp):
-                    dst[:, first * S:(first + n) * S] = t[:, src_first * S:(src_first + n) * S]
-            else:
-                buf, at = self.carry_recvbufs[q], 0
-                for dst in sums:
-                    size = dst.shape[0] * n * S
-                    dst[:, first * S:(first + n) * S] = buf[at:at + size].view(dst.shape[0], n * S)
-                    at += size
-        _hand_over(self.carry, sums, new)
 
     def transport(self, dist, host_staged=False):
         """host_staged: move the messages through host memory (gloo, which cannot send device buffers). Ships the state's
         messages and, behind them in the same order, the carried ones."""
         torch.cuda.synchronize()
         pairs = [(self.recvbufs, self.sendbufs)]
-        if getattr(self, "carry", ()):
+        if self.carry:
             pairs.append((self.carry_recvbufs, self.carry_sendbufs))
         staged, ops = [], []
         for recvbufs, sendbufs in pairs:
@@ -316,6 +359,24 @@ class _Repartition:
                 for q, b in recvbufs.items():
                     b.copy_(rbuf[q])
 
+    def finish(self):
+        """the new solver with its state, volumes and the carried sums put together from the kept run and the received messages"""
+        new, S = self.new_solver, self.S
+        sums = [torch.zeros((t.shape[0], new.owned_cells), dtype=torch.float64, device=t.device) for t in self.carry_tmp]
+        state, volumes = [new.step_planes(new.next)], [new.cell_geometry()[2]]
+        for q, first, n in self.recvs:
+            if q == self.rank:       # stays here: straight from the temporary planes
+                kept = _runs([self.tmp] + self.carry_tmp, self.kept_first(), n, S, [self.tmp_vol])
+                for dst, src in zip(_runs(state + sums, first, n, S, volumes), kept):
+                    dst.copy_(src)
+            else:
+                self._unpack_state(self.recvbufs[q], first, n)
+                if self.carry:
+                    _unpack(self.carry_recvbufs[q], _runs(sums, first, n, S))
+        _hand_over(self.carry, sums, new)
+        torch.cuda.synchronize()
+        return new
+
 
 class PartitionedAdapt(_Repartition):
     """adapt() + partition() for an SFC-partitioned plain-element run (MeshManager::adapt followed by
@@ -325,51 +386,38 @@ class PartitionedAdapt(_Repartition):
     def __init__(self, solver, all_criteria, threshold=10.0, min_level=1, max_level=4, family_members_averaged=4, indicator=None,
                  coarsen_below=None, carry=()):
         """indicator: where all_criteria came from (adapt_partitioned evaluates it; nothing here depends on it);
-        coarsen_below: the coarsen threshold of the two-threshold marks (None: `threshold`); carry: as for adapt(), shipped
-        in carry_sendbufs / carry_recvbufs (_pack_carry) and handed over by finish()"""
-        part = solver.part
-        super().__init__(solver, _marks(part.mesh, all_criteria, threshold, min_level, max_level, family_members_averaged, coarsen_below))
-        dtype, dev = solver.dtype, solver.planes.device
-        # 1. local data transfer (adapt_variables_and_volume) into 6 temporary planes
-        self.tmp = torch.zeros((6, max(1, self.n_have)), dtype=dtype, device=dev)
-        if self.n_have:
-            if dev.type == "cuda":
-                ad_local = torch.from_numpy(self.adapt_local).to(dev)
-                hip.call("t8gpu_hip_adapt_variables_and_volume", dtype, self.n_have, part.mesh.dim, hip.ptr(ad_local),
-                         solver.get_own_variables(solver.next), hip.vars_of(self.tmp), hip.ptr(solver.planes[25]),
-                         hip.ptr(self.tmp[5]), hip.stream_ptr())
-            else:
-                raise hip.T8gpuHipError("the data transfer kernel needs a GPU")
-        # 2. the new partition and an empty solver for it
-        self.new_part = self.new_mesh.partition(self.rank, self.world, subgrid=False, normal_dim=part.normal_dim)
-        self.new_solver = PlainSolver(self.new_part, dtype, flux_kind=solver.kind, mode=solver.mode,
-                                      state="zeros", inflow_states=solver.inflow_states,
-                                      plan_options=None if solver.plan is None else solver.plan.inherited_options())
-        self.new_solver.next, self.new_solver.prev = solver.next, solver.prev
-        # 3. the messages
-        self.sendbufs = {q: torch.empty(6 * n, dtype=dtype, device=dev) for q, _, n in self.sends if q != self.rank}
-        self.recvbufs = {q: torch.empty(6 * n, dtype=dtype, device=dev) for q, _, n in self.recvs if q != self.rank}
-        s = hip.stream_ptr()
-        for q, first, n in self.sends:
-            if q != self.rank:
-                hip.call("t8gpu_hip_gather_elements", dtype, n, first, hip.vars_of(self.tmp), hip.ptr(self.tmp[5]),
-                         hip.ptr(self.sendbufs[q]), s)
-        self._pack_carry(carry, part.mesh.dim)
+        coarsen_below: the coarsen threshold of the two-threshold marks (None: `threshold`); carry: as for adapt()"""
+        super().__init__(solver, all_criteria, threshold, min_level, max_level, family_members_averaged, coarsen_below, carry)
 
-    def finish(self):
-        new, dtype = self.new_solver, self.solver.dtype
-        s = hip.stream_ptr()
-        nv = new.get_own_variables(new.next)
-        for q, first, n in self.recvs:
-            if q == self.rank:       # stays here: straight from the temporary planes
-                src_first = self.kept_first()
-                new.planes[5 * new.next:5 * new.next + 5, first:first + n] = self.tmp[0:5, src_first:src_first + n]
-                new.planes[25, first:first + n] = self.tmp[5, src_first:src_first + n]
-            else:
-                hip.call("t8gpu_hip_scatter_elements", dtype, n, first, hip.ptr(self.recvbufs[q]), nv, hip.ptr(new.planes[25]), s)
-        self._unpack_carry(new)
-        torch.cuda.synchronize()
-        return new
+    def _pack_state(self, first, n):
+        buf = torch.empty(6 * n, dtype=self.tmp.dtype, device=self.tmp.device)
+        hip.call("t8gpu_hip_gather_elements", buf.dtype, n, first, hip.vars_of(self.tmp), hip.ptr(self.tmp_vol), hip.ptr(buf),
+                 hip.stream_ptr())
+        return buf
+
+    def _unpack_state(self, buf, first, n):
+        new = self.new_solver
+        hip.call("t8gpu_hip_scatter_elements", buf.dtype, n, first, hip.ptr(buf), new.get_own_variables(new.next),
+                 hip.ptr(new.planes[25]), hip.stream_ptr())
+
+
+class PartitionedSubgridAdapt(_Repartition):
+    """adapt() + partition() for an SFC-partitioned Subgrid run (SubgridMeshManager::adapt followed by
+    SubgridMeshManager::partition, t8gpu/mesh/subgrid_mesh_manager.inl:428-558, 1217-1369): the transfer is block-wise
+    injection / mean (subgrid_mesh_manager.inl:246-425), a message is 5 x 4^rank values + one volume per block. A run of
+    blocks is contiguous in every variable plane, so a message is six slices; no gather kernel is needed."""
+
+    def __init__(self, solver, all_criteria, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4, indicator=None,
+                 coarsen_below=None, carry=()):
+        """indicator / coarsen_below / carry: as for PartitionedAdapt"""
+        super().__init__(solver, all_criteria, threshold, min_level, max_level, family_members_averaged, coarsen_below, carry)
+
+    def _pack_state(self, first, n):
+        return _pack(_runs([self.tmp], first, n, self.S, [self.tmp_vol]))
+
+    def _unpack_state(self, buf, first, n):
+        new = self.new_solver
+        _unpack(buf, _runs([new.step_planes(new.next)], first, n, self.S, [new.volumes]))
 
 
 def _gather_criteria(crit, solver, dist, host_staged):
@@ -385,6 +433,24 @@ def _gather_criteria(crit, solver, dist, host_staged):
     return torch.cat([c[:n] for c, n in zip(chunks, sizes)]).cpu().numpy()
 
 
+def _adapt_collective(repartition, reference, reads_ghosts, solver, dist, host_staged, halo, kw):
+    """adapt_partitioned() and adapt_subgrid_partitioned(): the state's ghosts exchanged where the criteria read them
+    (`reads_ghosts`: the reference criterion does; an indicator always does), the criteria of every rank gathered, then
+    prepare / transport / finish of `repartition`."""
+    indicator = kw.get("indicator")
+    if solver.part.nranks > 1 and (reads_ghosts or indicator is not None):
+        if halo is None:
+            from .halo import HaloExchange
+            halo = HaloExchange(solver.part, solver.dtype, dist, overlap=False, stage_through_host=host_staged)
+        halo.exchange(solver.step_planes(solver.next))
+    all_crit = _gather_criteria(_criteria(solver, reference, indicator, halo).double(), solver, dist, host_staged)
+    pa = repartition(solver, all_crit, **kw)
+    pa.transport(dist, host_staged)
+    new = pa.finish()
+    new.last_adapt_criteria_sum = float(all_crit.sum())      # diagnostic: equal (to rounding) for every rank count
+    return new
+
+
 def adapt_partitioned(solver, dist, host_staged=False, halo=None, **kw):
     """Collective: every rank calls it with its own solver; returns the rank's new solver.
     host_staged: collectives and messages through host memory (gloo).
@@ -396,111 +462,7 @@ def adapt_partitioned(solver, dist, host_staged=False, halo=None, **kw):
     number of ranks. indicator= (a Loehner), coarsen_below= and carry= go to PartitionedAdapt; the indicator's buffer passes
     exchange the ghost entries of the criteria through the same `halo`. carry: as for adapt(): every rank's carried objects
     travel with its elements and refer to its new solver afterwards."""
-    if solver.part.nranks > 1:
-        if halo is None:
-            from .halo import HaloExchange
-            halo = HaloExchange(solver.part, solver.dtype, dist, overlap=False, stage_through_host=host_staged)
-        halo.exchange(solver.step_planes(solver.next))
-    all_crit = _gather_criteria(_criteria(solver, kw.get("indicator"), halo).double(), solver, dist, host_staged)
-    pa = PartitionedAdapt(solver, all_crit, **kw)
-    pa.transport(dist, host_staged)
-    new = pa.finish()
-    new.last_adapt_criteria_sum = float(all_crit.sum())      # diagnostic: equal (to rounding) for every rank count
-    return new
-
-
-def subgrid_refinement_criteria(solver):
-    """compute_refinement_criteria<Subgrid> (examples/subgrid/solver.inl:329-340); device tensor [N]."""
-    crit = torch.empty(solver.N, dtype=solver.dtype, device="cuda")
-    hip.call("t8gpu_hip_subgrid_refinement_criteria", solver.dtype, solver.rank, solver.N, hip.ptr(solver.planes[5 * solver.next]),
-             hip.ptr(solver.volumes), hip.ptr(crit), hip.stream_ptr())
-    return crit
-
-
-def adapt_subgrid(solver, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4, indicator=None, coarsen_below=None,
-                  carry=()):
-    """SubgridCompressibleEulerSolver::adapt (examples/subgrid/solver.inl:327-345) for a single-rank SubgridSolver:
-    H1-seminorm indicator, the forest adapt, block-wise data transfer (subgrid_mesh_manager.inl:246-425).
-    indicator (a Loehner): its block maxima instead, `threshold` the refine threshold; coarsen_below and carry: as for
-    adapt(); carried sums follow the subcell rule of the block transfer."""
-    from .solver import SubgridSolver
-    carry = _check_carry(carry, solver)
-    part = solver.part
-    assert part.nranks == 1
-    mesh = part.mesh
-    crit = _criteria(solver, indicator).double().cpu().numpy()
-    marks = _marks(mesh, crit, threshold, min_level, max_level, family_members_averaged, coarsen_below)
-    new_mesh, adapt_data = mesh.adapt(marks)
-    new_part = new_mesh.partition(0, 1, subgrid=True)
-    S = solver.S
-    new = SubgridSolver(new_part, solver.dtype, flux_kind=solver.kind, mode=solver.mode, state=np.zeros((5, new_part.N * S)),
-                        open_boundaries=solver.open_boundaries, inflow_states=solver.inflow_states,
-                        farfield=solver.farfield)
-    new.next, new.prev = solver.next, solver.prev
-    ad = torch.from_numpy(adapt_data).cuda()
-    hip.call("t8gpu_hip_subgrid_adapt_variables_and_volume", solver.dtype, solver.rank, new_part.N, hip.ptr(ad),
-             solver.get_own_variables(solver.next), new.get_own_variables(new.next), hip.ptr(solver.volumes),
-             hip.ptr(new.volumes), hip.stream_ptr())
-    _hand_over(carry, [_transfer_carry(c.sums, ad, new_part.N, solver.rank, S) for c in carry], new)
-    torch.cuda.synchronize()
-    return new, marks, adapt_data
-
-
-class PartitionedSubgridAdapt(_Repartition):
-    """adapt() + partition() for an SFC-partitioned Subgrid run (SubgridMeshManager::adapt followed by
-    SubgridMeshManager::partition, t8gpu/mesh/subgrid_mesh_manager.inl:428-558, 1217-1369): the transfer is block-wise
-    injection / mean (subgrid_mesh_manager.inl:246-425), a message is 5 x 4^rank values + one volume per block. A run of
-    blocks is contiguous in every variable plane, so a message is six slices; no gather kernel is needed."""
-
-    def __init__(self, solver, all_criteria, threshold=0.02, min_level=1, max_level=6, family_members_averaged=4, indicator=None,
-                 coarsen_below=None, carry=()):
-        """indicator / coarsen_below / carry: as for PartitionedAdapt"""
-        from .solver import SubgridSolver
-        part = solver.part
-        super().__init__(solver, _marks(part.mesh, all_criteria, threshold, min_level, max_level, family_members_averaged, coarsen_below))
-        S = self.S = solver.S
-        dtype, dev = solver.dtype, solver.planes.device
-        self.tmp = torch.zeros((5, max(1, self.n_have) * S), dtype=dtype, device=dev)
-        self.tmp_vol = torch.zeros(max(1, self.n_have), dtype=dtype, device=dev)
-        if self.n_have:
-            ad_local = torch.from_numpy(self.adapt_local).to(dev)
-            hip.call("t8gpu_hip_subgrid_adapt_variables_and_volume", dtype, solver.rank, self.n_have, hip.ptr(ad_local),
-                     solver.get_own_variables(solver.next), hip.vars_of(self.tmp), hip.ptr(solver.volumes), hip.ptr(self.tmp_vol),
-                     hip.stream_ptr())
-        self.new_part = self.new_mesh.partition(self.rank, self.world, subgrid=True)
-        tot = self.new_part.N + self.new_part.G
-        self.new_solver = SubgridSolver(self.new_part, dtype, flux_kind=solver.kind, mode=solver.mode, state=np.zeros((5, tot * S)),
-                                        open_boundaries=solver.open_boundaries, inflow_states=solver.inflow_states,
-                                        farfield=solver.farfield)
-        self.new_solver.next, self.new_solver.prev = solver.next, solver.prev
-        w = 5 * S + 1
-        self.sendbufs, self.recvbufs = {}, {}
-        for q, first, n in self.sends:
-            if q != self.rank:
-                buf = torch.empty(w * n, dtype=dtype, device=dev)
-                buf[: 5 * S * n].view(5, n * S).copy_(self.tmp[:, first * S:(first + n) * S])
-                buf[5 * S * n:].copy_(self.tmp_vol[first:first + n])
-                self.sendbufs[q] = buf
-        for q, _, n in self.recvs:
-            if q != self.rank:
-                self.recvbufs[q] = torch.empty(w * n, dtype=dtype, device=dev)
-        self._pack_carry(carry, solver.rank, S)
-
-    def finish(self):
-        new, S = self.new_solver, self.S
-        dst = new.planes[5 * new.next:5 * new.next + 5]
-        for q, first, n in self.recvs:
-            if q == self.rank:
-                src_first = self.kept_first()
-                dst[:, first * S:(first + n) * S] = self.tmp[:, src_first * S:(src_first + n) * S]
-                new.volumes[first:first + n] = self.tmp_vol[src_first:src_first + n]
-            else:
-                buf = self.recvbufs[q]
-                dst[:, first * S:(first + n) * S] = buf[: 5 * S * n].view(5, n * S)
-                new.volumes[first:first + n] = buf[5 * S * n:]
-        self._unpack_carry(new)
-        torch.cuda.synchronize()
-        return new
+    return _adapt_collective(PartitionedAdapt, refinement_criteria, True, solver, dist, host_staged, halo, kw)
 
 
 def adapt_subgrid_partitioned(solver, dist, host_staged=False, halo=None, **kw):
@@ -508,13 +470,4 @@ def adapt_subgrid_partitioned(solver, dist, host_staged=False, halo=None, **kw):
     The reference's criterion reads no other block, so without indicator= nothing is exchanged. A Loehner indicator reads the
     ghost blocks of the `next` state: they are exchanged first, through `halo` (the run's HaloExchange of this partition) or a
     temporary one, as in adapt_partitioned. carry= goes to PartitionedSubgridAdapt, as there."""
-    indicator = kw.get("indicator")
-    if indicator is not None and solver.part.nranks > 1:
-        if halo is None:
-            from .halo import HaloExchange
-            halo = HaloExchange(solver.part, solver.dtype, dist, overlap=False, stage_through_host=host_staged)
-        halo.exchange(solver.step_planes(solver.next))
-    all_crit = _gather_criteria(_criteria(solver, indicator, halo).double(), solver, dist, host_staged)
-    pa = PartitionedSubgridAdapt(solver, all_crit, **kw)
-    pa.transport(dist, host_staged)
-    return pa.finish()
+    return _adapt_collective(PartitionedSubgridAdapt, subgrid_refinement_criteria, False, solver, dist, host_staged, halo, kw)

@@ -119,7 +119,9 @@ class Monitor:
 class _Solver:
     """What PlainSolver and SubgridSolver share: the step roles (`next` / `prev`, solver.h:100-101), the stage loop with its
     halo overlap and both step drivers, and the state monitor. A solver supplies `owned_cells` (the columns of state()),
-    `_units()` (tiles or blocks of its fused plan), `_stage_compat`, `_native_stepper` and `_monitor_geometry()`."""
+    `_units()` (tiles or blocks of its fused plan), `_stage_compat`, `_native_stepper`, and what the monitor and amr.py ask
+    of it: `cell_geometry()` (dim, cells per element, the volume tensor) and `like(part)` (an empty solver of the same
+    configuration on another partition)."""
 
     def __init__(self, part, dtype, flux_kind, mode):
         if not torch.cuda.is_available():
@@ -179,6 +181,14 @@ class _Solver:
         hip.call("t8gpu_hip_plain_inflow_table", self.dtype, hip.ptr(self._states_dev), int(new.shape[0]), hip.ptr(self.inflow_table),
                  hip.stream_ptr(stream))
         self.inflow_states = new
+
+    def _like(self, part, **options):
+        """like(part) of both solvers: what they share of "the same configuration" (dtype, flux kind, mode, inflow states),
+        the class's own `options`, an all-zero state and the step roles. No stepper is attached."""
+        new = type(self)(part, self.dtype, flux_kind=self.kind, mode=self.mode, state="zeros", inflow_states=self.inflow_states,
+                         **options)
+        new.next, new.prev = self.next, self.prev
+        return new
 
     # -- accessors named after the reference API ------------------------------------------------
     def get_own_variables(self, step):
@@ -287,7 +297,7 @@ class _Solver:
         overwritten by the next call."""
         ws, res, _ = self._monitor_buffers()
         s = self.next if step is None else step
-        dim, cells_per_element, volumes = self._monitor_geometry()
+        dim, cells_per_element, volumes = self.cell_geometry()
         hip.call("t8gpu_hip_state_monitor", self.dtype, C.c_size_t(self.owned_cells), cells_per_element, dim,
                  self.get_own_variables(s), hip.ptr(volumes), hip.ptr(ws), hip.ptr(res), hip.stream_ptr(stream))
         return res
@@ -478,10 +488,16 @@ class PlainSolver(_Solver):
         hip.call("t8gpu_hip_rk3_stage", self.dtype, stage, self.N, self.get_own_variables(self.prev), st,
                  self.get_own_variables(dst), fl, hip.ptr(self.planes[25]), hip.fscalar(self.dtype, dt), stream)
 
-    # -- scalar diagnostics of the reference solver, computed on the device -----------------------
-    def _monitor_geometry(self):
+    def cell_geometry(self):
+        """(dim, cells per element, the elements' volumes on the device): for the monitor and the transfer of amr.py"""
         return int(self.part.mesh.dim), 1, self.planes[25]     # (the curved meshes of unstructured.py: dim = 3)
 
+    def like(self, part):
+        """An empty PlainSolver of this one's configuration on `part` (an adapted or repartitioned mesh): dtype, flux kind,
+        mode, inflow states, the options a tile plan hands on, `next` / `prev`; all-zero state, no stepper."""
+        return self._like(part, plan_options=None if self.plan is None else self.plan.inherited_options())
+
+    # -- scalar diagnostics of the reference solver, computed on the device -----------------------
     def compute_integral(self, variable=0, step=None):
         """sum(volume * variable) over the owned elements (CompressibleEulerSolver::compute_integral)."""
         ws, res = self._reduce_buffers()
@@ -545,8 +561,9 @@ class SubgridSolver(_Solver):
         self.owned_cells = part.N * self.S
         self.stride = tot * self.S
         self.planes = torch.zeros((25, self.stride), dtype=dtype, device="cuda")
-        ic = part.kh_initial_state() if state is None else state
-        self.planes[0:5] = _dev(ic, dtype)
+        if not (isinstance(state, str) and state == "zeros"):     # "zeros": as for PlainSolver
+            ic = part.kh_initial_state() if state is None else state
+            self.planes[0:5] = _dev(ic, dtype)
         self.volumes = _dev(part.volumes, dtype)
         self.level_diff = _dev(part.level_diff)
         self.nb_offset = _dev(part.nb_offset)
@@ -578,8 +595,14 @@ class SubgridSolver(_Solver):
                  self.get_own_variables(self.prev), st, self.get_own_variables(dst), fl, hip.ptr(self.volumes),
                  hip.fscalar(self.dtype, dt), stream)
 
-    def _monitor_geometry(self):
+    def cell_geometry(self):
+        """(dim, cells per element, the blocks' volumes on the device): for the monitor and the transfer of amr.py"""
         return self.rank, self.S, self.volumes
+
+    def like(self, part):
+        """An empty SubgridSolver of this one's configuration on `part`: as PlainSolver.like, with open_boundaries and
+        farfield in place of the plan options."""
+        return self._like(part, open_boundaries=self.open_boundaries, farfield=self.farfield)
 
     def compute_integral(self, variable=0, step=None):
         """sum(volume / S * variable) over the owned subcells (SubgridCompressibleEulerSolver::compute_integral,

@@ -7,8 +7,9 @@ import torch
 
 import _oracle as O
 from _gpu import NP, TOL10, perturbed_state, rel_err
+from test_gpu_stats import MESHES, adapt_marks, filled, make_solver, steer, time_step
 from t8gpu_amd import amr, hip
-from t8gpu_amd.solver import PlainSolver
+from t8gpu_amd.solver import PlainSolver, SubgridSolver
 from t8gpu_amd.synth import SynthMesh
 
 pytestmark = pytest.mark.gpu
@@ -274,3 +275,122 @@ def test_partitioned_subgrid_adapt_and_repartition_equals_single_rank(world, dim
                 s.run_stage(k, dt, split=True)
     torch.cuda.synchronize()
     assert torch.equal(torch.cat([n.state() for n in news], dim=1), want.state())
+
+
+class OneRank:
+    """torch.distributed as far as a collective adapt on one rank calls it"""
+
+    @staticmethod
+    def all_gather(chunks, mine):
+        chunks[0].copy_(mine)
+
+
+def twin(source, st, extra):
+    """a solver with the state of `source` now, a Statistics with the sums of `st` and a payload with those of `extra`"""
+    solver = make_solver(source.part, source.dtype, source.state().cpu().numpy())
+    mine = solver.statistics()
+    mine.sums.copy_(st.sums)
+    mine.weight = st.weight
+
+    class Payload:
+        pass
+
+    other = Payload()
+    other.solver, other.sums = solver, extra.sums.clone()
+    return solver, mine, other
+
+
+@pytest.mark.parametrize("loehner", [False, True])
+@pytest.mark.parametrize("subgrid", [False, True])
+@pytest.mark.parametrize("mesh", ["refined-2d", "refined-3d"])
+def test_collective_adapt_on_one_rank_equals_the_single_rank_adapt(mesh, subgrid, loehner):
+    """adapt_partitioned / adapt_subgrid_partitioned with world == 1 (the message plan is one send to itself: everything goes
+    through the temporary planes and the kept run) against adapt / adapt_subgrid on a twin solver: state, volumes and both
+    carried sums bit for bit. Without an indicator the marks are those of test_gpu_stats.py (refined, kept and coarsened
+    elements); with Loehner(buffer=1) they are the indicator's own, thresholds 0.8 / 0.2."""
+    m = MESHES[mesh]()
+    part = m.partition(subgrid=subgrid)
+    assert part.G == 0
+    source = make_solver(part, torch.float64, perturbed_state(part, 31))
+    st, extra = filled(source, 32)
+    a, st_a, extra_a = twin(source, st, extra)
+    b, st_b, extra_b = twin(source, st, extra)
+    if loehner:
+        kw = dict(threshold=0.8, min_level=1, max_level=6, indicator=amr.Loehner(buffer=1), coarsen_below=0.2)
+    else:
+        kw = {}
+        steer(m, adapt_marks(m))
+    single, collective = (amr.adapt_subgrid, amr.adapt_subgrid_partitioned) if subgrid else (amr.adapt, amr.adapt_partitioned)
+    new_a, marks, _ = single(a, carry=(st_a, extra_a), **kw)
+    new_b = collective(b, OneRank, carry=(st_b, extra_b), **kw)
+    assert marks.any() and (new_a.N != part.N if loehner else {-1, 0, 1} <= set(marks.tolist()))     # the mesh changed
+    assert new_a.N == new_b.N and new_a.owned_cells == new_b.owned_cells and new_b is not b
+    assert new_a.last_adapt_criteria_sum == new_b.last_adapt_criteria_sum
+    assert torch.equal(new_a.state(), new_b.state())
+    assert torch.equal(new_a.cell_geometry()[2][:new_a.N], new_b.cell_geometry()[2][:new_b.N])
+    assert st_a.solver is new_a and extra_a.solver is new_a and st_b.solver is new_b and extra_b.solver is new_b
+    assert tuple(st_b.sums.shape) == (15, new_b.owned_cells) and tuple(extra_b.sums.shape) == (7, new_b.owned_cells)
+    assert torch.equal(st_a.sums, st_b.sums) and torch.equal(extra_a.sums, extra_b.sums)
+    assert bool(st_b.sums.any()) and bool(torch.isfinite(new_b.state()).all())
+
+
+def moving_state():
+    rho, v, p = 1.2, (0.4, 0.1, 0.0), 1.1
+    return [rho, rho * v[0], rho * v[1], rho * v[2], p / 0.4 + 0.5 * rho * sum(c * c for c in v)]
+
+
+def like_case(subgrid):
+    """a solver of a configuration that is the default nowhere it can help, on a mesh with open sides"""
+    if subgrid:
+        mesh = SynthMesh(2, 2, 3, band=0.2, sides=(("farfield", 0), ("farfield", 1), "periodic", "periodic"))
+        inflow = np.array([[1.0, 0.0, 0.0, 0.0, 2.5], moving_state()])
+        part = mesh.partition(subgrid=True)
+        solver = SubgridSolver(part, torch.float64, flux_kind=hip.HLL, mode="fused", state=perturbed_state(part, 41),
+                               open_boundaries=True, farfield=True, inflow_states=inflow)
+    else:
+        mesh = SynthMesh(2, 3, 4, band=0.2, sides=(0, "outflow", "periodic", "periodic"))
+        inflow = np.array([moving_state()])
+        part = mesh.partition()
+        solver = PlainSolver(part, torch.float32, flux_kind=hip.HLL, mode="fused", state=perturbed_state(part, 41),
+                             plan_options=dict(fcap=320, irregular=False), inflow_states=inflow)
+        solver.use_native_stepper()
+        assert solver.plan.inherited_options() != PlainSolver(part, torch.float32, mode="fused",
+                                                              inflow_states=inflow).plan.inherited_options()
+    return mesh, part, solver
+
+
+@pytest.mark.parametrize("subgrid", [False, True])
+def test_like_keeps_the_configuration(subgrid):
+    mesh, part, solver = like_case(subgrid)
+    solver.iterate(time_step(part))
+    assert (solver.next, solver.prev) == (3, 0)                           # no longer those of a new solver
+    marks = np.zeros(part.N, np.int8)
+    marks[::5] = 1
+    new_part = mesh.adapt(marks)[0].partition(subgrid=subgrid, normal_dim=part.normal_dim)
+    assert new_part.N != part.N and part.N // 2 <= new_part.N <= 2 * part.N and new_part.G == 0
+    new = solver.like(new_part)
+    assert type(new) is type(solver) and new.part is new_part and new.stepper is None
+    for name in ("dtype", "kind", "mode", "next", "prev", "open_boundaries") + (("farfield",) if subgrid else ()):
+        assert getattr(new, name) == getattr(solver, name), name
+    assert np.array_equal(new.inflow_states, solver.inflow_states) and torch.equal(new.inflow_table, solver.inflow_table)
+    if not subgrid:
+        assert new.plan.inherited_options() == solver.plan.inherited_options()
+    dim, S, volumes = new.cell_geometry()
+    assert (dim, S) == solver.cell_geometry()[:2] and S == new_part.cells_per_element
+    assert torch.equal(volumes[:new_part.N], torch.from_numpy(new_part.volumes[:new_part.N]).to(new.dtype).cuda())
+    assert not bool(new.planes[:25].any())                                # (a PlainSolver's plane 25: the volumes)
+    state = torch.from_numpy(perturbed_state(new_part, 42)).to(new.dtype).cuda()
+    new.step_planes(new.next)[:, :state.shape[1]] = state
+    new.iterate(time_step(new_part))
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(new.state()).all()) and not torch.equal(new.state(), state[:, :new.owned_cells])
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_subgrid_solver_takes_a_zero_state_without_an_upload(dim):
+    part = MESHES[f"refined-{dim}d"]().partition(subgrid=True)
+    S = part.cells_per_element
+    a = SubgridSolver(part, torch.float64, state="zeros")
+    b = SubgridSolver(part, torch.float64, state=np.zeros((5, (part.N + part.G) * S)))
+    assert torch.equal(a.planes, b.planes) and not bool(a.planes.any()) and tuple(a.planes.shape) == (25, part.N * S)
+    assert torch.equal(a.volumes, b.volumes) and a.owned_cells == b.owned_cells
