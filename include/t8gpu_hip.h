@@ -510,7 +510,8 @@ int t8gpu_hip_planes_or_bits_f32(size_t n, const float* const planes[4], uint32_
 int t8gpu_hip_planes_or_bits_f64(size_t n, const double* const planes[4], uint32_t* out4, void* stream);
 /* max over the per-face speed estimates: thrust::reduce(..., maximum) in compute_timestep,
  * examples/compressible_euler/solver.cu:213-217 (the caller all-reduces the scalar across ranks, :218-223,
- * and forms dt = cfl * 0.5^max_level / speed, :225-228). */
+ * and forms dt = cfl * 0.5^max_level / speed, :225-228). Starts from 0 (the result for n = 0 and for data that is all
+ * negative). A NaN among the estimates propagates: the result is NaN wherever in the array it sits. */
 int t8gpu_hip_max_speed_f32(size_t n, const float* speed_estimates, void* workspace, double* result, void* stream);
 int t8gpu_hip_max_speed_f64(size_t n, const double* speed_estimates, void* workspace, double* result, void* stream);
 /* sum of volume * variable over the owned cells: compute_integral, solver.cu:190-211; with
@@ -937,7 +938,11 @@ enum {
   T8GPU_PROBE_LN_MEAN_REF = 5, /* compat tier: the reference formula, IEEE division and library log */
   T8GPU_PROBE_LOG_TAB = 6,     /* the table-driven fp64 log of the plain tile kernels (fp32: same as LOG) */
   T8GPU_PROBE_SQRT_RATIO = 7,  /* sqrt(a / b) through one reciprocal square root (the sound speed of the KEPES flux) */
-  T8GPU_PROBE_DIV_SHARED = 8   /* a / b from a reciprocal that several quotients share */
+  T8GPU_PROBE_DIV_SHARED = 8,  /* a / b from a reciprocal that several quotients share */
+  T8GPU_PROBE_RSQRT = 9,       /* 1 / sqrt(a): the normalisation of the per-face frames of curved meshes */
+  T8GPU_PROBE_RK_SCALE = 10,   /* a / b = dt / vol of the RK update (exact exponent arithmetic where vol is a power of two) */
+  T8GPU_PROBE_LN_MEAN_RS = 11, /* LN_MEAN with s = b + a and its shared reciprocal handed in (no kernel calls this form: probe only) */
+  T8GPU_PROBE_LN_MEAN_INV_RS = 12 /* 1 / (logarithmic mean), same arguments: the form the KEPES flux takes for beta */
 };
 int t8gpu_hip_math_probe_f32(int op, int n, const float* a, const float* b, float* out, void* stream);
 int t8gpu_hip_math_probe_f64(int op, int n, const double* a, const double* b, double* out, void* stream);

@@ -541,7 +541,7 @@ T8_DEV double ln_mean_dlog(double aL, double aR, double dlog) {
   const bool   small = u < 1.0e-4;
   const double num = small ? s * 52.50 : d;
   const double den = small ? t8_fma(u, t8_fma(u, t8_fma(u, 15.0, 21.0), 35.0), 105.0) : dlog;
-  return t8_div(num, den);
+  return d == 0.0 ? aL : t8_div(num, den);   // (the mean of two equal values is that value: (105 a) / 105 is not, for one a in eight)
 }
 // the same with s = aR + aL and its (shared) reciprocal handed in
 T8_DEV double ln_mean_dlog_rs(double aL, double aR, double dlog, double s, double rs) {
@@ -552,7 +552,7 @@ T8_DEV double ln_mean_dlog_rs(double aL, double aR, double dlog, double s, doubl
   const bool   small = u < 1.0e-4;
   const double num = small ? s * 52.50 : d;
   const double den = small ? t8_fma(u, t8_fma(u, t8_fma(u, 15.0, 21.0), 35.0), 105.0) : dlog;
-  return t8_div(num, den);
+  return d == 0.0 ? aL : t8_div(num, den);   // (the mean of two equal values is that value: (105 a) / 105 is not, for one a in eight)
 }
 // 1 / (logarithmic mean), same arguments: den / num in ONE division where 1 / (num / den) takes a division and a reciprocal (the
 // flux needs the mean of beta only through its reciprocal: kernels.inl:60-75, `1 / beta_hat`). num is never 0: it is the
@@ -576,7 +576,7 @@ T8_DEV float ln_mean_dlog(float aL, float aR, float /*dlog*/) {
   const bool  small = u < 1.0e-4f;
   const float num = small ? s * 52.50f : d;
   const float den = small ? t8_fma(u, t8_fma(u, t8_fma(u, 15.0f, 21.0f), 35.0f), 105.0f) : t8_log_fast(t8_div(aR, aL));
-  return t8_div(num, den);
+  return d == 0.0f ? aL : t8_div(num, den);   // (as in fp64: the mean of two equal values is that value)
 }
 
 T8_DEV float ln_mean_dlog_rs(float aL, float aR, float /*dlog*/, float s, float rs) {
@@ -587,7 +587,7 @@ T8_DEV float ln_mean_dlog_rs(float aL, float aR, float /*dlog*/, float s, float 
   const bool  small = u < 1.0e-4f;
   const float num = small ? s * 52.50f : d;
   const float den = small ? t8_fma(u, t8_fma(u, t8_fma(u, 15.0f, 21.0f), 35.0f), 105.0f) : t8_log_fast(t8_div(aR, aL));
-  return t8_div(num, den);
+  return d == 0.0f ? aL : t8_div(num, den);   // (as in fp64: the mean of two equal values is that value)
 }
 T8_DEV float ln_mean_inv_dlog_rs(float aL, float aR, float /*dlog*/, float s, float rs) {
 #pragma clang fp contract(off)

@@ -23,6 +23,22 @@ __global__ void k_math_probe(int op, int n, const T* __restrict__ a, const T* __
     case T8GPU_PROBE_DIV_SHARED: r = t8_div_by(x, y, t8_rcp_shared(y)); break;
     case T8GPU_PROBE_LN_MEAN: r = ln_mean_dlog(x, y, t8_log_fast(y) - t8_log_fast(x)); break;
     case T8GPU_PROBE_LN_MEAN_REF: r = ln_mean_ref<T>(x, y); break;
+    case T8GPU_PROBE_RSQRT: r = t8_rsqrt_fast(x); break;
+    case T8GPU_PROBE_RK_SCALE: r = rk_scale(x, y); break;           // x = dt, y = vol (kernels_fused_patch.hip: `scale`)
+    // the _rs forms with their arguments formed as kepes_core forms them for ln_mean_inv_dlog_rs -- the only one of the two a
+    // kernel calls; ln_mean_dlog_rs has no caller but this probe -- (flux_math.hpp: `bsum = L.beta + R.beta, rbs = t8_rcp_shared(bsum)` and
+    // `ln_mean_inv_dlog_rs(L.beta, R.beta, R.lbeta - L.lbeta, bsum, rbs)`): the sum, ONE shared reciprocal of it, and the
+    // difference of two stored logarithms (prim_from_state keeps t8_log_fast / t8_log_tab values per cell)
+    case T8GPU_PROBE_LN_MEAN_RS: {
+      const T s = x + y, rs = t8_rcp_shared(s);
+      r         = ln_mean_dlog_rs(x, y, t8_log_fast(y) - t8_log_fast(x), s, rs);
+      break;
+    }
+    case T8GPU_PROBE_LN_MEAN_INV_RS: {
+      const T s = x + y, rs = t8_rcp_shared(s);
+      r         = ln_mean_inv_dlog_rs(x, y, t8_log_fast(y) - t8_log_fast(x), s, rs);
+      break;
+    }
     default: r = T(0); break;
   }
   out[i] = r;
@@ -30,7 +46,7 @@ __global__ void k_math_probe(int op, int n, const T* __restrict__ a, const T* __
 
 template <class T>
 int math_probe(int op, int n, const T* a, const T* b, T* out, void* stream) {
-  if (op < 0 || op > T8GPU_PROBE_DIV_SHARED || n < 0 || !a || !out) return static_cast<int>(hipErrorInvalidValue);
+  if (op < 0 || op > T8GPU_PROBE_LN_MEAN_INV_RS || n < 0 || !a || !out) return static_cast<int>(hipErrorInvalidValue);
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_math_probe<T>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), op, n, a, b, out);
   return static_cast<int>(hipGetLastError());

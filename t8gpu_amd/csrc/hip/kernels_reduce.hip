@@ -6,7 +6,9 @@
 //                    vol * u there (solver.cu:190-211; subgrid: examples/subgrid/solver.inl:281-305).
 // Both become a two-level device reduction (grid-stride partials per workgroup -> one workgroup) that
 // writes a device scalar, stays on the stream and is bitwise reproducible (fixed tree, no atomics).
-// The integral accumulates in double whatever float_type is.
+// The integral accumulates in double whatever float_type is. The maximum starts from 0 and PROPAGATES NaN: one NaN speed
+// estimate (a blown-up state) gives a NaN result wherever in the array it sits, so compute_timestep never turns such a
+// state into a finite step on one layout and NaN on another.
 // A third one serves the step driver: the OR of the raw bits of four planes (is a plane all +0?).
 #include <hip/hip_runtime.h>
 
@@ -18,7 +20,8 @@ constexpr int kReduceBlocks = 1024;
 
 struct OpMax {
   static __device__ double identity() { return 0.0; }  // speeds are >= 0; the reference starts from 0 too
-  static __device__ double apply(double a, double b) { return a > b ? a : b; }
+  // a NaN on either side comes out (`a > b ? a : b` alone keeps or drops one depending on which side it arrives)
+  static __device__ double apply(double a, double b) { return (a > b || a != a) ? a : b; }
 };
 struct OpSum {
   static __device__ double identity() { return 0.0; }

@@ -507,14 +507,17 @@ class PlainSolver(_Solver):
         return float(res.item())
 
     def max_speed(self):
-        """max of the per-face wave-speed estimates of the last stage (input of compute_timestep)."""
+        """max of the per-face wave-speed estimates of the last stage (input of compute_timestep). Starts from 0; NaN if any
+        estimate is NaN, wherever it sits."""
         ws, res = self._reduce_buffers()
         hip.call("t8gpu_hip_max_speed", self.dtype, C.c_size_t(self.F + self.B), hip.ptr(self.speed), hip.ptr(ws),
                  hip.ptr(res), hip.stream_ptr())
         return float(res.item())
 
     def compute_timestep(self, cfl=0.7, max_level=None, dist=None):
-        """cfl * 0.5^max_level / max speed (solver.cu:213-229); `dist` all-reduces the maximum over ranks."""
+        """cfl * 0.5^max_level / max speed (solver.cu:213-229); `dist` all-reduces the maximum over ranks. Without `dist`, a NaN
+        speed estimate (a blown-up state) gives NaN, never a finite step; what the all-reduce makes of one rank's NaN is the
+        backend's business and is not pinned."""
         speed = torch.tensor([self.max_speed()], dtype=torch.float64, device="cuda" if dist is None or dist.get_backend() == "nccl" else "cpu")
         if dist is not None:
             dist.all_reduce(speed, op=dist.ReduceOp.MAX)

@@ -155,14 +155,53 @@ def test_signed_zeros_and_equal_neighbours(part, dtype, case):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("value", [1e-300, -0.0], ids=["tiny", "minus_zero"])
 def test_z_momentum_not_all_plus_zero_runs_general(part, dtype, value):
+    planted_z_momentum_runs_general(part, dtype, value, part.N // 2)
+
+
+def planted_z_momentum_runs_general(part, dtype, value, slot):
     st = planar_state(part)
-    st[3, part.N // 2] = value if value == 0 or dtype == torch.float64 else 1e-30     # (1e-300 is 0 in fp32)
+    st[3, slot] = value if value == 0 or dtype == torch.float64 else 1e-30     # (1e-300 is 0 in fp32)
     a, b = make_pair(part, dtype, st)
     assert bits(b.planes[3, :b.owned_cells]).any()
     run_pair(a, b)
     assert b.stepper.planar() == 0
     assert_ran(False)
     assert_same_bits(a, b)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("value", [1e-300, -0.0], ids=["tiny", "minus_zero"])
+@pytest.mark.parametrize("slot", ["first", "last"])
+def test_z_momentum_in_an_edge_slot_runs_general(part, dtype, value, slot):
+    """the same with the value in the first and in the last slot the plan addresses: the ends of the range the reduction reads
+    (its head and tail words; tests/test_gpu_planes_or_bits.py has every position of the reduction alone)"""
+    assert part.G == 0 and part.N > 2
+    planted_z_momentum_runs_general(part, dtype, value, 0 if slot == "first" else part.N + part.G - 1)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("value", [1e-300, -0.0], ids=["tiny", "minus_zero"])
+def test_z_momentum_behind_the_addressed_slots_runs_planar(part, dtype, value):
+    """planes with a stride beyond the slots the plan addresses (a solver with spare capacity): a value in the first slot that is
+    NOT addressed is no cell's z-momentum. The call runs planar, with the bits of the general form, and leaves the value alone."""
+    st = planar_state(part)
+    tot = part.N + part.G
+    a = PlainSolver(part, dtype, mode="fused", state=st, capacity=tot + 3)
+    b = PlainSolver(part, dtype, mode="fused", state=st, capacity=tot + 3)
+    b.use_native_stepper().set_planar(2)
+    assert b.plan.c.n_slots_addressed == tot and b.planes.shape[1] == tot + 3
+    v = value if value == 0 or dtype == torch.float64 else 1e-30
+    for s in (a, b):
+        for k in range(4):                       # the z-momentum plane of every step slot
+            s.planes[5 * k + 3, tot] = v
+    planted = bits(b.planes[3, tot:tot + 1]).clone()
+    assert planted.item() != 0 and not bits(b.planes[3, :tot]).any()
+    run_pair(a, b)
+    assert b.stepper.planar() == 1
+    assert_ran(True)
+    assert_same_bits(a, b)
+    for k in range(4):
+        assert torch.equal(bits(b.planes[5 * k + 3, tot:tot + 1]), planted)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
