@@ -231,16 +231,26 @@ inline void hll_total_flux(const T uL[5], const T uR[5], T F[5], T* speed = null
 // kernels.cu:196-206 / kernels.inl:159-166; wall mirror kernels.cu:371-375 /
 // kernels.inl:169-176; back-rotation kernels.cu:288-290 / kernels.inl:179-186.
 // ---------------------------------------------------------------------------
+// ONE DEPARTURE from the reference: its seed (ny, nz, -nx) is antiparallel to n at n = +-(1, -1, 1) / sqrt 3, where the
+// projection leaves nothing (t1 = -n, t2 = 0 or NaN) and near which the frame loses orthonormality as eps / |r|. Where the
+// squared length before normalisation is below 2^-6 (4.2 degrees around that direction, 0.27 % of all directions) the frame
+// is built from the second seed (nz, -nx, ny) in the same way. Every other normal keeps the reference's arithmetic and bits.
 template <class T>
-inline void face_basis(const T n[3], T t1[3], T t2[3]) {
-  t1[0] = n[1];
-  t1[1] = n[2];
-  t1[2] = -n[0];
+inline T frame_project(const T n[3], T s0, T s1, T s2, T t1[3]) {
+  t1[0] = s0;
+  t1[1] = s1;
+  t1[2] = s2;
   const T dp = n[0] * t1[0] + n[1] * t1[1] + n[2] * t1[2];
   t1[0] -= dp * n[0];
   t1[1] -= dp * n[1];
   t1[2] -= dp * n[2];
-  const T nrm = std::sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
+  return t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2];
+}
+template <class T>
+inline void face_basis(const T n[3], T t1[3], T t2[3]) {
+  T r2 = frame_project<T>(n, n[1], n[2], -n[0], t1);
+  if (r2 < T(0.015625)) r2 = frame_project<T>(n, n[2], -n[0], n[1], t1);
+  const T nrm = std::sqrt(r2);
   t1[0] /= nrm;
   t1[1] /= nrm;
   t1[2] /= nrm;

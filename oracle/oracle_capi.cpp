@@ -47,6 +47,10 @@ extern "C" int oracle_num_threads() {
   extern "C" void oracle_ln_mean_##SUF(int n, const T* aL, const T* aR, T* out) {                                     \
     for (int i = 0; i < n; i++) out[i] = ln_mean<T>(aL[i], aR[i]);                                                    \
   }                                                                                                                   \
+  /* the face frames of n unit normals: normals3, t1, t2 are [n][3] row-major */                                      \
+  extern "C" void oracle_face_basis_##SUF(int n, const T* normals3, T* t1, T* t2) {                                   \
+    for (int i = 0; i < n; i++) face_basis<T>(normals3 + 3 * (size_t)i, t1 + 3 * (size_t)i, t2 + 3 * (size_t)i);      \
+  }                                                                                                                   \
   /* batched face-frame flux: uL,uR,flux are [n][5] row-major; speed [n] or null */                                   \
   extern "C" void oracle_face_frame_flux_##SUF(int kind, int n, const T* uL, const T* uR, T* flux, T* speed) {        \
     for (int i = 0; i < n; i++) {                                                                                     \

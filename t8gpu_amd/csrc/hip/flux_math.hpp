@@ -219,20 +219,37 @@ T8_DEV void axis_basis(int axis, bool positive, T n[3], T t1[3], T t2[3]) {
   }
 }
 
-// face frame (n, t1, t2): kernels.cu:174-193 == kernels.inl:133-156
+// The tangent of a face frame before normalisation: the seed (s0, s1, s2) minus its component along n; returns its squared
+// length |r|^2 = 1 - (n . seed)^2.
+template <class T>
+T8_DEV T frame_project(const T n[3], T s0, T s1, T s2, T t1[3]) {
+#pragma clang fp contract(off)
+  t1[0] = s0;
+  t1[1] = s1;
+  t1[2] = s2;
+  const T dp = n[0] * t1[0] + n[1] * t1[1] + n[2] * t1[2];
+  t1[0] -= dp * n[0];
+  t1[1] -= dp * n[1];
+  t1[2] -= dp * n[2];
+  return t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2];
+}
+// |r|^2 below which a frame takes its second seed (2^-6: a cone of 4.2 degrees around +-(1, -1, 1) / sqrt 3, 0.27 % of directions)
+template <class T>
+constexpr T kFrameSeedSwitch = T(0.015625);
+
+// face frame (n, t1, t2): kernels.cu:174-193 == kernels.inl:133-156, with ONE DEPARTURE from the reference. Its seed
+// (ny, nz, -nx) is antiparallel to n at n = +-(1, -1, 1) / sqrt 3: there the projection leaves nothing (fp32: t1 = -n, t2 = 0,
+// silently; fp64: NaN or the same), and near that direction the frame loses orthonormality as eps / |r|. Where |r|^2 < 2^-6 the
+// frame is built from the second seed (nz, -nx, ny) instead, by the same projection, normalisation and cross product (n . seed
+// = 1/3 at the bad direction, |r|^2 = 8/9). Every other normal keeps the reference's arithmetic and bits.
 // (No contraction: tile_plan.cpp computes the same frame on the host for the geometry dictionary, with separately rounded
 // products; a tile with a dictionary and one without must see the same bits.)
 template <class T>
 T8_DEV void face_basis(const T n[3], T t1[3], T t2[3]) {
 #pragma clang fp contract(off)
-  t1[0] = n[1];
-  t1[1] = n[2];
-  t1[2] = -n[0];
-  const T dp = n[0] * t1[0] + n[1] * t1[1] + n[2] * t1[2];
-  t1[0] -= dp * n[0];
-  t1[1] -= dp * n[1];
-  t1[2] -= dp * n[2];
-  const T nrm = t8_sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
+  T r2 = frame_project<T>(n, n[1], n[2], -n[0], t1);
+  if (r2 < kFrameSeedSwitch<T>) r2 = frame_project<T>(n, n[2], -n[0], n[1], t1);
+  const T nrm = t8_sqrt(r2);
   t1[0] /= nrm;
   t1[1] /= nrm;
   t1[2] /= nrm;
@@ -428,19 +445,15 @@ T8_DEV double t8_rsqrt_fast(double x) {
 // face of a curved mesh has its own normal): the same construction with the normalisation as ONE reciprocal square root and
 // three products instead of an IEEE square root and three IEEE divisions -- 25 VALU instructions instead of 75 in fp64, a tenth
 // of such a face's work. The tangents differ from face_basis()'s in the last bit or two (the flux does not depend on their
-// choice; the dictionary's frames, computed on the host, differ from the device's by as much already:
-// tests/test_gpu_unstructured.py::test_fused_variants_agree_and_conserve); for n = +-e_axis both give the exact frame.
+// choice; the dictionary's frames, computed on the host, differ from the device's by less than 32 eps radians, the limit of
+// tests/test_gpu_frames.py); for n = +-e_axis both give the exact frame. The second seed inside the cone |r|^2 < 2^-6 around
+// +-(1, -1, 1) / sqrt 3 is face_basis()'s (see there: a departure from the reference).
 template <class T>
 T8_DEV void face_basis_fast(const T n[3], T t1[3], T t2[3]) {
 #pragma clang fp contract(off)
-  t1[0] = n[1];
-  t1[1] = n[2];
-  t1[2] = -n[0];
-  const T dp = n[0] * t1[0] + n[1] * t1[1] + n[2] * t1[2];
-  t1[0] -= dp * n[0];
-  t1[1] -= dp * n[1];
-  t1[2] -= dp * n[2];
-  const T inv = t8_rsqrt_fast(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
+  T r2 = frame_project<T>(n, n[1], n[2], -n[0], t1);
+  if (r2 < kFrameSeedSwitch<T>) r2 = frame_project<T>(n, n[2], -n[0], n[1], t1);
+  const T inv = t8_rsqrt_fast(r2);
   t1[0] *= inv;
   t1[1] *= inv;
   t1[2] *= inv;

@@ -378,10 +378,18 @@ uvector<uint16_t> geometry_dictionary(const Mesh& m, std::vector<double>& geo_ta
     double* row = &geo_table[12 * i];
     std::memcpy(row, uniq[i].data(), 32);
     const double* n = row;
-    double t1[3] = {n[1], n[2], -n[0]};
-    const double dp = n[0] * t1[0] + n[1] * t1[1] + n[2] * t1[2];
-    for (int k = 0; k < 3; k++) t1[k] -= dp * n[k];
-    const double nrm = std::sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
+    // (flux_math.hpp: face_basis, bit for bit -- its departure from the reference included: inside the cone |r|^2 < 2^-6 around
+    //  +-(1, -1, 1) / sqrt 3, where the seed (ny, nz, -nx) is nearly antiparallel to n, the second seed (nz, -nx, ny))
+    double t1[3];
+    auto project = [n, &t1](double s0, double s1, double s2) {
+      t1[0] = s0, t1[1] = s1, t1[2] = s2;
+      const double dp = n[0] * t1[0] + n[1] * t1[1] + n[2] * t1[2];
+      for (int k = 0; k < 3; k++) t1[k] -= dp * n[k];
+      return t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2];
+    };
+    double r2 = project(n[1], n[2], -n[0]);
+    if (r2 < 0.015625) r2 = project(n[2], -n[0], n[1]);
+    const double nrm = std::sqrt(r2);
     for (int k = 0; k < 3; k++) row[4 + k] = t1[k] / nrm;
     row[8]  = n[1] * row[6] - n[2] * row[5];
     row[9]  = n[2] * row[4] - n[0] * row[6];

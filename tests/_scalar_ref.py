@@ -1,5 +1,6 @@
 """Host-side references and structured inputs for the GPU tests of the small device routines: the bit-OR of planes
-(test_gpu_planes_or_bits.py), the fast-tier scalar helpers (test_gpu_fastmath.py). Pure numpy: tested without a GPU in
+(test_gpu_planes_or_bits.py), the fast-tier scalar helpers (test_gpu_fastmath.py), the per-cell KEPES record
+(test_gpu_inflow_table.py; its reference alone uses mpmath). Otherwise pure numpy: tested without a GPU in
 test_scalar_ref_host.py. Long double is the 80-bit x87 format here (64-bit mantissa): 2^-11 of a double's rounding."""
 import numpy as np
 
@@ -226,3 +227,151 @@ def ln_mean_inputs(dtype, seed=12):
         aR.append(a.copy())
     aL, aR = np.concatenate(aL), np.concatenate(aR)
     return np.concatenate([aL, aR]), np.concatenate([aR, aL])
+
+
+# ---- the per-cell KEPES record (flux_math.hpp: prim_from_state) -----------------------------------------------------------------
+# Words 5-13 of an inflow-table row (t8gpu_hip.h: T8GPU_INFLOW_WORDS): rho, vx, vy, vz, p, beta, lrho, lbeta, v0.
+PRIM_WORDS = ("rho", "vx", "vy", "vz", "p", "beta", "lrho", "lbeta", "v0")
+DIV_ULP = 2.5                                   # t8_rcp, t8_div: the limit pinned in test_gpu_fastmath.py (fp64 2.0, fp32 2.5)
+LOG_K = {np.float64: 2.0, np.float32: 4.0}      # the logs prim_from_state calls there: fp64 t8_log_tab, fp32 t8_log_fast
+
+
+def prim_reference(states):
+    """The nine quantities from the states AS ROUNDED to their type, evaluated with mpmath at 160 bits and returned as long
+    double arrays (dict by PRIM_WORDS, plus C = E / (p / 0.4), the cancellation factor of the pressure, B = beta |v|^2 and
+    lp = ln p). kappa = 1.4 and 0.4 are the decimal constants."""
+    import mpmath
+    out = {k: [] for k in PRIM_WORDS + ("C", "B", "lp")}
+    with mpmath.workprec(160):
+        kappa, km1, half = mpmath.mpf("1.4"), mpmath.mpf("0.4"), mpmath.mpf("0.5")
+        for s in np.asarray(states):
+            rho, mx, my, mz, E = (mpmath.mpf(float(x)) for x in s)
+            v = (mx / rho, my / rho, mz / rho)
+            v2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2]
+            p = km1 * (E - half * rho * v2)
+            beta = rho / (2 * p)
+            lrho, lp = mpmath.log(rho), mpmath.log(p)
+            vals = dict(rho=rho, vx=v[0], vy=v[1], vz=v[2], p=p, beta=beta, lrho=lrho, lbeta=lrho - lp,
+                        v0=(kappa - (lp - kappa * lrho)) / (kappa - 1) - beta * v2, C=E / (p / km1), B=beta * v2, lp=lp)
+            for k, x in vals.items():
+                out[k].append(LD(mpmath.nstr(x, 30)))
+    return {k: np.array(x, LD) for k, x in out.items()}
+
+
+def prim_bounds(ref, dtype):
+    """Absolute bounds on words 5-13, by PRIM_WORDS, from the operation sequence of prim_from_state. eps = 2^-23 / 2^-52; a
+    rounding is eps / 2 relative, t8_rcp and t8_div DIV_ULP eps, a logarithm LOG_K max(eps |log x|, eps / 2) absolute.
+      rho    copied: 0.
+      v      m * rcp(rho): (DIV_ULP + 0.5) eps = 3 eps relative.
+      ke     = 0.5 (vx^2 + vy^2 + vz^2) by a product and two FMAs: each square 6 eps, three roundings of a sum of positive
+             terms 1.5 eps: 7.5 eps relative.
+      p      = km1 fma(-rho, ke, E): rho ke carries 7.5 eps of itself = 7.5 (C - 1) eps of e = E - rho ke, C = E / e the
+             cancellation factor; the FMA 0.5 eps; km1 = T(1.4) - 1 is 0.5 eps (fp32) / 1 eps (fp64) off 0.4; the product 0.5 eps:
+             (7.5 C + 2) eps relative (C - 1 taken as C).
+      beta   = 0.5 t8_div(rho, p): p's bound + DIV_ULP = (7.5 C + 4.5) eps relative.
+      lrho   LOG_K max(eps |ln rho|, eps / 2) absolute.
+      lp     the same at p, + p's relative bound (d ln p = dp / p); lbeta = lrho - lp: both + 0.5 eps |lbeta|.
+      v0     = fma(-rp, ke, (kappa - fma(-kappa, lrho, lp)) (1 / km1)):
+             s = lp - kappa lrho: lp's bound + 1.4 lrho's bound + 0.5 eps 1.4 |ln rho| (kappa as rounded) + 0.5 eps |s|;
+             kappa - s: + 0.5 eps (1.4 + |kappa - s|); A = (kappa - s) (1 / km1): that / 0.4 + 2 eps |A| (km1 1 eps, its
+             reciprocal and the product 0.5 eps each); rp ke = B = beta |v|^2: (7.5 C + 4.5 + 7.5) eps B; the FMA 0.5 eps |v0|."""
+    e = LD(np.finfo(dtype).eps)
+    k = LD(LOG_K[dtype])
+    C = ref["C"]
+    rel_p = (LD(7.5) * C + 2) * e
+    b = {"rho": np.zeros_like(C)}
+    for w in ("vx", "vy", "vz"):
+        b[w] = (DIV_ULP + LD(0.5)) * e * np.abs(ref[w])
+    b["p"] = rel_p * np.abs(ref["p"])
+    b["beta"] = (rel_p + DIV_ULP * e) * np.abs(ref["beta"])
+    b["lrho"] = k * np.maximum(e * np.abs(ref["lrho"]), e / 2)
+    lp = k * np.maximum(e * np.abs(ref["lp"]), e / 2) + rel_p
+    b["lbeta"] = b["lrho"] + lp + LD(0.5) * e * np.abs(ref["lbeta"])
+    s = ref["lp"] - LD(1.4) * ref["lrho"]
+    err_s = lp + LD(1.4) * b["lrho"] + LD(0.5) * e * LD(1.4) * np.abs(ref["lrho"]) + LD(0.5) * e * np.abs(s)
+    err_d = err_s + LD(0.5) * e * (LD(1.4) + np.abs(LD(1.4) - s))
+    A = (LD(1.4) - s) / LD(0.4)
+    b["v0"] = err_d / LD(0.4) + 2 * e * np.abs(A) + (rel_p + (DIV_ULP + LD(7.5)) * e) * ref["B"] + LD(0.5) * e * np.abs(ref["v0"])
+    return b
+
+
+def _state(dtype, rho, p, v):
+    rho, p, v = np.asarray(rho, np.float64), np.asarray(p, np.float64), np.asarray(v, np.float64)
+    E = p / 0.4 + 0.5 * rho * (v * v).sum(1)
+    return np.concatenate([rho[:, None], rho[:, None] * v, E[:, None]], 1).astype(dtype)
+
+
+def log_table_edges(dtype, seed=5):
+    """200 arguments at the interval edges of t8_log_tab's table: 2^e (1 + i / 128), i = 0 .. 127, the value just below each
+    (the last of the interval before) and just above, e in -20 .. 20; the powers of two are the i = 0 ones (all kept)."""
+    rng = np.random.default_rng(seed)
+    i, ex = rng.integers(1, 128, 138), rng.integers(-20, 21, 138)
+    i[:8] = 127
+    x = np.ldexp(1 + i / 128, ex).astype(dtype)
+    x = np.where(np.arange(138) % 3 == 0, x, np.where(np.arange(138) % 3 == 1, step_ulps(x, -1), step_ulps(x, 1)))
+    pw = np.ldexp(1.0, np.arange(-20, 21)).astype(dtype)
+    out = np.concatenate([pw, step_ulps(pw[::2], -1), x])          # 41 + 21 + 138
+    assert out.size == 200
+    return out
+
+
+def pressure_to_energy(dtype, p):
+    """E of a state AT REST whose device pressure km1 * E is exactly p (km1 = T(1.4) - 1, one rounded product): the quotient
+    rounded, or one of its four neighbours; where none gives p (a product cannot reach every value) the nearest one is kept"""
+    T = np.dtype(dtype).type
+    km1 = T(1.4) - T(1)
+    E0 = (p.astype(LD) / LD(km1)).astype(dtype)
+    best = E0.copy()
+    gap = np.abs((km1 * E0).astype(LD) - p.astype(LD))
+    for j in (-2, -1, 1, 2):
+        Ej = step_ulps(E0, j)
+        g = np.abs((km1 * Ej).astype(LD) - p.astype(LD))
+        best, gap = np.where(g < gap, Ej, best), np.minimum(g, gap)
+    return best
+
+
+def inflow_state_families(dtype, seed=21):
+    """{family: states [200, 5] of `dtype`}: 25 calls of 8 states each."""
+    rng = np.random.default_rng(seed)
+    n = 200
+
+    def logu(lo, hi, k=n):
+        return np.exp(rng.uniform(np.log(lo), np.log(hi), k))
+
+    def directions(k=n):
+        d = rng.standard_normal((k, 3))
+        d /= np.linalg.norm(d, axis=1)[:, None]
+        axis = np.eye(3)[rng.integers(0, 3, k)] * rng.choice([-1.0, 1.0], k)[:, None]
+        return np.where((np.arange(k) % 2 == 0)[:, None], d, axis)          # oblique and single-axis, alternating
+
+    fam = {}
+    # at rest, zero momenta of either sign (every combination of signs occurs; vz = -0 in half of them)
+    s = _state(dtype, logu(0.1, 10), logu(0.1, 10), np.zeros((n, 3)))
+    sign = ((np.arange(n)[:, None] >> np.arange(3)) & 1).astype(bool)
+    s[:, 1:4] = np.where(sign, dtype(-0.0), dtype(0.0))
+    fam["at rest"] = s
+    # Mach 0.1 .. 20: E / e_int = 1 + 0.28 M^2 up to 113
+    rho, p = logu(0.5, 2), logu(0.5, 2)
+    mach = logu(0.1, 20)
+    mach[:2] = 0.1, 20.0
+    fam["Mach 0.1 - 20"] = _state(dtype, rho, p, (mach * np.sqrt(1.4 * p / rho))[:, None] * directions())
+    # rho and p each over 1e-6 .. 1e6, Mach up to 2
+    rho, p = logu(1e-6, 1e6), logu(1e-6, 1e6)
+    rho[:4], p[:4] = (1e-6, 1e-6, 1e6, 1e6), (1e-6, 1e6, 1e-6, 1e6)
+    fam["twelve decades"] = _state(dtype, rho, p, (rng.uniform(0, 2, n) * np.sqrt(1.4 * p / rho))[:, None] * directions())
+    # rho and the DEVICE pressure at powers of two and at the edges of the log table's intervals (at rest: p = km1 * E)
+    edges = log_table_edges(dtype)
+    s = np.zeros((n, 5), dtype)
+    s[:, 0], s[:, 4] = edges, pressure_to_energy(dtype, rng.permutation(edges))
+    fam["table edges"] = s
+    # moving, with one or two momenta a zero of either sign
+    rho, p = logu(0.5, 2), logu(0.5, 2)
+    s = _state(dtype, rho, p, rng.uniform(-1, 1, (n, 3)))
+    zero = ((np.arange(n)[:, None] % 7 + 1) >> np.arange(3)) & 1
+    zero[zero.sum(1) == 3] = (0, 0, 1)
+    s[:, 1:4] = np.where(zero.astype(bool), np.where(sign, dtype(-0.0), dtype(0.0)), s[:, 1:4])
+    s[:, 4] = (p / 0.4 + 0.5 * (s[:, 1:4].astype(np.float64) ** 2).sum(1) / s[:, 0].astype(np.float64)).astype(dtype)
+    fam["signed zeros"] = s
+    for a in fam.values():
+        assert a.shape == (n, 5) and a.dtype == dtype and (a[:, 0] > 0).all() and np.isfinite(a).all()
+    return fam
