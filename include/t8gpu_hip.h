@@ -51,6 +51,21 @@ int         t8gpu_hip_range_pop(void);
  * rocprofv3 prints it (e.g. "k_plain_stage<double, 0, 3>"); "" before the first call. bench.py compares it with the kernels
  * named by the committed profile before it reports that profile's PMC figures. Not thread-safe (one host thread per rank). */
 const char* t8gpu_hip_last_stage_kernel(void);
+/* The grid of that launch in workgroups (ABI 16; 0 before the first call), and launch `index` (0, 1, ... in launch order; at
+ * most the first 8) of the same call: its kernel name and, through `workgroups` (nullable), its grid; NULL past the call's
+ * last launch. Per host thread, like the name. */
+int         t8gpu_hip_last_stage_workgroups(void);
+const char* t8gpu_hip_last_stage_launch(int index, int* workgroups);
+/* A limit on the resident workgroups of the persistent launches, FOR TESTS (ABI 16): the persistent kernels (k_plain_persistent,
+ * k_plain_patch / k_plain_stage, k_plain_patch3 / k_plain_patch3_both) size their grid as min(tiles, resident) with resident =
+ * compute units x workgroups per CU -- hundreds -- so only meshes of benchmark size make a workgroup walk several tiles. With a
+ * limit of `workgroups` > 0 every launcher takes resident = min(compute units x workgroups per CU, workgroups), in its grid and
+ * in every decision that compares a tile count with the resident workgroups (the persistent tile kernel's size rule: a plan of
+ * at least 8 x limit generic tiles takes it; the chunked patch walk; k_plain_patch3_both, which needs a limit >= 16 that is a
+ * multiple of 8 and declines any other). 0 (the default): none -- no launch changes. Returns the previous value. Process-wide
+ * and atomic, read at launch time: it holds for the launches enqueued after the call, from any host thread. A captured graph
+ * keeps the grid it was captured with. t8gpu_hip_plain_persistent_accepts answers under the limit as well: plan while it is 0. */
+int         t8gpu_hip_set_resident_limit(int workgroups);
 
 /* ---- plain elements, reference-dataflow kernels ("compat" tier) ------------------------------- */
 

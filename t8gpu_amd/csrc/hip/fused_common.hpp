@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -29,6 +30,19 @@ inline int env_per_cu(const char* name) {
   const char* env = std::getenv(name);
   const int   v   = env ? std::atoi(env) : 0;
   return (v < 0 || v > 8) ? 0 : v;
+}
+
+// Resident workgroups of a persistent launch: `per_cu` on each of `cus` compute units, or the limit a test has set
+// (t8gpu_hip.h: t8gpu_hip_set_resident_limit; 0 = none) where that is smaller. Every persistent launcher sizes its grid -- and
+// takes its decisions that compare a tile count with the resident workgroups -- through this one function. An atomic, read at
+// launch time: the step driver launches from two host threads.
+inline std::atomic<int>& resident_limit() {
+  static std::atomic<int> limit{0};
+  return limit;
+}
+inline int resident_workgroups(int cus, int per_cu) {
+  const int full = cus * per_cu, limit = resident_limit().load(std::memory_order_relaxed);
+  return limit > 0 && limit < full ? limit : full;
 }
 
 // ---- host side of the fused-stage launchers ---------------------------------------------------------------------

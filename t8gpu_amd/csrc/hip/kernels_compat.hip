@@ -535,7 +535,7 @@ namespace t8gpu_hip {
 StageKernelNote& stage_kernel_note() {
   // per host thread: the step driver's two lanes enqueue from two threads (stepper.hip); the caller's thread -- the one that asks
   // t8gpu_hip_last_stage_kernel -- launches the interior tiles, the bulk of a stage
-  static thread_local StageKernelNote note = {{0}, -1};
+  static thread_local StageKernelNote note = {{0}, -1, 0, 0, {}};
   return note;
 }
 }  // namespace t8gpu_hip
@@ -545,7 +545,15 @@ using namespace t8gpu_hip;
 extern "C" {
 
 const char* t8gpu_hip_last_stage_kernel(void) { return stage_kernel_note().name; }
-int t8gpu_hip_abi_version(void) { return 15; }   // 2: T8gpuPlainPlan.tile_desc; 3: T8gpuSubgridPlan row format (far-cell recipes), n_blocks_addressed, family records; 4: T8gpuPlainPlan.n_patch_tiles; 5: T8gpuPlainPlan.ell holds rows for generic tiles only (tile_desc word 6), patch_dim; 6: T8gpuPlainPlan.n_irregular_tiles; 7: T8gpuPlainPlan ghost window (ghost_buf, send_map, send_list, send_buf, n_owned); 8: t8gpu_hip_plain_geo_frames_* (plan builders must call it); 9: T8gpuPlainPlan open boundaries (inflow, has_open_faces), t8gpu_hip_flux_boundary_bc_*, t8gpu_hip_plain_inflow_table_*; 10: T8gpuSubgridPlan open boundaries (inflow, has_open_faces), t8gpu_hip_subgrid_boundary_bc_*; 11: far-field boundary kinds (T8gpuPlainPlan.has_farfield_faces, face_lr codes 0xFFF8 + k, t8gpu_hip_flux_boundary_bc_* kinds 10..15); 12: far-field kinds on Subgrid blocks (T8gpuSubgridPlan.has_farfield_faces, code bits 23-26 hold 10 + k, t8gpu_hip_subgrid_boundary_far_*); 13: planar 2D stage (t8gpu_hip_plain_fused_stage_planar_*, t8gpu_hip_stepper_set_planar / _planar, t8gpu_hip_planes_or_bits_*); 14: t8gpu_hip_plain_patch_lds_bytes; 15: iterate_steps writes the speed estimates in its last step only (t8gpu_hip_stepper_set_speed_every_step / _speed_stages)
+int t8gpu_hip_last_stage_workgroups(void) { return stage_kernel_note().weight < 0 ? 0 : stage_kernel_note().workgroups; }
+const char* t8gpu_hip_last_stage_launch(int index, int* workgroups) {
+  const StageKernelNote& n = stage_kernel_note();
+  if (index < 0 || index >= n.n_launches || index >= kStageLaunchesNoted) return nullptr;
+  if (workgroups) *workgroups = n.launches[index].workgroups;
+  return n.launches[index].name;
+}
+int t8gpu_hip_set_resident_limit(int workgroups) { return resident_limit().exchange(workgroups > 0 ? workgroups : 0); }
+int t8gpu_hip_abi_version(void) { return 16; }   // 2: T8gpuPlainPlan.tile_desc; 3: T8gpuSubgridPlan row format (far-cell recipes), n_blocks_addressed, family records; 4: T8gpuPlainPlan.n_patch_tiles; 5: T8gpuPlainPlan.ell holds rows for generic tiles only (tile_desc word 6), patch_dim; 6: T8gpuPlainPlan.n_irregular_tiles; 7: T8gpuPlainPlan ghost window (ghost_buf, send_map, send_list, send_buf, n_owned); 8: t8gpu_hip_plain_geo_frames_* (plan builders must call it); 9: T8gpuPlainPlan open boundaries (inflow, has_open_faces), t8gpu_hip_flux_boundary_bc_*, t8gpu_hip_plain_inflow_table_*; 10: T8gpuSubgridPlan open boundaries (inflow, has_open_faces), t8gpu_hip_subgrid_boundary_bc_*; 11: far-field boundary kinds (T8gpuPlainPlan.has_farfield_faces, face_lr codes 0xFFF8 + k, t8gpu_hip_flux_boundary_bc_* kinds 10..15); 12: far-field kinds on Subgrid blocks (T8gpuSubgridPlan.has_farfield_faces, code bits 23-26 hold 10 + k, t8gpu_hip_subgrid_boundary_far_*); 13: planar 2D stage (t8gpu_hip_plain_fused_stage_planar_*, t8gpu_hip_stepper_set_planar / _planar, t8gpu_hip_planes_or_bits_*); 14: t8gpu_hip_plain_patch_lds_bytes; 15: iterate_steps writes the speed estimates in its last step only (t8gpu_hip_stepper_set_speed_every_step / _speed_stages); 16: t8gpu_hip_set_resident_limit, t8gpu_hip_last_stage_workgroups, t8gpu_hip_last_stage_launch
 int t8gpu_hip_device_count(int* count) { return static_cast<int>(hipGetDeviceCount(count)); }
 int t8gpu_hip_set_device(int device) { return static_cast<int>(hipSetDevice(device)); }
 const char* t8gpu_hip_error_string(int code) {

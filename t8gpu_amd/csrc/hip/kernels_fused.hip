@@ -88,22 +88,22 @@ int plain_generic_stage(int kind, int stage, const T8gpuPlainPlan* plan, int til
         if constexpr (FAR && !OPEN) {
           return static_cast<int>(hipErrorInvalidValue);   // (never: `far` implies `open`)
         } else if constexpr (!PIPELINED && FAR) {
-          note_stage_kernel<T>(tile_count, "k_plain_fused_far", K, S);
+          note_stage_kernel<T>(tile_count, grid.x, "k_plain_fused_far", K, S);
           return launch(&k_plain_fused_far<T, K, S>, grid, block, lds, s, *plan, tile_begin, fmk<T>(prev), fmk<T>(mid), fmk<T>(out),
                         volume, dt, speed);
         } else if constexpr (!PIPELINED) {
-          note_stage_kernel<T>(tile_count, "k_plain_fused", K, S, OPEN);
+          note_stage_kernel<T>(tile_count, grid.x, "k_plain_fused", K, S, OPEN);
           return launch(&k_plain_fused<T, K, S, OPEN>, grid, block, lds, s, *plan, tile_begin, fmk<T>(prev), fmk<T>(mid), fmk<T>(out),
                         volume, dt, speed);
         } else if constexpr (FAR) {
           constexpr int  MAXP = FOUR ? 4 : 2;
-          note_stage_kernel<T>(tile_count, "k_plain_fused_p_far", K, S, DICT, MAXP);
+          note_stage_kernel<T>(tile_count, grid.x, "k_plain_fused_p_far", K, S, DICT, MAXP);
           return launch(&k_plain_fused_p_far<T, K, S, DICT, MAXP>, grid, block, lds, s, *plan, tile_begin, fmk<T>(prev), fmk<T>(mid),
                         fmk<T>(out), volume, dt, speed);
         } else {
           constexpr int  MAXP = FOUR ? 4 : 2;
           constexpr bool D    = DENSE && DICT && !FOUR && K == 0 && sizeof(T) == 8;   // (`dense` is never set otherwise)
-          note_stage_kernel<T>(tile_count, "k_plain_fused_p", K, S, DICT, MAXP, D, OPEN);
+          note_stage_kernel<T>(tile_count, grid.x, "k_plain_fused_p", K, S, DICT, MAXP, D, OPEN);
           return launch(&k_plain_fused_p<T, K, S, DICT, MAXP, D, OPEN>, grid, block, lds, s, *plan, tile_begin, fmk<T>(prev), fmk<T>(mid),
                         fmk<T>(out), volume, dt, speed);
         }

@@ -406,7 +406,7 @@ int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch
   // a ghost window (t8gpu_hip.h) is honoured by a workgroup's FIRST patch only (plain_patch_body): one patch per workgroup
   if (plan->ghost_buf || plan->send_map) persistent = false;
   const int  per_cu    = sizeof(T) == 8 ? (four ? 4 : 3) : 5;
-  const int  resident  = cus * per_cu;
+  const int  resident  = resident_workgroups(cus, per_cu);
   // A persistent launch that shares the GPU with the other lane's kernels (the interior launch of a multi-rank stage: the plan
   // has ghost-reading tiles and the range is not the whole plan) must not count on all its workgroups being resident from
   // the start: whatever slots the RCCL kernel and the ghost-reading tiles hold when it is dispatched, that many of its
@@ -430,11 +430,11 @@ int plain_patch_stage(int kind, int stage, const T8gpuPlainPlan* plan, int patch
       [&](auto K, auto S, auto NT, auto MIXED, auto OPEN, auto PLANAR) {
         constexpr bool PL = PLANAR && K == 0;   // (HLL / HLLC: nothing new is instantiated)
         if constexpr (MIXED) {
-          note_stage_kernel<T>(patch_count + tile_count, "k_plain_stage", K, S, NT, OPEN, PL);
+          note_stage_kernel<T>(patch_count + tile_count, grid.x, "k_plain_stage", K, S, NT, OPEN, PL);
           return launch(&k_plain_stage<T, K, S, NT, OPEN, PL>, grid, block, lds, stream, *plan, patch_begin, patch_count, patch_wgs, chunk,
                         tile_begin, tile_count, prev, mid, out, volume, dt, speed);
         } else {
-          note_stage_kernel<T>(patch_count, "k_plain_patch", K, S, NT, PL);
+          note_stage_kernel<T>(patch_count, grid.x, "k_plain_patch", K, S, NT, PL);
           return launch(&k_plain_patch<T, K, S, NT, PL>, grid, block, lds, stream, *plan, patch_begin, patch_count, chunk, prev, mid, out, volume,
                         dt, speed);
         }

@@ -379,13 +379,13 @@ int plain_patch3_stage(int kind, int stage, const T8gpuPlainPlan* plan, int tile
   if (!plan_planes_fit_32bit<T>(plan)) return static_cast<int>(hipErrorInvalidValue);
   const int cus = device_cu_count();
   if (cus == 0) return static_cast<int>(hipErrorInvalidDevice);
-  const int  resident  = cus * (sizeof(T) == 8 ? 2 : 3);
+  const int  resident  = resident_workgroups(cus, sizeof(T) == 8 ? 2 : 3);
   const int  grid_size = (!persistent || tile_count < resident) ? tile_count : resident;
   const dim3 grid(grid_size), block(512);
   const bool nt = stream_hint(plan->n_slots_addressed, sizeof(T));   // (flux_math.hpp: stream_store)
   return dispatch(
       [&](auto K, auto S, auto IRR, auto NT) {
-        note_stage_kernel<T>(tile_count, "k_plain_patch3", K, S, IRR, NT);
+        note_stage_kernel<T>(tile_count, grid.x, "k_plain_patch3", K, S, IRR, NT);
         return launch(&k_plain_patch3<T, K, S, IRR, NT>, grid, block, patch3_lds<T>(kind), stream, *plan, tile_begin, tile_count, prev, mid,
                       out, volume, dt, speed);
       },
@@ -403,8 +403,9 @@ int plain_patch3_both_stage(int kind, int stage, const T8gpuPlainPlan* plan, int
   if (!plan_planes_fit_32bit<T>(plan)) return static_cast<int>(hipErrorInvalidValue);
   const int cus = device_cu_count();
   if (cus == 0) return static_cast<int>(hipErrorInvalidDevice);
-  const int resident = cus * (sizeof(T) == 8 ? 2 : 3);
+  const int resident = resident_workgroups(cus, sizeof(T) == 8 ? 2 : 3);
   if (reg_count + irr_count < 2 * resident) return -1;
+  if (resident < 16 || resident % 8 != 0) return -1;   // (the split below: two shares of at least 8, the regular one a multiple of 8)
   // the resident workgroups in proportion to the work (an irregular patch costs ~1.2 regular ones), the regular share a multiple of 8
   const double w_r = reg_count, w_i = 1.2 * irr_count;
   int reg_wgs = static_cast<int>(resident * w_r / (w_r + w_i) / 8.0 + 0.5) * 8;
@@ -414,7 +415,7 @@ int plain_patch3_both_stage(int kind, int stage, const T8gpuPlainPlan* plan, int
   const bool nt = stream_hint(plan->n_slots_addressed, sizeof(T));   // (flux_math.hpp: stream_store)
   return dispatch(
       [&](auto K, auto S, auto NT) {
-        note_stage_kernel<T>(reg_count + irr_count, "k_plain_patch3_both", K, S, NT);
+        note_stage_kernel<T>(reg_count + irr_count, grid.x, "k_plain_patch3_both", K, S, NT);
         return launch(&k_plain_patch3_both<T, K, S, NT>, grid, block, patch3_lds<T>(kind), stream, *plan, reg_begin, reg_count, reg_wgs,
                       irr_begin, irr_count, prev, mid, out, volume, dt, speed);
       },

@@ -355,7 +355,7 @@ bool plain_persistent_accepts(int kind, const T8gpuPlainPlan* plan, int tile_cou
   // exposed first tile of every workgroup and the ragged last round cost more than the pipelining saves: measured
   // 0.047 vs 0.044 ms per stage, so those launches go back to the one-tile kernel.
   // (fp64 KEPES: small launches too -- there the one-tile kernel has its denser register budget: c1 2 270 -> 2 400 M/s)
-  const int resident = cus * per_cu;
+  const int resident = resident_workgroups(cus, per_cu);   // (a resident limit moves the size rule below with it)
   if (per_cu_env == 0 && tile_count < 8 * resident && (tile_count > resident || (kind == 0 && sizeof(T) == 8))) return false;
   if (lds_out) *lds_out = lds;
   if (resident_out) *resident_out = resident;
@@ -373,7 +373,7 @@ int plain_persistent_stage(int kind, int stage, const T8gpuPlainPlan* plan, int 
   return dispatch(
       [&](auto K, auto S, auto ELL8) {
         constexpr int C = ELL8 ? 1 : 3;   // ELL chunks of 8 entries per element: 1, or (16 / 24 entries) up to 3
-        note_stage_kernel<T>(tile_count, "k_plain_persistent", K, S, C);
+        note_stage_kernel<T>(tile_count, grid.x, "k_plain_persistent", K, S, C);
         return launch(&k_plain_persistent<T, K, S, C>, grid, block, lds, stream, *plan, tile_begin, tile_count, prev, mid, out, volume, dt,
                       speed);
       },

@@ -986,15 +986,15 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
         [&](auto K, auto S, auto RANK3, auto WIDE, auto OPEN, auto FAR) {
           constexpr int R = RANK3 ? 3 : 2;
           if constexpr (OPEN && FAR) {
-            note_stage_kernel<T>(count, "k_subgrid_fused_far", K, S, R, early, WIDE);
+            note_stage_kernel<T>(count, grid.x, "k_subgrid_fused_far", K, S, R, early, WIDE);
             return launch(&k_subgrid_fused_far<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
                           smk<T>(out), volumes, dt);
           } else if constexpr (OPEN) {
-            note_stage_kernel<T>(count, "k_subgrid_fused_open", K, S, R, early, WIDE);
+            note_stage_kernel<T>(count, grid.x, "k_subgrid_fused_open", K, S, R, early, WIDE);
             return launch(&k_subgrid_fused_open<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
                           smk<T>(out), volumes, dt);
           } else {
-            note_stage_kernel<T>(count, "k_subgrid_fused", K, S, R, early, WIDE);
+            note_stage_kernel<T>(count, grid.x, "k_subgrid_fused", K, S, R, early, WIDE);
             return launch(&k_subgrid_fused<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
                           smk<T>(out), volumes, dt);
           }
@@ -1035,17 +1035,17 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
         if constexpr (OPEN && FAR) {
           const char* name   = RANK3 ? "k_subgrid_family_far" : "k_subgrid_family2_far";
           const auto  kernel = RANK3 ? &k_subgrid_family_far<T, K, S, WIDE, NT> : &k_subgrid_family2_far<T, K, S, WIDE, NT>;
-          note_stage_kernel<T>(block_count, name, K, S, WIDE, NT);
+          note_stage_kernel<T>(block_count, grid.x, name, K, S, WIDE, NT);
           return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
         } else if constexpr (OPEN) {   // (the cubes / squares hold no open-face block: the blocks behind them run the OPEN algorithm)
           const char* name   = RANK3 ? "k_subgrid_family_open" : "k_subgrid_family2_open";
           const auto  kernel = RANK3 ? &k_subgrid_family_open<T, K, S, WIDE, NT> : &k_subgrid_family2_open<T, K, S, WIDE, NT>;
-          note_stage_kernel<T>(block_count, name, K, S, WIDE, NT);
+          note_stage_kernel<T>(block_count, grid.x, name, K, S, WIDE, NT);
           return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
         } else {
           const char* name   = RANK3 ? "k_subgrid_family" : "k_subgrid_family2";
           const auto  kernel = RANK3 ? &k_subgrid_family<T, K, S, WIDE, NT> : &k_subgrid_family2<T, K, S, WIDE, NT>;
-          note_stage_kernel<T>(block_count, name, K, S, WIDE, NT);
+          note_stage_kernel<T>(block_count, grid.x, name, K, S, WIDE, NT);
           return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
         }
       },

@@ -1,4 +1,5 @@
 """ctypes mirror of include/t8gpu_hip.h. The HIP library is mandatory: import fails loudly without it."""
+import contextlib
 import ctypes as C
 import os
 
@@ -6,7 +7,7 @@ import numpy as np
 
 from . import build as _build
 
-ABI_VERSION = 15  # t8gpu_hip_abi_version() of include/t8gpu_hip.h: the layout of the plan structs mirrored in fused.py
+ABI_VERSION = 16  # t8gpu_hip_abi_version() of include/t8gpu_hip.h: the layout of the plan structs mirrored in fused.py
 KEPES, HLL, HLLC = 0, 1, 2   # HLLC is an addition: the reference has none
 
 
@@ -89,3 +90,49 @@ def call(name, dtype, *args):
     fn = getattr(lib(), f"{name}_{suffix(dtype)}")
     fn.restype = C.c_int
     check(fn(*args))
+
+
+# -- the stage-kernel note and the resident limit (t8gpu_hip.h; what tests/test_gpu_walks.py drives) -----------------------
+def last_stage_kernel():
+    """name of the kernel that carried most of the last fused-stage call of this thread"""
+    q = lib().t8gpu_hip_last_stage_kernel
+    q.restype = C.c_char_p
+    return (q() or b"").decode()
+
+
+def last_stage_workgroups():
+    """grid of that launch, in workgroups"""
+    q = lib().t8gpu_hip_last_stage_workgroups
+    q.restype = C.c_int
+    return int(q())
+
+
+def last_stage_launches():
+    """[(kernel name, workgroups)] of the launches of that call, in launch order"""
+    q = lib().t8gpu_hip_last_stage_launch
+    q.restype, q.argtypes = C.c_char_p, [C.c_int, C.POINTER(C.c_int)]
+    out, n = [], C.c_int(0)
+    while True:
+        name = q(len(out), C.byref(n))
+        if name is None:
+            return out
+        out.append((name.decode(), int(n.value)))
+
+
+def set_resident_limit(workgroups):
+    """t8gpu_hip_set_resident_limit: at most `workgroups` resident workgroups per persistent launch (0: no limit); returns
+    the previous value"""
+    q = lib().t8gpu_hip_set_resident_limit
+    q.restype, q.argtypes = C.c_int, [C.c_int]
+    return int(q(int(workgroups)))
+
+
+@contextlib.contextmanager
+def resident_limit(workgroups):
+    """`with hip.resident_limit(n):` -- the launches enqueued inside run under the limit; the previous value comes back after.
+    Build plans outside: the planner's rules ask the launcher, which answers under the limit."""
+    before = set_resident_limit(workgroups)
+    try:
+        yield
+    finally:
+        set_resident_limit(before)
