@@ -155,7 +155,8 @@ int t8gpu_hip_subgrid_boundary_bc_f64(int flux_kind, int rank, int num_faces, in
                                       T8gpuVars_f64 fluxes, void* stream);
 /* The same with far-field faces as well (ABI 12): kinds 10 + k take the outside state of the characteristic condition against
  * state k of `inflow_table`, per sub-face from the inside subcell and the block face's outward normal. Kinds of 9
- * and below as t8gpu_hip_subgrid_boundary_bc_*, which keeps its kernel for plans without far-field faces. */
+ * and below as t8gpu_hip_subgrid_boundary_bc_* (bit for bit: one kernel template, whose instantiation behind _bc holds no
+ * far-field code, for plans without far-field faces). */
 int t8gpu_hip_subgrid_boundary_far_f32(int flux_kind, int rank, int num_faces, int num_boundary_faces,
                                        const int32_t* face_neighbors, const uint8_t* boundary_kinds, const float* inflow_table,
                                        const float* face_normals, const float* face_surfaces, T8gpuVars_f32 state,

@@ -71,6 +71,12 @@ int dispatch(F&& f, int kind, int stage, B... flags) {
   };
   return kind == 0 ? with_kind(int_c<0>{}) : kind == 1 ? with_kind(int_c<1>{}) : with_kind(int_c<2>{});
 }
+// its sibling for launchers without a stage (kernels_compat.hip, kernels_boundary.hip): f(int_c<kind>, bool_c<b>...), kind 0..2
+template <class F, class... B>
+int dispatch_kind(F&& f, int kind, B... flags) {
+  auto with_kind = [&](auto K) { return dispatch_flags([&](auto... c) { return f(K, c...); }, flags...); };
+  return kind == 0 ? with_kind(int_c<0>{}) : kind == 1 ? with_kind(int_c<1>{}) : with_kind(int_c<2>{});
+}
 
 // Launches `kernel` with `lds` bytes of dynamic LDS; a kernel is granted more than the default 64 KiB first. Returns 0 or a
 // hipError_t.

@@ -4,8 +4,8 @@
 // are the other half of the budget: change of the integral + dt * boundary flux = 0, stage by stage. The reference has
 // nothing of the kind.
 //
-// Per face the arithmetic is the compat tier's (kernels_compat.hip: k_flux_boundary_bc, k_subgrid_boundary_far): the same
-// routines in the state's float type with contraction off, the outside state by the face's kind. Products with the area
+// Per face the arithmetic is the compat tier's by construction: the routines its boundary kernels call (compat_faces.hpp:
+// boundary_face_flux, sg_inside_cell) in the state's float type with contraction off. Products with the area
 // and every sum are double. Scheme of kernels_monitor.hip: the faces arrive sorted by group (face_order, group_offsets);
 // pass one reduces a contiguous chunk of ONE group's faces per workgroup (wavefront shuffles, then LDS), pass two folds a
 // group's chunk partials in a fixed tree. No atomics: the same data gives the same bits. Slot table: t8gpu_hip.h, DESIGN §13.
@@ -16,6 +16,7 @@
 
 #include <type_traits>
 
+#include "compat_faces.hpp"
 #include "flux_math.hpp"
 #include "fused_common.hpp"
 #include "t8gpu_hip.h"
@@ -90,41 +91,6 @@ __device__ __forceinline__ double boundary_block_reduce(double (&a)[kBndLive]) {
   return r;
 }
 
-// the outside state of a face of kind `kind` (o holds the inside state on entry): k_flux_boundary_bc
-template <class T>
-__device__ __forceinline__ void outside_state(int kind, const T* __restrict__ inflow, const T n[3], T o[5]) {
-  if (kind >= T8GPU_BOUNDARY_FARFIELD) {
-    farfield_state<T>(inflow + T8GPU_INFLOW_WORDS * (kind - T8GPU_BOUNDARY_FARFIELD), n, o);
-  } else if (kind >= 2) {
-#pragma unroll
-    for (int k = 0; k < 5; k++) o[k] = inflow[T8GPU_INFLOW_WORDS * (kind - 2) + k];
-  }
-}
-
-// the inside subcell of sub-face (i, j) of a block face with outward normal n: the left half of the sub-face map of
-// kernels_compat.hip (sg_face_cells, which lives in that file beside its kernels; exact +-1.0 compares)
-template <class T, int RANK>
-__device__ __forceinline__ int inside_subcell(const T n[3], int i, int j) {
-  int al[3] = {0, 0, 0}, si[3] = {0, 0, 0}, sj[3] = {0, 0, 0};
-  if (RANK == 3) {
-    if (n[0] == T(1.0)) { al[0] = 3; si[1] = 1; sj[2] = 1; }
-    if (n[0] == T(-1.0)) { si[1] = 1; sj[2] = 1; }
-    if (n[1] == T(1.0)) { al[1] = 3; si[0] = 1; sj[2] = 1; }
-    if (n[1] == T(-1.0)) { si[0] = 1; sj[2] = 1; }
-    if (n[2] == T(1.0)) { al[2] = 3; si[0] = 1; sj[1] = 1; }
-    if (n[2] == T(-1.0)) { si[0] = 1; sj[1] = 1; }
-  } else {
-    if (n[0] == T(1.0)) { al[0] = 3; si[1] = 1; }
-    if (n[0] == T(-1.0)) { si[1] = 1; }
-    if (n[1] == T(1.0)) { al[1] = 3; si[0] = 1; }
-    if (n[1] == T(-1.0)) { si[0] = 1; }
-  }
-  int lc[3];
-#pragma unroll
-  for (int d = 0; d < 3; d++) lc[d] = al[d] + i * si[d] + j * sj[d];
-  return lc[0] + 4 * lc[1] + 16 * lc[2];
-}
-
 // ---- pass one, plain elements: one lane per boundary face ------------------------------------------------------------
 template <class T, int KIND>
 __global__ __launch_bounds__(kBndLanes) void k_boundary_partial(int F, int ndim, GroupOffsets go, int num_groups,
@@ -145,13 +111,11 @@ __global__ __launch_bounds__(kBndLanes) void k_boundary_partial(int F, int ndim,
     const int    kind = kinds ? kinds[i] : 0;
     T            n[3] = {T(0), T(0), T(0)};
     for (int k = 0; k < ndim; k++) n[k] = normals[(size_t)ndim * slot + k];
-    T s[5], o[5];
+    T s[5];
 #pragma unroll
-    for (int k = 0; k < 5; k++) o[k] = s[k] = st.p[k][e];
-    outside_state<T>(kind, inflow, n, o);
+    for (int k = 0; k < 5; k++) s[k] = st.p[k][e];
     T t1[3], t2[3], Ff[5], g[5], spd;
-    face_basis<T>(n, t1, t2);
-    face_frame_flux_ref<T, KIND>(n, t1, t2, s, o, kind == 0, Ff, spd);
+    boundary_face_flux<T, KIND, true>(n, s, kind, inflow, t1, t2, Ff, spd);
     from_face_frame<T>(n, t1, t2, Ff, g);
     boundary_face<T>(a, (double)areas[slot], g, s, n);
   }
@@ -159,7 +123,7 @@ __global__ __launch_bounds__(kBndLanes) void k_boundary_partial(int F, int ndim,
   if (threadIdx.x < kBndLive) partial[(size_t)blockIdx.x * kBndSlots + threadIdx.x] = r;
 }
 
-// ---- pass one, Subgrid blocks: one lane per sub-face, 256 / SF block faces per workgroup (k_subgrid_boundary_far) -----
+// ---- pass one, Subgrid blocks: one lane per sub-face, 256 / SF block faces per workgroup ------------------------------
 template <class T, int KIND, int RANK>
 __global__ __launch_bounds__(kBndLanes) void k_subgrid_boundary_partial(int F, GroupOffsets go, int num_groups,
                                                                         const int32_t* __restrict__ order,
@@ -184,14 +148,12 @@ __global__ __launch_bounds__(kBndLanes) void k_subgrid_boundary_partial(int F, G
     const int    kind = kinds ? kinds[f] : 0;
     T n[3] = {T(0), T(0), T(0.0)};
     for (int d = 0; d < RANK; d++) n[d] = normals[(size_t)RANK * slot + d];
-    T t1[3], t2[3];
-    face_basis<T>(n, t1, t2);
-    const size_t li = (size_t)l * S + inside_subcell<T, RANK>(n, i, j);
-    T            sl[5], so[5], Ff[5], g[5], spd;
+    int          si[3], sj[3];
+    const size_t li = (size_t)l * S + sg_inside_cell<T, RANK>(n, i, j, si, sj);
+    T            sl[5], t1[3], t2[3], Ff[5], g[5], spd;
 #pragma unroll
-    for (int k = 0; k < 5; k++) so[k] = sl[k] = st.p[k][li];
-    outside_state<T>(kind, inflow, n, so);
-    face_frame_flux_ref<T, KIND>(n, t1, t2, sl, so, kind == 0, Ff, spd);
+    for (int k = 0; k < 5; k++) sl[k] = st.p[k][li];
+    boundary_face_flux<T, KIND, true>(n, sl, kind, inflow, t1, t2, Ff, spd);
     from_face_frame<T>(n, t1, t2, Ff, g);
     boundary_face<T>(a, (double)areas[slot] / SF, g, sl, n);
   }
@@ -248,13 +210,15 @@ int boundary_fluxes(int kind, int F, int B, int ndim, const int32_t* fn, const u
     return static_cast<int>(hipErrorInvalidValue);
   hipStream_t s  = static_cast<hipStream_t>(stream);
   double*     ws = static_cast<double*>(workspace);
-  if (nchunks > 0) {
-    const dim3 grid(nchunks), block(kBndLanes);
-#define T8_BND(K) \
-  hipLaunchKernelGGL((k_boundary_partial<T, K>), grid, block, 0, s, F, ndim, go, num_groups, order, fn, kinds, inflow, normals, areas, st, ws)
-    if (kind == 0) T8_BND(0); else if (kind == 1) T8_BND(1); else T8_BND(2);
-#undef T8_BND
-  }
+  int         rc = 0;
+  if (nchunks > 0)
+    rc = dispatch_kind(
+        [&](auto K) {
+          return launch(&k_boundary_partial<T, K>, dim3(nchunks), dim3(kBndLanes), 0, s, F, ndim, go, num_groups, order, fn, kinds,
+                        inflow, normals, areas, st, ws);
+        },
+        kind);
+  if (rc != 0) return rc;
   hipLaunchKernelGGL(k_boundary_final, dim3(num_groups), dim3(256), 0, s, go, kBndLanes, static_cast<const double*>(ws), result,
                      accumulate, weight);
   return static_cast<int>(hipGetLastError());
@@ -274,17 +238,15 @@ int subgrid_boundary_fluxes(int kind, int rank, int F, int B, const int32_t* fn,
     return static_cast<int>(hipErrorInvalidValue);
   hipStream_t s  = static_cast<hipStream_t>(stream);
   double*     ws = static_cast<double*>(workspace);
-  if (nchunks > 0) {
-    const dim3 grid(nchunks), block(kBndLanes);
-#define T8_SGBND(K, R) \
-  hipLaunchKernelGGL((k_subgrid_boundary_partial<T, K, R>), grid, block, 0, s, F, go, num_groups, order, fn, kinds, inflow, normals, areas, st, ws)
-    if (rank == 3) {
-      if (kind == 0) T8_SGBND(0, 3); else if (kind == 1) T8_SGBND(1, 3); else T8_SGBND(2, 3);
-    } else {
-      if (kind == 0) T8_SGBND(0, 2); else if (kind == 1) T8_SGBND(1, 2); else T8_SGBND(2, 2);
-    }
-#undef T8_SGBND
-  }
+  int         rc = 0;
+  if (nchunks > 0)
+    rc = dispatch_kind(
+        [&](auto K, auto RANK3) {
+          return launch(&k_subgrid_boundary_partial<T, K, RANK3 ? 3 : 2>, dim3(nchunks), dim3(kBndLanes), 0, s, F, go, num_groups,
+                        order, fn, kinds, inflow, normals, areas, st, ws);
+        },
+        kind, rank == 3);
+  if (rc != 0) return rc;
   hipLaunchKernelGGL(k_boundary_final, dim3(num_groups), dim3(256), 0, s, go, per_chunk, static_cast<const double*>(ws), result,
                      accumulate, weight);
   return static_cast<int>(hipGetLastError());

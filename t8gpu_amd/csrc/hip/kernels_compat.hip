@@ -10,6 +10,7 @@
 // Keep the reference's rounding sequence in this tier: no mul+add contraction.
 #pragma clang fp contract(off)
 
+#include "compat_faces.hpp"
 #include "flux_math.hpp"
 #include "fused_common.hpp"
 #include "stage_kernel_note.hpp"
@@ -69,61 +70,26 @@ __global__ __launch_bounds__(256) void k_flux_faces(int F, int ndim, const int32
   }
 }
 
-// ---- a5: reflective wall faces, kernels.cu:311-469 ----------------------------------------------
-template <class T, int KIND>
+// ---- a5: boundary faces, kernels.cu:311-469 (reflective walls) ------------------------------------
+// MODE (compat_faces.hpp: BoundaryMode) = kBndWalls: the reference's kernel, every face a wall, no kinds list or table read;
+// kBndFar: the faces' kinds 0..15 (open boundaries and far field; not in the reference), the same flux against the outside
+// state of the kind (boundary_face_flux).
+template <class T, int KIND, int MODE>
 __global__ __launch_bounds__(256) void k_flux_boundary(int F, int B, int ndim, const int32_t* __restrict__ fn,
+                                                       const uint8_t* __restrict__ kinds, const T* __restrict__ inflow,
                                                        const T* __restrict__ normals, const T* __restrict__ areas,
                                                        Vars<T> st, Vars<T> fl, T* __restrict__ speed) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B) return;
   const T   area = areas[F + i];
   const int e    = fn[2 * (size_t)F + i];
+  const int kind = MODE == kBndWalls ? 0 : kinds[i];
   T         n[3] = {T(0), T(0), T(0)};
   for (int k = 0; k < ndim; k++) n[k] = normals[(size_t)ndim * (F + i) + k];
   T s[5];
   load5(st, e, s);
   T t1[3], t2[3], Ff[5], g[5], spd;
-  face_basis<T>(n, t1, t2);
-  face_frame_flux_ref<T, KIND>(n, t1, t2, s, s, true, Ff, spd);
-  if (speed) speed[F + i] = spd;
-#pragma unroll
-  for (int k = 0; k < 5; k++) Ff[k] = area * Ff[k];
-  from_face_frame<T>(n, t1, t2, Ff, g);
-#pragma unroll
-  for (int k = 0; k < 5; k++) gadd(&fl.p[k][e], -g[k]);
-}
-
-// ---- boundary faces with their kinds (open boundaries; not in the reference) ----------------------
-// The wall flux above with a different outside state: outflow = the inside state unmirrored, inflow k = the conservative
-// state of inflow table entry k (t8gpu_hip.h: T8GPU_INFLOW_WORDS), far field k = the characteristic state against entry k.
-template <class T, int KIND>
-__global__ __launch_bounds__(256) void k_flux_boundary_bc(int F, int B, int ndim, const int32_t* __restrict__ fn,
-                                                          const uint8_t* __restrict__ kinds, const T* __restrict__ inflow,
-                                                          const T* __restrict__ normals, const T* __restrict__ areas,
-                                                          Vars<T> st, Vars<T> fl, T* __restrict__ speed) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  const T   area = areas[F + i];
-  const int e    = fn[2 * (size_t)F + i];
-  const int kind = kinds[i];
-  T         n[3] = {T(0), T(0), T(0)};
-  for (int k = 0; k < ndim; k++) n[k] = normals[(size_t)ndim * (F + i) + k];
-  T s[5], o[5];
-  load5(st, e, s);
-  if (kind >= T8GPU_BOUNDARY_FARFIELD) {   // far field k: the characteristic condition (fused_common.hpp: farfield_outside)
-#pragma unroll
-    for (int k = 0; k < 5; k++) o[k] = s[k];
-    farfield_state<T>(inflow + T8GPU_INFLOW_WORDS * (kind - T8GPU_BOUNDARY_FARFIELD), n, o);
-  } else if (kind >= 2) {
-#pragma unroll
-    for (int k = 0; k < 5; k++) o[k] = inflow[T8GPU_INFLOW_WORDS * (kind - 2) + k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 5; k++) o[k] = s[k];
-  }
-  T t1[3], t2[3], Ff[5], g[5], spd;
-  face_basis<T>(n, t1, t2);
-  face_frame_flux_ref<T, KIND>(n, t1, t2, s, o, kind == 0, Ff, spd);
+  boundary_face_flux<T, KIND, MODE == kBndFar>(n, s, kind, inflow, t1, t2, Ff, spd);
   if (speed) speed[F + i] = spd;
 #pragma unroll
   for (int k = 0; k < 5; k++) Ff[k] = area * Ff[k];
@@ -213,39 +179,10 @@ __global__ __launch_bounds__(64) void k_subgrid_inner(int N, Vars<T> st, Vars<T>
   }
 }
 
-// sub-face -> cell map of compute_outer_fluxes, kernels.inl:710-758 / 837-866 (exact +-1.0 compares)
-template <class T, int RANK>
-T8_DEV void sg_face_cells(const T n[3], const int off[3], int ds, int i, int j, int& lflat, int& rflat) {
-  int al[3] = {0, 0, 0}, si[3] = {0, 0, 0}, sj[3] = {0, 0, 0};
-  if (RANK == 3) {
-    if (n[0] == T(1.0)) { al[0] = 3; si[1] = 1; sj[2] = 1; }
-    if (n[0] == T(-1.0)) { si[1] = 1; sj[2] = 1; }
-    if (n[1] == T(1.0)) { al[1] = 3; si[0] = 1; sj[2] = 1; }
-    if (n[1] == T(-1.0)) { si[0] = 1; sj[2] = 1; }
-    if (n[2] == T(1.0)) { al[2] = 3; si[0] = 1; sj[1] = 1; }
-    if (n[2] == T(-1.0)) { si[0] = 1; sj[1] = 1; }
-  } else {
-    if (n[0] == T(1.0)) { al[0] = 3; si[1] = 1; }
-    if (n[0] == T(-1.0)) { si[1] = 1; }
-    if (n[1] == T(1.0)) { al[1] = 3; si[0] = 1; }
-    if (n[1] == T(-1.0)) { si[0] = 1; }
-  }
-  int lc[3], rc[3];
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    lc[d] = al[d] + i * si[d] + j * sj[d];
-    rc[d] = off[d] + ds * (i * si[d] + j * sj[d]) / 2;
-  }
-  lflat = lc[0] + 4 * lc[1] + 16 * lc[2];
-  rflat = rc[0] + 4 * rc[1] + 16 * rc[2];
-}
-
-// ---- a14 / a15: outer and wall faces of blocks, kernels.inl:664-911 / 913-1107 --------------------
-// SF = sub-faces per coarse face (16 or 4); 64/SF coarse faces share one wavefront. WALL selects
-// the reflective variant (boundary slices start after the F interior entries).
-template <class T, int KIND, int RANK, bool WALL>
-__global__ __launch_bounds__(64) void k_subgrid_faces(int F, int count, const int32_t* __restrict__ fn,
-                                                      const int32_t* __restrict__ idx,
+// ---- a14: outer faces of blocks, kernels.inl:664-911 ---------------------------------------------
+// SF = sub-faces per coarse face (16 or 4); 64/SF coarse faces share one wavefront.
+template <class T, int KIND, int RANK>
+__global__ __launch_bounds__(64) void k_subgrid_faces(int F, const int32_t* __restrict__ fn, const int32_t* __restrict__ idx,
                                                       const int32_t* __restrict__ level_diff,
                                                       const int32_t* __restrict__ nb_off,
                                                       const T* __restrict__ normals, const T* __restrict__ areas,
@@ -253,25 +190,18 @@ __global__ __launch_bounds__(64) void k_subgrid_faces(int F, int count, const in
   constexpr int S  = RANK == 3 ? 64 : 16;
   constexpr int SF = RANK == 3 ? 16 : 4;
   const int     f  = blockIdx.x * (64 / SF) + threadIdx.x / SF;
-  if (f >= count) return;
-  const int    t    = threadIdx.x % SF;
-  const int    i    = t % 4, j = t / 4;
-  const size_t slot = WALL ? (size_t)F + f : (size_t)f;
-  int          l, r = 0, ds = 2, off[3] = {0, 0, 0};
-  if (WALL) {
-    l = fn[2 * (size_t)F + f];
-  } else {
-    l = fn[2 * (size_t)f];
-    r = fn[2 * (size_t)f + 1];
-    if (idx) {
-      l = idx[l];
-      r = idx[r];
-    }
-    ds = (level_diff[f] == 0) ? 2 : 1;
-    for (int d = 0; d < RANK; d++) off[d] = nb_off[(size_t)RANK * f + d];
+  if (f >= F) return;
+  const int t = threadIdx.x % SF;
+  const int i = t % 4, j = t / 4;
+  int       l = fn[2 * (size_t)f], r = fn[2 * (size_t)f + 1], off[3] = {0, 0, 0};
+  if (idx) {
+    l = idx[l];
+    r = idx[r];
   }
+  const int ds = (level_diff[f] == 0) ? 2 : 1;
+  for (int d = 0; d < RANK; d++) off[d] = nb_off[(size_t)RANK * f + d];
   T n[3] = {T(0), T(0), T(0.0)};
-  for (int d = 0; d < RANK; d++) n[d] = normals[(size_t)RANK * slot + d];
+  for (int d = 0; d < RANK; d++) n[d] = normals[(size_t)RANK * f + d];
   T t1[3], t2[3];
   face_basis<T>(n, t1, t2);
   int lflat, rflat;
@@ -280,25 +210,26 @@ __global__ __launch_bounds__(64) void k_subgrid_faces(int F, int count, const in
   const size_t ri = (size_t)r * S + rflat;
   T            sl[5], sr[5], Ff[5], g[5], spd;
   load5(st, li, sl);
-  if (!WALL) load5(st, ri, sr);
-  face_frame_flux_ref<T, KIND>(n, t1, t2, sl, WALL ? sl : sr, WALL, Ff, spd);
+  load5(st, ri, sr);
+  face_frame_flux_ref<T, KIND>(n, t1, t2, sl, sr, false, Ff, spd);
   from_face_frame<T>(n, t1, t2, Ff, g);
-  const T surface = areas[slot] / static_cast<T>(SF);
+  const T surface = areas[f] / static_cast<T>(SF);
 #pragma unroll
   for (int k = 0; k < 5; k++) {
     gadd(&fl.p[k][li], -g[k] * surface);
-    if (!WALL) gadd(&fl.p[k][ri], g[k] * surface);
+    gadd(&fl.p[k][ri], g[k] * surface);
   }
 }
 
-// ---- boundary faces of blocks with their kinds (open boundaries; not in the reference) -------------
-// The wall kernel above with a different outside state: outflow = the inside subcell's state unmirrored, inflow k = the
-// conservative state of inflow table entry k (t8gpu_hip.h: T8GPU_INFLOW_WORDS, words 0-4); walls as above.
-template <class T, int KIND, int RANK>
-__global__ __launch_bounds__(64) void k_subgrid_boundary_bc(int F, int B, const int32_t* __restrict__ fn,
-                                                            const uint8_t* __restrict__ kinds, const T* __restrict__ inflow,
-                                                            const T* __restrict__ normals, const T* __restrict__ areas,
-                                                            Vars<T> st, Vars<T> fl) {
+// ---- a15: boundary faces of blocks, kernels.inl:913-1107 (reflective walls) ------------------------
+// The boundary slices start after the F interior entries. MODE (compat_faces.hpp: BoundaryMode) = kBndWalls: the reference's
+// kernel; kBndOpen: the faces' kinds 0..9 (not in the reference), for plans without far-field faces -- no far-field code;
+// kBndFar: kinds 0..15, the outside state of every sub-face from its inside subcell and the block face's outward normal.
+template <class T, int KIND, int RANK, int MODE>
+__global__ __launch_bounds__(64) void k_subgrid_boundary(int F, int B, const int32_t* __restrict__ fn,
+                                                         const uint8_t* __restrict__ kinds, const T* __restrict__ inflow,
+                                                         const T* __restrict__ normals, const T* __restrict__ areas,
+                                                         Vars<T> st, Vars<T> fl) {
   constexpr int S  = RANK == 3 ? 64 : 16;
   constexpr int SF = RANK == 3 ? 16 : 4;
   const int     f  = blockIdx.x * (64 / SF) + threadIdx.x / SF;
@@ -307,67 +238,14 @@ __global__ __launch_bounds__(64) void k_subgrid_boundary_bc(int F, int B, const 
   const int    i    = t % 4, j = t / 4;
   const size_t slot = (size_t)F + f;
   const int    l    = fn[2 * (size_t)F + f];
-  const int    kind = kinds[f];
-  const int    off[3] = {0, 0, 0};
+  const int    kind = MODE == kBndWalls ? 0 : kinds[f];
   T n[3] = {T(0), T(0), T(0.0)};
   for (int d = 0; d < RANK; d++) n[d] = normals[(size_t)RANK * slot + d];
-  T t1[3], t2[3];
-  face_basis<T>(n, t1, t2);
-  int lflat, rflat;
-  sg_face_cells<T, RANK>(n, off, 2, i, j, lflat, rflat);
-  const size_t li = (size_t)l * S + lflat;
-  T            sl[5], so[5], Ff[5], g[5], spd;
+  int          si[3], sj[3];
+  const size_t li = (size_t)l * S + sg_inside_cell<T, RANK>(n, i, j, si, sj);
+  T            sl[5], t1[3], t2[3], Ff[5], g[5], spd;
   load5(st, li, sl);
-  if (kind >= 2) {
-#pragma unroll
-    for (int k = 0; k < 5; k++) so[k] = inflow[T8GPU_INFLOW_WORDS * (kind - 2) + k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 5; k++) so[k] = sl[k];
-  }
-  face_frame_flux_ref<T, KIND>(n, t1, t2, sl, so, kind == 0, Ff, spd);
-  from_face_frame<T>(n, t1, t2, Ff, g);
-  const T surface = areas[slot] / static_cast<T>(SF);
-#pragma unroll
-  for (int k = 0; k < 5; k++) gadd(&fl.p[k][li], -g[k] * surface);
-}
-
-// The same with far-field faces (kinds 10 + k) as well: the outside state of every sub-face from the characteristic condition
-// against table entry k, the inside subcell and the block face's outward normal (fused_common.hpp: farfield_state, the routine
-// of k_flux_boundary_bc). A kernel of its own: k_subgrid_boundary_bc keeps its code for plans without far-field faces.
-template <class T, int KIND, int RANK>
-__global__ __launch_bounds__(64) void k_subgrid_boundary_far(int F, int B, const int32_t* __restrict__ fn,
-                                                             const uint8_t* __restrict__ kinds, const T* __restrict__ inflow,
-                                                             const T* __restrict__ normals, const T* __restrict__ areas,
-                                                             Vars<T> st, Vars<T> fl) {
-  constexpr int S  = RANK == 3 ? 64 : 16;
-  constexpr int SF = RANK == 3 ? 16 : 4;
-  const int     f  = blockIdx.x * (64 / SF) + threadIdx.x / SF;
-  if (f >= B) return;
-  const int    t    = threadIdx.x % SF;
-  const int    i    = t % 4, j = t / 4;
-  const size_t slot = (size_t)F + f;
-  const int    l    = fn[2 * (size_t)F + f];
-  const int    kind = kinds[f];
-  const int    off[3] = {0, 0, 0};
-  T n[3] = {T(0), T(0), T(0.0)};
-  for (int d = 0; d < RANK; d++) n[d] = normals[(size_t)RANK * slot + d];
-  T t1[3], t2[3];
-  face_basis<T>(n, t1, t2);
-  int lflat, rflat;
-  sg_face_cells<T, RANK>(n, off, 2, i, j, lflat, rflat);
-  const size_t li = (size_t)l * S + lflat;
-  T            sl[5], so[5], Ff[5], g[5], spd;
-  load5(st, li, sl);
-#pragma unroll
-  for (int k = 0; k < 5; k++) so[k] = sl[k];
-  if (kind >= T8GPU_BOUNDARY_FARFIELD) {
-    farfield_state<T>(inflow + T8GPU_INFLOW_WORDS * (kind - T8GPU_BOUNDARY_FARFIELD), n, so);
-  } else if (kind >= 2) {
-#pragma unroll
-    for (int k = 0; k < 5; k++) so[k] = inflow[T8GPU_INFLOW_WORDS * (kind - 2) + k];
-  }
-  face_frame_flux_ref<T, KIND>(n, t1, t2, sl, so, kind == 0, Ff, spd);
+  boundary_face_flux<T, KIND, MODE == kBndFar>(n, sl, kind, inflow, t1, t2, Ff, spd);
   from_face_frame<T>(n, t1, t2, Ff, g);
   const T surface = areas[slot] / static_cast<T>(SF);
 #pragma unroll
@@ -382,151 +260,97 @@ Vars<T> mk(const V& v) {
   return o;
 }
 
-inline int launch_status() { return static_cast<int>(hipGetLastError()); }
+// Every launcher: 0 for an empty launch, hipErrorInvalidValue for a dimension or flux kind it has no kernel for, else the
+// launch's status. dispatch_kind (fused_common.hpp) turns the flux kind (and the rank, as a flag) into template arguments.
+inline bool bad_kind(int kind) { return kind < 0 || kind > 2; }
 
 template <class T, class V>
 int flux_faces(int kind, int F, int ndim, const int32_t* fn, const int32_t* idx, const T* normals, const T* areas,
                V st, V fl, T* speed, void* stream) {
   if (F <= 0) return 0;
-  if (ndim < 2 || ndim > 3 || (kind < 0 || kind > 2)) return static_cast<int>(hipErrorInvalidValue);
-  const dim3  grid((F + 255) / 256), block(256);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (kind == 0)
-    hipLaunchKernelGGL((k_flux_faces<T, 0>), grid, block, 0, s, F, ndim, fn, idx, normals, areas, mk<T>(st), mk<T>(fl), speed);
-  else if (kind == 1)
-    hipLaunchKernelGGL((k_flux_faces<T, 1>), grid, block, 0, s, F, ndim, fn, idx, normals, areas, mk<T>(st), mk<T>(fl), speed);
-  else
-    hipLaunchKernelGGL((k_flux_faces<T, 2>), grid, block, 0, s, F, ndim, fn, idx, normals, areas, mk<T>(st), mk<T>(fl), speed);
-  return launch_status();
+  if (ndim < 2 || ndim > 3 || bad_kind(kind)) return static_cast<int>(hipErrorInvalidValue);
+  const dim3 grid((F + 255) / 256), block(256);
+  return dispatch_kind(
+      [&](auto K) {
+        return launch(&k_flux_faces<T, K>, grid, block, 0, static_cast<hipStream_t>(stream), F, ndim, fn, idx, normals, areas,
+                      mk<T>(st), mk<T>(fl), speed);
+      },
+      kind);
 }
 
-template <class T, class V>
-int flux_boundary(int kind, int F, int B, int ndim, const int32_t* fn, const T* normals, const T* areas, V st, V fl,
-                  T* speed, void* stream) {
+// MODE = kBndWalls: kinds and inflow are not read
+template <class T, int MODE, class V>
+int flux_boundary(int kind, int F, int B, int ndim, const int32_t* fn, const uint8_t* kinds, const T* inflow, const T* normals,
+                  const T* areas, V st, V fl, T* speed, void* stream) {
   if (B <= 0) return 0;
-  if (ndim < 2 || ndim > 3 || (kind < 0 || kind > 2)) return static_cast<int>(hipErrorInvalidValue);
-  const dim3  grid((B + 255) / 256), block(256);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (kind == 0)
-    hipLaunchKernelGGL((k_flux_boundary<T, 0>), grid, block, 0, s, F, B, ndim, fn, normals, areas, mk<T>(st), mk<T>(fl), speed);
-  else if (kind == 1)
-    hipLaunchKernelGGL((k_flux_boundary<T, 1>), grid, block, 0, s, F, B, ndim, fn, normals, areas, mk<T>(st), mk<T>(fl), speed);
-  else
-    hipLaunchKernelGGL((k_flux_boundary<T, 2>), grid, block, 0, s, F, B, ndim, fn, normals, areas, mk<T>(st), mk<T>(fl), speed);
-  return launch_status();
+  if (ndim < 2 || ndim > 3 || bad_kind(kind)) return static_cast<int>(hipErrorInvalidValue);
+  const dim3 grid((B + 255) / 256), block(256);
+  return dispatch_kind(
+      [&](auto K) {
+        return launch(&k_flux_boundary<T, K, MODE>, grid, block, 0, static_cast<hipStream_t>(stream), F, B, ndim, fn, kinds,
+                      inflow, normals, areas, mk<T>(st), mk<T>(fl), speed);
+      },
+      kind);
 }
 
-template <class T, class V>
-int flux_boundary_bc(int kind, int F, int B, int ndim, const int32_t* fn, const uint8_t* kinds, const T* inflow, const T* normals,
-                     const T* areas, V st, V fl, T* speed, void* stream) {
-  if (!kinds) return flux_boundary<T, V>(kind, F, B, ndim, fn, normals, areas, st, fl, speed, stream);
-  if (B <= 0) return 0;
-  if (ndim < 2 || ndim > 3 || (kind < 0 || kind > 2)) return static_cast<int>(hipErrorInvalidValue);
-  const dim3  grid((B + 255) / 256), block(256);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (kind == 0)
-    hipLaunchKernelGGL((k_flux_boundary_bc<T, 0>), grid, block, 0, s, F, B, ndim, fn, kinds, inflow, normals, areas, mk<T>(st), mk<T>(fl), speed);
-  else if (kind == 1)
-    hipLaunchKernelGGL((k_flux_boundary_bc<T, 1>), grid, block, 0, s, F, B, ndim, fn, kinds, inflow, normals, areas, mk<T>(st), mk<T>(fl), speed);
-  else
-    hipLaunchKernelGGL((k_flux_boundary_bc<T, 2>), grid, block, 0, s, F, B, ndim, fn, kinds, inflow, normals, areas, mk<T>(st), mk<T>(fl), speed);
-  return launch_status();
-}
-
+// STAGE = stage: dispatch_kind's three values 0..2 are stage - 1
 template <class T, int S, class V>
 int rk_stage(int stage, size_t ncells, V prev, V mid, V out, V fl, const T* volume, T dt, void* stream) {
   if (ncells == 0) return 0;
   if (stage < 1 || stage > 3) return static_cast<int>(hipErrorInvalidValue);
   size_t blocks = (ncells + 255) / 256;
   if (blocks > 256 * 32) blocks = 256 * 32;
-  const dim3  grid(static_cast<unsigned>(blocks)), block(256);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  Vars<T>     m = stage == 1 ? mk<T>(prev) : mk<T>(mid);
-  if (stage == 1)
-    hipLaunchKernelGGL((k_rk_stage<T, 1, S>), grid, block, 0, s, ncells, mk<T>(prev), m, mk<T>(out), mk<T>(fl), volume, dt);
-  else if (stage == 2)
-    hipLaunchKernelGGL((k_rk_stage<T, 2, S>), grid, block, 0, s, ncells, mk<T>(prev), m, mk<T>(out), mk<T>(fl), volume, dt);
-  else
-    hipLaunchKernelGGL((k_rk_stage<T, 3, S>), grid, block, 0, s, ncells, mk<T>(prev), m, mk<T>(out), mk<T>(fl), volume, dt);
-  return launch_status();
+  const dim3 grid(static_cast<unsigned>(blocks)), block(256);
+  return dispatch_kind(
+      [&](auto S0) {
+        return launch(&k_rk_stage<T, S0 + 1, S>, grid, block, 0, static_cast<hipStream_t>(stream), ncells, mk<T>(prev),
+                      stage == 1 ? mk<T>(prev) : mk<T>(mid), mk<T>(out), mk<T>(fl), volume, dt);
+      },
+      stage - 1);
 }
 
 template <class T, class V>
 int subgrid_inner(int kind, int rank, int N, V st, V fl, const T* volumes, void* stream) {
   if (N <= 0) return 0;
-  if ((rank != 2 && rank != 3) || (kind < 0 || kind > 2)) return static_cast<int>(hipErrorInvalidValue);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3  block(64);
-  const dim3  grid(rank == 3 ? N : (N + 3) / 4);
-#define T8_INNER(K, R) hipLaunchKernelGGL((k_subgrid_inner<T, K, R>), grid, block, 0, s, N, mk<T>(st), mk<T>(fl), volumes)
-  if (rank == 3) {
-    if (kind == 0) T8_INNER(0, 3); else if (kind == 1) T8_INNER(1, 3); else T8_INNER(2, 3);
-  } else {
-    if (kind == 0) T8_INNER(0, 2); else if (kind == 1) T8_INNER(1, 2); else T8_INNER(2, 2);
-  }
-#undef T8_INNER
-  return launch_status();
-}
-
-template <class T, bool WALL, class V>
-int subgrid_faces(int kind, int rank, int F, int count, const int32_t* fn, const int32_t* idx, const int32_t* ld,
-                  const int32_t* off, const T* normals, const T* areas, V st, V fl, void* stream) {
-  if (count <= 0) return 0;
-  if ((rank != 2 && rank != 3) || (kind < 0 || kind > 2)) return static_cast<int>(hipErrorInvalidValue);
-  hipStream_t s   = static_cast<hipStream_t>(stream);
-  const int   fpb = rank == 3 ? 4 : 16;
-  const dim3  block(64), grid((count + fpb - 1) / fpb);
-#define T8_FACES(K, R)                                                                                              \
-  hipLaunchKernelGGL((k_subgrid_faces<T, K, R, WALL>), grid, block, 0, s, F, count, fn, idx, ld, off, normals, areas, \
-                     mk<T>(st), mk<T>(fl))
-  if (rank == 3) {
-    if (kind == 0) T8_FACES(0, 3); else if (kind == 1) T8_FACES(1, 3); else T8_FACES(2, 3);
-  } else {
-    if (kind == 0) T8_FACES(0, 2); else if (kind == 1) T8_FACES(1, 2); else T8_FACES(2, 2);
-  }
-#undef T8_FACES
-  return launch_status();
+  if ((rank != 2 && rank != 3) || bad_kind(kind)) return static_cast<int>(hipErrorInvalidValue);
+  const dim3 block(64), grid(rank == 3 ? N : (N + 3) / 4);
+  return dispatch_kind(
+      [&](auto K, auto RANK3) {
+        return launch(&k_subgrid_inner<T, K, RANK3 ? 3 : 2>, grid, block, 0, static_cast<hipStream_t>(stream), N, mk<T>(st),
+                      mk<T>(fl), volumes);
+      },
+      kind, rank == 3);
 }
 
 template <class T, class V>
-int subgrid_boundary_bc(int kind, int rank, int F, int B, const int32_t* fn, const uint8_t* kinds, const T* inflow, const T* normals,
-                        const T* areas, V st, V fl, void* stream) {
-  if (!kinds) return subgrid_faces<T, true, V>(kind, rank, F, B, fn, nullptr, nullptr, nullptr, normals, areas, st, fl, stream);
-  if (B <= 0) return 0;
-  if ((rank != 2 && rank != 3) || (kind < 0 || kind > 2)) return static_cast<int>(hipErrorInvalidValue);
-  hipStream_t s   = static_cast<hipStream_t>(stream);
-  const int   fpb = rank == 3 ? 4 : 16;
-  const dim3  block(64), grid((B + fpb - 1) / fpb);
-#define T8_BC(K, R) \
-  hipLaunchKernelGGL((k_subgrid_boundary_bc<T, K, R>), grid, block, 0, s, F, B, fn, kinds, inflow, normals, areas, mk<T>(st), mk<T>(fl))
-  if (rank == 3) {
-    if (kind == 0) T8_BC(0, 3); else if (kind == 1) T8_BC(1, 3); else T8_BC(2, 3);
-  } else {
-    if (kind == 0) T8_BC(0, 2); else if (kind == 1) T8_BC(1, 2); else T8_BC(2, 2);
-  }
-#undef T8_BC
-  return launch_status();
+int subgrid_faces(int kind, int rank, int F, const int32_t* fn, const int32_t* idx, const int32_t* ld, const int32_t* off,
+                  const T* normals, const T* areas, V st, V fl, void* stream) {
+  if (F <= 0) return 0;
+  if ((rank != 2 && rank != 3) || bad_kind(kind)) return static_cast<int>(hipErrorInvalidValue);
+  const int  fpb = rank == 3 ? 4 : 16;
+  const dim3 block(64), grid((F + fpb - 1) / fpb);
+  return dispatch_kind(
+      [&](auto K, auto RANK3) {
+        return launch(&k_subgrid_faces<T, K, RANK3 ? 3 : 2>, grid, block, 0, static_cast<hipStream_t>(stream), F, fn, idx, ld,
+                      off, normals, areas, mk<T>(st), mk<T>(fl));
+      },
+      kind, rank == 3);
 }
 
-// kinds 0 .. 15 (far-field faces too): k_subgrid_boundary_far
-template <class T, class V>
-int subgrid_boundary_far(int kind, int rank, int F, int B, const int32_t* fn, const uint8_t* kinds, const T* inflow, const T* normals,
-                         const T* areas, V st, V fl, void* stream) {
-  if (!kinds) return subgrid_faces<T, true, V>(kind, rank, F, B, fn, nullptr, nullptr, nullptr, normals, areas, st, fl, stream);
+// MODE = kBndWalls: kinds and inflow are not read
+template <class T, int MODE, class V>
+int subgrid_boundary(int kind, int rank, int F, int B, const int32_t* fn, const uint8_t* kinds, const T* inflow, const T* normals,
+                     const T* areas, V st, V fl, void* stream) {
   if (B <= 0) return 0;
-  if ((rank != 2 && rank != 3) || (kind < 0 || kind > 2)) return static_cast<int>(hipErrorInvalidValue);
-  hipStream_t s   = static_cast<hipStream_t>(stream);
-  const int   fpb = rank == 3 ? 4 : 16;
-  const dim3  block(64), grid((B + fpb - 1) / fpb);
-#define T8_FAR(K, R) \
-  hipLaunchKernelGGL((k_subgrid_boundary_far<T, K, R>), grid, block, 0, s, F, B, fn, kinds, inflow, normals, areas, mk<T>(st), mk<T>(fl))
-  if (rank == 3) {
-    if (kind == 0) T8_FAR(0, 3); else if (kind == 1) T8_FAR(1, 3); else T8_FAR(2, 3);
-  } else {
-    if (kind == 0) T8_FAR(0, 2); else if (kind == 1) T8_FAR(1, 2); else T8_FAR(2, 2);
-  }
-#undef T8_FAR
-  return launch_status();
+  if ((rank != 2 && rank != 3) || bad_kind(kind)) return static_cast<int>(hipErrorInvalidValue);
+  const int  fpb = rank == 3 ? 4 : 16;
+  const dim3 block(64), grid((B + fpb - 1) / fpb);
+  return dispatch_kind(
+      [&](auto K, auto RANK3) {
+        return launch(&k_subgrid_boundary<T, K, RANK3 ? 3 : 2, MODE>, grid, block, 0, static_cast<hipStream_t>(stream), F, B, fn,
+                      kinds, inflow, normals, areas, mk<T>(st), mk<T>(fl));
+      },
+      kind, rank == 3);
 }
 
 }  // namespace t8gpu_hip
@@ -561,6 +385,7 @@ const char* t8gpu_hip_error_string(int code) {
   return hipGetErrorString(static_cast<hipError_t>(code));
 }
 
+// (a _bc / _far call without a kinds list is the walls-only launch)
 #define T8_DEFINE_COMPAT(SUF, T, V)                                                                                  \
   int t8gpu_hip_flux_faces_##SUF(int kind, int F, int ndim, const int32_t* fn, const int32_t* idx, const T* normals, \
                                  const T* areas, V st, V fl, T* speed, void* stream) {                               \
@@ -568,12 +393,15 @@ const char* t8gpu_hip_error_string(int code) {
   }                                                                                                                  \
   int t8gpu_hip_flux_boundary_##SUF(int kind, int F, int B, int ndim, const int32_t* fn, const T* normals,           \
                                     const T* areas, V st, V fl, T* speed, void* stream) {                            \
-    return flux_boundary<T, V>(kind, F, B, ndim, fn, normals, areas, st, fl, speed, stream);                         \
+    return flux_boundary<T, kBndWalls, V>(kind, F, B, ndim, fn, nullptr, nullptr, normals, areas, st, fl, speed,     \
+                                          stream);                                                                   \
   }                                                                                                                  \
-  int t8gpu_hip_flux_boundary_bc_##SUF(int kind, int F, int B, int ndim, const int32_t* fn, const uint8_t* kinds,       \
-                                       const T* inflow, const T* normals, const T* areas, V st, V fl, T* speed,        \
-                                       void* stream) {                                                                 \
-    return flux_boundary_bc<T, V>(kind, F, B, ndim, fn, kinds, inflow, normals, areas, st, fl, speed, stream);         \
+  int t8gpu_hip_flux_boundary_bc_##SUF(int kind, int F, int B, int ndim, const int32_t* fn, const uint8_t* kinds,    \
+                                       const T* inflow, const T* normals, const T* areas, V st, V fl, T* speed,      \
+                                       void* stream) {                                                               \
+    return kinds ? flux_boundary<T, kBndFar, V>(kind, F, B, ndim, fn, kinds, inflow, normals, areas, st, fl, speed,  \
+                                                stream)                                                              \
+                 : t8gpu_hip_flux_boundary_##SUF(kind, F, B, ndim, fn, normals, areas, st, fl, speed, stream);       \
   }                                                                                                                  \
   int t8gpu_hip_rk3_stage_##SUF(int stage, int N, V prev, V mid, V out, V fl, const T* volume, T dt, void* stream) { \
     return rk_stage<T, 1, V>(stage, N < 0 ? 0 : (size_t)N, prev, mid, out, fl, volume, dt, stream);                  \
@@ -584,22 +412,23 @@ const char* t8gpu_hip_error_string(int code) {
   int t8gpu_hip_subgrid_outer_##SUF(int kind, int rank, int F, const int32_t* fn, const int32_t* idx,                \
                                     const int32_t* ld, const int32_t* off, const T* normals, const T* areas, V st,   \
                                     V fl, void* stream) {                                                            \
-    return subgrid_faces<T, false, V>(kind, rank, F, F, fn, idx, ld, off, normals, areas, st, fl, stream);           \
+    return subgrid_faces<T, V>(kind, rank, F, fn, idx, ld, off, normals, areas, st, fl, stream);                     \
   }                                                                                                                  \
   int t8gpu_hip_subgrid_boundary_##SUF(int kind, int rank, int F, int B, const int32_t* fn, const T* normals,        \
                                        const T* areas, V st, V fl, void* stream) {                                   \
-    return subgrid_faces<T, true, V>(kind, rank, F, B, fn, nullptr, nullptr, nullptr, normals, areas, st, fl,        \
-                                     stream);                                                                        \
+    return subgrid_boundary<T, kBndWalls, V>(kind, rank, F, B, fn, nullptr, nullptr, normals, areas, st, fl, stream); \
   }                                                                                                                  \
-  int t8gpu_hip_subgrid_boundary_bc_##SUF(int kind, int rank, int F, int B, const int32_t* fn, const uint8_t* kinds,  \
+  int t8gpu_hip_subgrid_boundary_bc_##SUF(int kind, int rank, int F, int B, const int32_t* fn, const uint8_t* kinds, \
                                           const T* inflow, const T* normals, const T* areas, V st, V fl,             \
                                           void* stream) {                                                            \
-    return subgrid_boundary_bc<T, V>(kind, rank, F, B, fn, kinds, inflow, normals, areas, st, fl, stream);           \
+    return kinds ? subgrid_boundary<T, kBndOpen, V>(kind, rank, F, B, fn, kinds, inflow, normals, areas, st, fl, stream) \
+                 : t8gpu_hip_subgrid_boundary_##SUF(kind, rank, F, B, fn, normals, areas, st, fl, stream);           \
   }                                                                                                                  \
   int t8gpu_hip_subgrid_boundary_far_##SUF(int kind, int rank, int F, int B, const int32_t* fn, const uint8_t* kinds, \
                                            const T* inflow, const T* normals, const T* areas, V st, V fl,            \
                                            void* stream) {                                                           \
-    return subgrid_boundary_far<T, V>(kind, rank, F, B, fn, kinds, inflow, normals, areas, st, fl, stream);          \
+    return kinds ? subgrid_boundary<T, kBndFar, V>(kind, rank, F, B, fn, kinds, inflow, normals, areas, st, fl, stream) \
+                 : t8gpu_hip_subgrid_boundary_##SUF(kind, rank, F, B, fn, normals, areas, st, fl, stream);           \
   }                                                                                                                  \
   int t8gpu_hip_subgrid_rk3_stage_##SUF(int stage, int rank, int N, V prev, V mid, V out, V fl, const T* volumes,    \
                                         T dt, void* stream) {                                                        \

@@ -139,10 +139,11 @@ def test_field_names_and_slots():
 def test_kernel_source_hash_is_the_one_of_the_committed_c4_profile():
     """fields.hip is an output pass, not a stage kernel: it and its helpers stay out of the hashed sources, so the c4
     traffic record (tied to the hash) stays valid. The record is the one scripts/commit_profile.py wrote for
-    profiles/r10_c4_f64_stage.md, taken when the persistent launchers got their resident limit and the launch note its grids
-    (host code of the hashed files; the kernels are those of r09)."""
+    profiles/r11_c4_f64_stage.md, taken when the compat tier's boundary kernels moved onto one face routine (compat_faces.hpp,
+    kernels_compat.hip and a host-side helper of fused_common.hpp among the hashed files; the fused kernels are those of r09,
+    their device code unchanged)."""
     records = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
-    tied = [r for r in records.values() if isinstance(r, dict) and r.get("source") == "profiles/r10_c4_f64_stage.md"]
-    assert len(tied) == 1 and tied[0]["kernel_source_hash"] == "c28bcc8ba66e37a2"
+    tied = [r for r in records.values() if isinstance(r, dict) and r.get("source") == "profiles/r11_c4_f64_stage.md"]
+    assert len(tied) == 1 and tied[0]["kernel_source_hash"] == "93f38f202888225f"
     assert build.kernel_source_hash() == tied[0]["kernel_source_hash"]
     assert os.path.exists(os.path.join(build.CSRC, "hip", "fields.hip"))
