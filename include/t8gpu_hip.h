@@ -487,7 +487,7 @@ typedef struct T8gpuSubgridPlan {
   const void*    inflow;        /* DEVICE float_type [K][T8GPU_INFLOW_WORDS] */
   int32_t        has_open_faces;
   /* FAR-FIELD FACES (ABI 12): a plan built by t8gpu_plan_subgrid_create_far may hold kinds 10 + k in the same bits: a far-field
-   * face against state k of `inflow` (k < 6). has_farfield_faces = 1 (with has_open_faces = 1) selects the _far kernels, whose
+   * face against state k of `inflow` (k < 6). has_farfield_faces = 1 (with has_open_faces = 1) selects the kernels of MODE kBndFar, whose
    * block algorithm builds the outside state of every such sub-face from the inside subcell, the outward normal +-e_axis and
    * the table row (Riemann invariants); the table must then hold an entry for every far-field code too. 0 (a
    * zeroed tail): no far-field faces, as before ABI 12. */

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """usage: scripts/subgrid_farfield_cost.py [--rounds R] [--steps K] [--cases c3,c3q] [--dtype f32|f64]
 Cost of far-field sides on Subgrid meshes: the bench.py c3 / c3q meshes with x far field and the other sides periodic, against
-the same meshes with x inflow / outflow (the _open kernels), fused tier + native driver, KEPES. The two plans hold the same
-blocks in the same families; they differ in the kernels the launcher picks (_far against _open). Runs alternate (open, far,
+the same meshes with x inflow / outflow (the Subgrid kernels' MODE 1, kBndOpen), fused tier + native driver, KEPES. The two plans
+hold the same blocks in the same families; they differ in the MODE the launcher picks (2, kBndFar, against 1). Runs alternate (open, far,
 open, ...) R times; prints per case the median ms/step of each with every run (one JSON line per case)."""
 import argparse
 import json

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """usage: scripts/subgrid_open_cost.py [--rounds R] [--steps K] [--cases c3,c3q] [--dtype f32|f64]
 Cost of open boundaries on Subgrid meshes: the bench.py c3 / c3q meshes with x inflow / outflow and the other sides periodic,
-against the same meshes fully periodic, fused tier, KEPES. Runs alternate (periodic, open, periodic, ...) R times; prints per
+against the same meshes fully periodic (the Subgrid kernels' MODE 1, kBndOpen, against MODE 0, kBndWalls), fused tier, KEPES. Runs alternate (periodic, open, periodic, ...) R times; prints per
 case the median ms/step of each and the share of blocks that left the families (one JSON line per case)."""
 import argparse
 import json

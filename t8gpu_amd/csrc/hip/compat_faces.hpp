@@ -15,10 +15,6 @@
 
 namespace t8gpu_hip {
 
-// Which boundary kinds a kernel decodes (compile time): walls only (no kinds list and no inflow table is read), kinds 0..9
-// (wall, outflow, inflow k), or kinds 0..15 (far field k as well). A kernel below kBndFar holds no far-field code.
-enum BoundaryMode { kBndWalls = 0, kBndOpen = 1, kBndFar = 2 };
-
 // The outside state o of a boundary face of kind `kind` with outward normal n and inside state s (t8gpu_host.h: T8GPU_BOUNDARY_*,
 // t8gpu_hip.h: T8GPU_INFLOW_WORDS): wall (0, which the flux mirrors) and outflow (1) keep the inside state, inflow 2 + k takes the
 // conservative state of table row k (words 0-4), far field 10 + k the characteristic state against row k

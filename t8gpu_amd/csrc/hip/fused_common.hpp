@@ -179,6 +179,12 @@ T8_DEV void ghost_window_send(const T8gpuPlainPlan& P, int e, const T v[5]) {
   }
 }
 
+// Which boundary kinds a kernel decodes (compile time): walls only (no kinds list and no inflow table is read), kinds 0..9
+// (wall, outflow, inflow k), or kinds 0..15 (far field k as well). A kernel below kBndFar holds no far-field code. The MODE of
+// the compat tier (compat_faces.hpp, kernels_compat.hip, kernels_boundary.hip) and of the Subgrid stage kernels
+// (kernels_subgrid_fused.hip); the plain tile kernels spell the same choice as the bools OPEN, FAR (below).
+enum BoundaryMode { kBndWalls = 0, kBndOpen = 1, kBndFar = 2 };
+
 // ---- boundary faces of the tile plan (ABI 9) ------------------------------------------------------------------------
 // The r half of a face_lr entry (tile_plan.cpp: boundary_code): a tile-local slot below 0xFFF0, else 0xFFFF reflective wall,
 // 0xFFFE outflow, 0xFFF0 + k inflow state k. The one place that spells the codes; only the OPEN instantiations of the tile

@@ -4,11 +4,12 @@
 //                      evaluated once from LDS, the far cells of the outward faces pooled over the wavefronts;
 //   k_subgrid_family2  2D: one wavefront = a 2x2 square of blocks, the same within a wavefront.
 // The launcher (subgrid_fused_stage) takes the family kernels wherever the host plan found cubes / squares and runs the
-// remaining blocks with the block algorithm in the same launch; all three give the same bits. Plans with outflow / inflow
-// faces (T8gpuSubgridPlan::has_open_faces) take the _open forms of the three kernels: their block algorithm decodes the kind
-// of every boundary face (sg_boundary_kind); the family bodies are the wall-only ones (no family holds an open-face block).
-// Plans that also have far-field faces (has_farfield_faces) take the _far forms: the block algorithm with OPEN + FAR, which
-// builds the outside state of a far-field sub-face from the inside subcell (sg_farfield_state); family bodies as before.
+// remaining blocks with the block algorithm in the same launch; all three give the same bits. Every kernel's last template
+// argument is its MODE (fused_common.hpp: BoundaryMode), which the launcher takes from the plan. kBndWalls: the plan has walls
+// only. kBndOpen: it has outflow / inflow faces (T8gpuSubgridPlan::has_open_faces), and the block algorithm decodes the kind of
+// every boundary face (sg_boundary_kind). kBndFar: it also has far-field faces (has_farfield_faces), and the block algorithm
+// builds the outside state of a far-field sub-face from the inside subcell (sg_farfield_state). The family bodies are the
+// wall-only ones under every MODE: no family holds a block with an open or far-field face.
 //
 // Replaces, per stage, compute_inner_fluxes + compute_boundary_fluxes + compute_outer_fluxes +
 // subgrid::SSP_3RK_stepK (examples/subgrid/solver.inl:166-195) and their flux-plane round trips
@@ -35,6 +36,9 @@
 // result does not depend on the listing rule (quirk Q4) or on the partition. There are no atomics, no flux
 // planes and the result is bitwise reproducible. The wave runs in lock-step,
 // so the reference's unsynchronised LDS reuse has no counterpart here.
+// (The axis pick of a block's face, the sub-face index `tsub`, the exchange of a + pass and the RK epilogue are written out
+// where they are used, in the block algorithm and in both family bodies: as shared device functions each of the four changed
+// the instructions of 172 to 648 of the 648 kernels -- profiles/r12_subgrid_fused_refactor.md.)
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -45,11 +49,6 @@
 #include "t8gpu_hip.h"
 
 namespace t8gpu_hip {
-
-template <class T>
-struct SVars {
-  T* p[5];
-};
 
 // Element `i` of a state plane. NARROW (every plane of the rank, ghost blocks included, is shorter than 4 GiB -- the
 // launcher checks): the byte offset fits 32 bits, so the five planes share ONE offset register and the loads take the
@@ -63,11 +62,6 @@ template <bool WIDE, class T>
 T8_DEV T& at(T* p, size_t i) {
   if (WIDE) return p[i];
   return *reinterpret_cast<T*>(reinterpret_cast<char*>(p) + static_cast<uint32_t>(i * sizeof(T)));
-}
-
-T8_DEV int sg_xcd_position(int b, int nb) {
-  const int q = nb >> 3, rem = nb & 7, x = b & 7, k = b >> 3;
-  return x * q + (x < rem ? x : rem) + k;
 }
 
 // Everything below is written with shifts instead of small arrays: a runtime-indexed per-lane array
@@ -92,9 +86,9 @@ T8_DEV int cell_coord(int flat, int a) { return (flat >> (2 * a)) & 3; }   // fl
 // ---- boundary faces (open boundaries) -------------------------------------------------------------------------------
 // A boundary face has far = -1 in its record row and its kind in bits 23-26 of the code word (subgrid_plan.cpp): 0 reflective
 // wall, 1 outflow (the outside state is the inside subcell's own), 2 + k inflow with conservative state k of the plan's inflow
-// table, 10 + k far field against state k (plans of t8gpu_plan_subgrid_create_far; decoded by the FAR instantiations, below).
-// The one place that spells the encoding; only the OPEN instantiations of the block algorithm decode it (the others see
-// walls only, as before). An open face evaluates the ordinary face flux: left = the inside subcell, outward normal, unmirrored.
+// table, 10 + k far field against state k (plans of t8gpu_plan_subgrid_create_far; decoded under MODE kBndFar, below).
+// The one place that spells the encoding; the block algorithm decodes it where its MODE (fused_common.hpp: BoundaryMode) is not
+// kBndWalls (under kBndWalls it sees walls only, as before). An open face evaluates the ordinary face flux: left = the inside subcell, outward normal, unmirrored.
 T8_DEV int sg_boundary_kind(int code) { return (code >> 23) & 15; }
 // the conservative state of inflow kind `bc` (>= 2): words 0-4 of its T8GPU_INFLOW_WORDS row (t8gpu_hip_plain_inflow_table_*).
 // Words 5-13 hold the plain tiles' KEPES record (prim_from_state<T, sizeof(T) == 8>); the Subgrid kernels derive their own
@@ -108,7 +102,7 @@ T8_DEV void sg_inflow_state(const T8gpuSubgridPlan& P, int bc, T s[5]) {
 
 // ---- far-field faces (ABI 12) -----------------------------------------------------------------------------------------
 // Kind 10 + k: the characteristic condition (fused_common.hpp: farfield_outside) against row k of the inflow table,
-// per sub-face, with the inside subcell on the left and the outward normal +-e_axis. Only the FAR instantiations decode these
+// per sub-face, with the inside subcell on the left and the outward normal +-e_axis. Only MODE kBndFar decodes these
 // kinds (a plan without has_farfield_faces holds none). `s` holds the inside subcell's conservative state on entry and the
 // outside state on return: the table row's words 0-4 (supersonic inflow: what sg_inflow_state gives an inflow face), untouched
 // (supersonic outflow, the guard: the caller keeps what an outflow face takes) or the built state. Returns the FarSide.
@@ -133,9 +127,7 @@ T8_DEV CellData<T, KIND> cell_from_state(const T s[5]) {
   if (KIND == 0) {
     // fp64: table-driven logarithm, the 2 KB table read from global memory (it stays in the L1 / K$; an LDS copy per
     // one-wave workgroup would cost the kernel a wavefront per SIMD). fp32: hardware log2.
-    const Prim<T> q = prim_from_state<T, true>(s, kLogTab);
-    c.v[0] = q.rho; c.v[1] = q.vx; c.v[2] = q.vy; c.v[3] = q.vz; c.v[4] = q.p;
-    c.v[5] = q.beta; c.v[6] = q.lrho; c.v[7] = q.lbeta; c.v[8] = q.v0;
+    prim_words<T>(s, c.v, kLogTab);
   } else {
 #pragma unroll
     for (int k = 0; k < 5; k++) c.v[k] = s[k];
@@ -149,8 +141,8 @@ T8_DEV void cell_flux(const CellData<T, KIND>& L, const CellData<T, KIND>& R, bo
   if (KIND == 0) {
     T spd;
     Prim<T> a, b;
-    a.rho = L.v[0]; a.vx = L.v[1]; a.vy = L.v[2]; a.vz = L.v[3]; a.p = L.v[4]; a.beta = L.v[5]; a.lrho = L.v[6]; a.lbeta = L.v[7]; a.v0 = L.v[8];
-    b.rho = R.v[0]; b.vx = R.v[1]; b.vy = R.v[2]; b.vz = R.v[3]; b.p = R.v[4]; b.beta = R.v[5]; b.lrho = R.v[6]; b.lbeta = R.v[7]; b.v0 = R.v[8];
+    words_prim<T>(L.v, a);
+    words_prim<T>(R.v, b);
     kepes_axis<T>(a, b, wall, axis, positive, area, g, spd);   // subgrid faces are axis-aligned (kernels.inl:717-750 requires it)
   } else {
     T n[3], t1[3], t2[3];
@@ -172,8 +164,8 @@ T8_DEV float  area_of(int lo, int, float) { return __int_as_float(lo); }
 T8_DEV double area_of(int lo, int hi, double) { return __hiloint2double(hi, lo); }
 
 // lane data of one generic face from its row {other block, code, area}; `live_row` = the row exists
-template <class T, int S, bool WIDE>
-T8_DEV FaceLane<T> face_lane_from_row(const SVars<T>& src, int4 rec, bool live_row, int si, int sj) {
+template <class T, bool WIDE>
+T8_DEV FaceLane<T> face_lane_from_row(const FVars<T>& src, int4 rec, bool live_row, int si, int sj) {
   FaceLane<T> L;
   L.active = live_row;
   L.right = L.wall = false;
@@ -202,12 +194,13 @@ T8_DEV FaceLane<T> face_lane_from_row(const SVars<T>& src, int4 rec, bool live_r
 }
 // (FAR: `own0` = the first cell of the lane's block. A far-field face leaves as an outflow face (bc 1: the outside state is the
 //  inside subcell's own record) or as an inflow face whose state `sf` is the table row or the built state)
-template <class T, int S, bool WIDE, bool OPEN = false, bool FAR = false>
-T8_DEV FaceLane<T> load_face_lane(const T8gpuSubgridPlan& P, const SVars<T>& src, int first, int nbf, int idx, int si, int sj,
-                                  size_t own0 = 0) {
+template <class T, bool WIDE, int MODE>
+T8_DEV FaceLane<T> load_face_lane(const T8gpuSubgridPlan& P, const FVars<T>& src, int first, int nbf, int idx, int si, int sj,
+                                  size_t own0) {
+  constexpr bool OPEN = MODE != kBndWalls, FAR = MODE == kBndFar;
   int4 rec = make_int4(0, 0, 0, 0);
   if (idx < nbf) rec = reinterpret_cast<const int4*>(P.bf_rec)[first + idx];   // {other block, code, area}
-  FaceLane<T> L = face_lane_from_row<T, S, WIDE>(src, rec, idx < nbf, si, sj);
+  FaceLane<T> L = face_lane_from_row<T, WIDE>(src, rec, idx < nbf, si, sj);
   if (OPEN && L.active && L.wall) {
     L.bc = sg_boundary_kind(rec.y);
     if (FAR && L.bc >= kSgFarfield) {
@@ -228,7 +221,7 @@ struct PlusFace {
   bool on, wall;   // on: listed as ONE coarse face (faces towards finer blocks are in the generic list); wall: a boundary face
   int  far, hf;    // far cell of sub-face (0, 0); hf: two sub-faces share a far cell (the block is the fine side)
   T    area;
-  int  bc;         // the kind of a boundary face (read by the OPEN instantiations only)
+  int  bc;         // the kind of a boundary face (read where MODE is not kBndWalls)
 };
 template <class T>
 T8_DEV PlusFace<T> plus_face(int4 w, bool live) {   // w = the four words of the block record for this face
@@ -249,7 +242,7 @@ T8_DEV PlusFace<T> plus_face(int4 w, bool live) {   // w = the four words of the
 // state of the far cell behind sub-face (ti, tj) of a + / - face with tangential strides 1 << la, 1 << lb; a wall face
 // reads cell `wall_cell` instead (pass -1: nothing)
 template <class T, bool WIDE>
-T8_DEV void load_far(const SVars<T>& src, bool on, bool wall, int far0, int hf, int la, int lb, int ti, int tj, ptrdiff_t wall_cell,
+T8_DEV void load_far(const FVars<T>& src, bool on, bool wall, int far0, int hf, int la, int lb, int ti, int tj, ptrdiff_t wall_cell,
                      T sf[5]) {
 #pragma unroll
   for (int k = 0; k < 5; k++) sf[k] = T(1);
@@ -276,16 +269,26 @@ T8_DEV void block_sync() {
   }
 }
 
+// LDS of one wavefront of the block algorithm: NW rows of block_row(RANK) words -- the 64 cells of its block(s), then the far
+// cells of their + faces (RANK 3: 3 x 16 of one block; RANK 2: 2 x 4 of each of four) --, then the [5][64] flux exchange buffer.
+constexpr int block_row(int RANK) { return 64 + (RANK == 3 ? 48 : 32); }
+constexpr int block_lds_words(int NW, int RANK) { return NW * block_row(RANK) + 5 * 64; }
+// leftover blocks per workgroup of k_subgrid_family behind the cubes (fp64: LDS for 4 only)
+template <class T>
+constexpr int family_rest_blocks() {
+  return sizeof(T) == 8 ? 4 : 8;
+}
+
 // One wavefront's work on its block(s): `pos_base` = the wavefront's position in the launch (RANK 3: the block record;
 // RANK 2: four records), c = lane, pe / xb = the wavefront's LDS slices ([NW][64 + BPW * PF] cells of the block(s) then
 // the far cells of their + faces; [5][64] flux exchange buffer).
-// OPEN: the plan has outflow / inflow faces (sg_boundary_kind); OPEN = false is the wall-only block algorithm.
-// FAR (with OPEN): ... and far-field faces. The outside state of such a sub-face is built by the lane that evaluates it, right
+// MODE (BoundaryMode), spelled OPEN and FAR in the body. OPEN (MODE is not kBndWalls): the plan has outflow / inflow faces
+// (sg_boundary_kind); OPEN = false is the wall-only block algorithm. FAR (MODE kBndFar): ... and far-field faces.
+// The outside state of such a sub-face is built by the lane that evaluates it, right
 // before its flux (it is not live across the passes); the kind test diverges only in wavefronts that hold boundary sub-faces.
-template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE, bool WAVE_ONLY, bool NT = false, bool OPEN = false,
-          bool FAR = false>
-T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_count, int pos_base, int c, const SVars<T>& prev,
-                          const SVars<T>& src, const SVars<T>& out, const T* __restrict__ volumes, T dt, T* pe, T* xb) {
+template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE, bool WAVE_ONLY, bool NT, int MODE>
+T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_count, int pos_base, int c, const FVars<T>& prev,
+                          const FVars<T>& src, const FVars<T>& out, const T* __restrict__ volumes, T dt, T* pe, T* xb) {
   // (pe / xb carry no __restrict__: other lanes write what this lane reads, and a no-alias pointer would let the
   //  compiler keep values across the synchronisation points)
   constexpr int NW  = CellData<T, KIND>::words;
@@ -293,7 +296,8 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
   constexpr int SF  = RANK == 3 ? 16 : 4;   // sub-faces per coarse face
   constexpr int BPW = 64 / S;               // blocks per wavefront
   constexpr int PF  = RANK * SF;            // far cells of a block's + faces
-  constexpr int PEL = 64 + BPW * PF;        // row length of pe
+  constexpr int PEL = block_row(RANK);      // row length of pe: 64 + BPW * PF
+  constexpr bool OPEN = MODE != kBndWalls, FAR = MODE == kBndFar;
   const int    base = (c / S) * S, cl = c - base;
   const int    pos  = RANK == 3 ? pos_base : pos_base * BPW + c / S;
   const bool   live = pos < block_count;
@@ -412,7 +416,7 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
     if (inner || pl.on) cell_flux<T, KIND>(mine, other, wall, d, true, ar, g);   // left = this cell, normal +e_d
     block_sync<WAVE_ONLY>();
 #pragma unroll
-    for (int k = 0; k < 5; k++) xb[(k) * 64 + (c)] = g[k];
+    for (int k = 0; k < 5; k++) xb[k * 64 + c] = g[k];
     block_sync<WAVE_ONLY>();
 #pragma unroll
     for (int k = 0; k < 5; k++) acc[k] -= g[k];
@@ -466,7 +470,7 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
   // ---- remaining coarse faces (towards finer blocks: four sub-faces per surface cell; kernels.inl:664-911) ----------
   for (int p0 = 0; p0 < npass; p0 += 4) {
     T                 g[5] = {T(0), T(0), T(0), T(0), T(0)};
-    const FaceLane<T> fl = load_face_lane<T, S, WIDE, OPEN, FAR>(P, src, b0, nbf, p0 + slot, si, sj, (size_t)e * S);
+    const FaceLane<T> fl = load_face_lane<T, WIDE, MODE>(P, src, b0, nbf, p0 + slot, si, sj, (size_t)e * S);
     if (fl.active) {
       CellData<T, KIND> here, there;
 #pragma unroll
@@ -535,51 +539,24 @@ T8_DEV void subgrid_block(const T8gpuSubgridPlan& P, int block_begin, int block_
     }
     const T scale = dt / (vol / T(S));
 #pragma unroll
-    for (int k = 0; k < 5; k++) {
-      stream_store<NT>(&at<WIDE>(out.p[k], o), rk_stage_update<T, STAGE>(pv[k], s0[k], scale, acc[k]));
-    }
+    for (int k = 0; k < 5; k++) stream_store<NT>(&at<WIDE>(out.p[k], o), rk_stage_update<T, STAGE>(pv[k], s0[k], scale, acc[k]));
   }
 }
 
-
 // RANK 3: one Subgrid<4,4,4> block per wavefront. RANK 2: four Subgrid<4,4> blocks per wavefront
 // (16 lanes each; every index is relative to the lane's own block).
-template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE>
-__global__ __launch_bounds__(64) void k_subgrid_fused(T8gpuSubgridPlan P, int block_begin, int block_count, SVars<T> prev,
-                                                      SVars<T> src, SVars<T> out, const T* __restrict__ volumes, T dt) {
+template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE, int MODE>
+__global__ __launch_bounds__(64) void k_subgrid_fused(T8gpuSubgridPlan P, int block_begin, int block_count, FVars<T> prev,
+                                                      FVars<T> src, FVars<T> out, const T* __restrict__ volumes, T dt) {
   constexpr int NW = CellData<T, KIND>::words;
-  constexpr int PEL = 64 + (RANK == 3 ? 1 : 4) * RANK * (RANK == 3 ? 16 : 4);
-  __shared__ T pe[NW * PEL];  // cells of the wave's block(s), then the far cells of their + faces
-  __shared__ T xb[5 * 64];    // flux exchange buffer (+ passes: per cell; generic passes: [slot * SF + sub-face])
+  // (two arrays, block_lds_words(NW, RANK) together: that they cannot overlap is known to the compiler this way)
+  __shared__ T pe[NW * block_row(RANK)];  // cells of the wave's block(s), then the far cells of their + faces
+  __shared__ T xb[5 * 64];                // flux exchange buffer (+ passes: per cell; generic passes: [slot * SF + sub-face])
   // (RANK 3: the block index is wave-uniform -- blockIdx arithmetic only --, so the per-block loads (volume, face lists,
   //  face records) stay scalar loads and their branches scalar branches)
-  const int pos_base = sg_xcd_position(blockIdx.x, gridDim.x);
-  subgrid_block<T, KIND, STAGE, RANK, EARLY_PREV, WIDE, false>(P, block_begin, block_count, pos_base, threadIdx.x, prev, src, out, volumes,
-                                                               dt, pe, xb);
-}
-// the same for plans with outflow / inflow faces
-template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE>
-__global__ __launch_bounds__(64) void k_subgrid_fused_open(T8gpuSubgridPlan P, int block_begin, int block_count, SVars<T> prev,
-                                                           SVars<T> src, SVars<T> out, const T* __restrict__ volumes, T dt) {
-  constexpr int NW = CellData<T, KIND>::words;
-  constexpr int PEL = 64 + (RANK == 3 ? 1 : 4) * RANK * (RANK == 3 ? 16 : 4);
-  __shared__ T pe[NW * PEL];
-  __shared__ T xb[5 * 64];
-  const int pos_base = sg_xcd_position(blockIdx.x, gridDim.x);
-  subgrid_block<T, KIND, STAGE, RANK, EARLY_PREV, WIDE, false, false, true>(P, block_begin, block_count, pos_base, threadIdx.x, prev, src,
+  const int pos_base = xcd_position(blockIdx.x, gridDim.x);
+  subgrid_block<T, KIND, STAGE, RANK, EARLY_PREV, WIDE, false, false, MODE>(P, block_begin, block_count, pos_base, threadIdx.x, prev, src,
                                                                             out, volumes, dt, pe, xb);
-}
-// ... and far-field faces
-template <class T, int KIND, int STAGE, int RANK, bool EARLY_PREV, bool WIDE>
-__global__ __launch_bounds__(64) void k_subgrid_fused_far(T8gpuSubgridPlan P, int block_begin, int block_count, SVars<T> prev,
-                                                          SVars<T> src, SVars<T> out, const T* __restrict__ volumes, T dt) {
-  constexpr int NW = CellData<T, KIND>::words;
-  constexpr int PEL = 64 + (RANK == 3 ? 1 : 4) * RANK * (RANK == 3 ? 16 : 4);
-  __shared__ T pe[NW * PEL];
-  __shared__ T xb[5 * 64];
-  const int pos_base = sg_xcd_position(blockIdx.x, gridDim.x);
-  subgrid_block<T, KIND, STAGE, RANK, EARLY_PREV, WIDE, false, false, true, true>(P, block_begin, block_count, pos_base, threadIdx.x, prev,
-                                                                                  src, out, volumes, dt, pe, xb);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -596,17 +573,28 @@ __global__ __launch_bounds__(64) void k_subgrid_fused_far(T8gpuSubgridPlan P, in
 T8_DEV int fam_compact(int w, int d) { return d == 0 ? w >> 1 : (d == 1 ? (w & 1) | ((w >> 2) << 1) : w & 3); }   // drop bit d
 T8_DEV int fam_expand(int j, int d) { return d == 0 ? j << 1 : (d == 1 ? (j & 1) | ((j >> 1) << 2) : j); }      // zero bit at d
 
-// (second launch bound = wavefronts per SIMD the register allocation must allow: 3 workgroups per CU in fp32 (80 VGPRs),
-//  2 in fp64 (128 VGPRs; its 66 KB of LDS allow no more))
-// (the body of k_subgrid_family, k_subgrid_family_open and k_subgrid_family_far: OPEN / FAR reach the blocks outside every cube only)
-template <class T, int KIND, int STAGE, bool WIDE, bool NT, bool OPEN, bool FAR = false>
-T8_DEV void subgrid_family(const T8gpuSubgridPlan& P, const SVars<T>& prev, const SVars<T>& src, const SVars<T>& out,
+// The second launch bound of k_subgrid_family = wavefronts per SIMD the register allocation must allow: 3 workgroups per CU in
+// fp32 (80 VGPRs), 2 in fp64 (128 VGPRs; its 66 KB of LDS allow no more).
+// (fp64 KEPES stages 2 and 3 with 64-bit addressing, far field: the rest blocks' far-field state does not fit 128 VGPRs beside the
+//  64-bit plane addresses -- 4 VGPRs spilled in a trial build --, so these four instantiations are bounded to 3 waves per SIMD,
+//  which is one workgroup per CU instead of two; planes of 4 GiB and more only)
+template <class T, int KIND, int STAGE, bool WIDE, int MODE>
+constexpr int family_waves_per_simd() {
+  return sizeof(T) == 8 ? (KIND == 0 && STAGE > 1 && WIDE && MODE == kBndFar ? 3 : 4) : 6;
+}
+// (the body of k_subgrid_family. MODE reaches the blocks outside every cube only: no cube holds a block with an open or
+//  far-field face)
+template <class T, int KIND, int STAGE, bool WIDE, bool NT, int MODE>
+T8_DEV void subgrid_family(const T8gpuSubgridPlan& P, const FVars<T>& prev, const FVars<T>& src, const FVars<T>& out,
                            const T* __restrict__ volumes, T dt) {
   constexpr int  NW    = CellData<T, KIND>::words;
   constexpr bool EARLY = sizeof(T) == 4;   // fp32: previous-step state requested up front; fp64: fetched last (registers)
   constexpr int FAM_WORDS = NW * 704 + 3 * 5 * 64 + 5 * 512;       // this kernel's arrays
-  constexpr int BLK_WORDS = NW * 112 + 5 * 64;                      // one wavefront of the block algorithm
-  constexpr int RESTB     = sizeof(T) == 8 ? 4 : 8;                 // leftover blocks per workgroup (fp64: LDS for 4 only)
+  constexpr int BLK_WORDS = block_lds_words(NW, 3);                 // one wavefront of the block algorithm ...
+  constexpr int BLK_PE    = NW * block_row(3);                      // ... its cell rows; the exchange buffer follows
+  // (constants, not calls in the pointer arithmetic below: called at run time, block_row is a function of the module
+  //  that this kernel and k_subgrid_family2 share, and that moved registers and instructions of 108 kernels)
+  constexpr int RESTB     = family_rest_blocks<T>();                // leftover blocks per workgroup
   __shared__ T lds[FAM_WORDS > RESTB * BLK_WORDS ? FAM_WORDS : RESTB * BLK_WORDS];
   const int tid = threadIdx.x, c = tid & 63;
   const int w   = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: the per-block reads below stay scalar
@@ -620,8 +608,8 @@ T8_DEV void subgrid_family(const T8gpuSubgridPlan& P, const SVars<T>& prev, cons
       T8gpuSubgridPlan R = P;
       R.block_rec        = P.rest_rec;
       T* const mine_lds  = lds + w * BLK_WORDS;
-      subgrid_block<T, KIND, STAGE, 3, sizeof(T) == 4, WIDE, true, NT, OPEN, FAR>(R, 0, P.n_rest, pos, c, prev, src, out, volumes, dt,
-                                                                             mine_lds, mine_lds + NW * 112);
+      subgrid_block<T, KIND, STAGE, 3, EARLY, WIDE, true, NT, MODE>(R, 0, P.n_rest, pos, c, prev, src, out, volumes, dt, mine_lds,
+                                                                    mine_lds + BLK_PE);
     }
     return;
   }
@@ -634,7 +622,7 @@ T8_DEV void subgrid_family(const T8gpuSubgridPlan& P, const SVars<T>& prev, cons
   // fluxes through the outward - faces in theirs ([k][lane]: slot s of the pooled round = slice 3 + s / 64, lane s % 64)
   T* const xall         = lds + NW * 704 + 3 * 5 * 64;
   T* const xw           = xall + w * 320;
-  const int4* __restrict__ frec = reinterpret_cast<const int4*>(P.fam_rec) + 40 * (size_t)sg_xcd_position(blockIdx.x, P.n_families);
+  const int4* __restrict__ frec = reinterpret_cast<const int4*>(P.fam_rec) + 40 * (size_t)xcd_position(blockIdx.x, P.n_families);
   const int    e0 = frec[0].x;
   const int    e  = e0 + w;
   const int    cc[3] = {c & 3, (c >> 2) & 3, c >> 4};
@@ -762,23 +750,10 @@ T8_DEV void subgrid_family(const T8gpuSubgridPlan& P, const SVars<T>& prev, cons
 #pragma unroll
   for (int k = 0; k < 5; k++) stream_store<NT>(&at<WIDE>(out.p[k], o), rk_stage_update<T, STAGE>(pv[k], s0[k], scale, acc[k]));
 }
-template <class T, int KIND, int STAGE, bool WIDE, bool NT>
-__global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_subgrid_family(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src, SVars<T> out,
-                                                        const T* __restrict__ volumes, T dt) {
-  subgrid_family<T, KIND, STAGE, WIDE, NT, false>(P, prev, src, out, volumes, dt);
-}
-template <class T, int KIND, int STAGE, bool WIDE, bool NT>
-__global__ __launch_bounds__(512, sizeof(T) == 8 ? 4 : 6) void k_subgrid_family_open(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src,
-                                                                                     SVars<T> out, const T* __restrict__ volumes, T dt) {
-  subgrid_family<T, KIND, STAGE, WIDE, NT, true>(P, prev, src, out, volumes, dt);
-}
-// (fp64 KEPES stages 2 and 3 with 64-bit addressing: the rest blocks' far-field state does not fit 128 VGPRs beside the 64-bit
-//  plane addresses -- 4 VGPRs spilled in a trial build --, so these four instantiations are bounded to 3 waves per SIMD, which
-//  is one workgroup per CU instead of two; planes of 4 GiB and more only)
-template <class T, int KIND, int STAGE, bool WIDE, bool NT>
-__global__ __launch_bounds__(512, sizeof(T) == 8 ? (KIND == 0 && STAGE > 1 && WIDE ? 3 : 4) : 6) void k_subgrid_family_far(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src,
-                                                                                    SVars<T> out, const T* __restrict__ volumes, T dt) {
-  subgrid_family<T, KIND, STAGE, WIDE, NT, true, true>(P, prev, src, out, volumes, dt);
+template <class T, int KIND, int STAGE, bool WIDE, bool NT, int MODE>
+__global__ __launch_bounds__(512, (family_waves_per_simd<T, KIND, STAGE, WIDE, MODE>())) void k_subgrid_family(
+    T8gpuSubgridPlan P, FVars<T> prev, FVars<T> src, FVars<T> out, const T* __restrict__ volumes, T dt) {
+  subgrid_family<T, KIND, STAGE, WIDE, NT, MODE>(P, prev, src, out, volumes, dt);
 }
 
 // (Round 4, measured and dropped: a PERSISTENT form of this kernel -- a resident grid of 2 (fp64) / 3 (fp32) workgroups per CU
@@ -802,20 +777,21 @@ __global__ __launch_bounds__(512, sizeof(T) == 8 ? (KIND == 0 && STAGE > 1 && WI
 // the + faces in lanes 0-15, 16 behind the - faces in lanes 16-31: one half-filled primitive round instead of the block
 // kernel's two). Same fluxes, same summation order: bitwise equal to the block kernel. The blocks outside every square run
 // behind the squares in the same launch (four per wavefront, the block algorithm).
-template <class T, int KIND, int STAGE, bool WIDE, bool NT, bool OPEN, bool FAR = false>
-T8_DEV void subgrid_family2(const T8gpuSubgridPlan& P, const SVars<T>& prev, const SVars<T>& src, const SVars<T>& out,
+template <class T, int KIND, int STAGE, bool WIDE, bool NT, int MODE>
+T8_DEV void subgrid_family2(const T8gpuSubgridPlan& P, const FVars<T>& prev, const FVars<T>& src, const FVars<T>& out,
                             const T* __restrict__ volumes, T dt) {
   constexpr int  NW        = CellData<T, KIND>::words;
   constexpr bool EARLY     = sizeof(T) == 4;
   constexpr int  FAM_WORDS = NW * 80 + 5 * 64 + 2 * 5 * 8 + 5 * 16;
-  constexpr int  BLK_WORDS = NW * 96 + 5 * 64;
+  constexpr int  BLK_WORDS = block_lds_words(NW, 2);
+  constexpr int  BLK_PE    = NW * block_row(2);   // (a constant: see subgrid_family)
   __shared__ T lds[FAM_WORDS > BLK_WORDS ? FAM_WORDS : BLK_WORDS];
   const int c = threadIdx.x;
   if (static_cast<int>(blockIdx.x) >= P.n_families) {   // the blocks outside every square: four per wavefront
     T8gpuSubgridPlan R = P;
     R.block_rec        = P.rest_rec;
-    subgrid_block<T, KIND, STAGE, 2, EARLY, WIDE, false, NT, OPEN, FAR>(R, 0, P.n_rest, static_cast<int>(blockIdx.x) - P.n_families, c, prev,
-                                                                    src, out, volumes, dt, lds, lds + NW * 96);
+    subgrid_block<T, KIND, STAGE, 2, EARLY, WIDE, false, NT, MODE>(R, 0, P.n_rest, static_cast<int>(blockIdx.x) - P.n_families, c, prev, src,
+                                                                   out, volumes, dt, lds, lds + BLK_PE);
     return;
   }
   // primitives [64 cells of the square, then 16 far cells behind the outward + faces ((d * 2 + j) * 4 + sub-face)];
@@ -825,7 +801,7 @@ T8_DEV void subgrid_family2(const T8gpuSubgridPlan& P, const SVars<T>& prev, con
   T* const xw        = lds + NW * 80;
   T(*const sfl)[5][8] = reinterpret_cast<T(*)[5][8]>(lds + NW * 80 + 320);
   T(*const mfl)[16]  = reinterpret_cast<T(*)[16]>(lds + NW * 80 + 320 + 80);
-  const int4* __restrict__ frec = reinterpret_cast<const int4*>(P.fam_rec) + 16 * (size_t)sg_xcd_position(blockIdx.x, P.n_families);
+  const int4* __restrict__ frec = reinterpret_cast<const int4*>(P.fam_rec) + 16 * (size_t)xcd_position(blockIdx.x, P.n_families);
   const int    e0 = frec[0].x;
   const int    w = c >> 4, cl = c & 15;
   const int    e  = e0 + w;
@@ -937,27 +913,10 @@ T8_DEV void subgrid_family2(const T8gpuSubgridPlan& P, const SVars<T>& prev, con
 #pragma unroll
   for (int k = 0; k < 5; k++) stream_store<NT>(&at<WIDE>(out.p[k], o), rk_stage_update<T, STAGE>(pv[k], s0[k], scale, acc[k]));
 }
-template <class T, int KIND, int STAGE, bool WIDE, bool NT>
-__global__ __launch_bounds__(64) void k_subgrid_family2(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src, SVars<T> out,
+template <class T, int KIND, int STAGE, bool WIDE, bool NT, int MODE>
+__global__ __launch_bounds__(64) void k_subgrid_family2(T8gpuSubgridPlan P, FVars<T> prev, FVars<T> src, FVars<T> out,
                                                         const T* __restrict__ volumes, T dt) {
-  subgrid_family2<T, KIND, STAGE, WIDE, NT, false>(P, prev, src, out, volumes, dt);
-}
-template <class T, int KIND, int STAGE, bool WIDE, bool NT>
-__global__ __launch_bounds__(64) void k_subgrid_family2_open(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src, SVars<T> out,
-                                                             const T* __restrict__ volumes, T dt) {
-  subgrid_family2<T, KIND, STAGE, WIDE, NT, true>(P, prev, src, out, volumes, dt);
-}
-template <class T, int KIND, int STAGE, bool WIDE, bool NT>
-__global__ __launch_bounds__(64) void k_subgrid_family2_far(T8gpuSubgridPlan P, SVars<T> prev, SVars<T> src, SVars<T> out,
-                                                            const T* __restrict__ volumes, T dt) {
-  subgrid_family2<T, KIND, STAGE, WIDE, NT, true, true>(P, prev, src, out, volumes, dt);
-}
-
-template <class T, class V>
-SVars<T> smk(const V& v) {
-  SVars<T> o;
-  for (int k = 0; k < 5; k++) o.p[k] = v.p[k];
-  return o;
+  subgrid_family2<T, KIND, STAGE, WIDE, NT, MODE>(P, prev, src, out, volumes, dt);
 }
 
 template <class T, class V>
@@ -967,9 +926,12 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
     return static_cast<int>(hipErrorInvalidValue);
   if (block_begin < 0 || block_count < 0 || block_begin + block_count > plan->num_elements) return static_cast<int>(hipErrorInvalidValue);
   if (block_count == 0) return 0;
-  const bool open = plan->has_open_faces != 0;   // outflow / inflow faces: the _open kernels
-  const bool far  = open && plan->has_farfield_faces != 0;   // ... and far-field faces: the _far kernels
-  if (open && !plan->inflow) return static_cast<int>(hipErrorInvalidValue);
+  // which boundary kinds the kernels decode: outflow / inflow faces take MODE kBndOpen, far-field faces as well kBndFar
+  const int mode = plan->has_open_faces == 0 ? kBndWalls : (plan->has_farfield_faces != 0 ? kBndFar : kBndOpen);
+  if (mode != kBndWalls && !plan->inflow) return static_cast<int>(hipErrorInvalidValue);
+  auto with_mode = [mode](auto&& f) {   // f(int_c<MODE>): the compile-time choice, made here for both launches below
+    return mode == kBndFar ? f(int_c<kBndFar>{}) : mode == kBndOpen ? f(int_c<kBndOpen>{}) : f(int_c<kBndWalls>{});
+  };
   stage_kernel_note_reset();
   hipStream_t s = static_cast<hipStream_t>(stream);
   // fp32 requests the previous-step state up front (one round trip less per wavefront); fp64 keeps fetching it last:
@@ -982,24 +944,16 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
   // one launch of the block kernel over records `pl.block_rec[begin, begin + count)`
   auto blocks = [&](const T8gpuSubgridPlan& pl, int begin, int count) {
     const dim3 grid(pl.rank == 3 ? count : (count + 3) / 4), block(64);
-    return dispatch(
-        [&](auto K, auto S, auto RANK3, auto WIDE, auto OPEN, auto FAR) {
-          constexpr int R = RANK3 ? 3 : 2;
-          if constexpr (OPEN && FAR) {
-            note_stage_kernel<T>(count, grid.x, "k_subgrid_fused_far", K, S, R, early, WIDE);
-            return launch(&k_subgrid_fused_far<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
-                          smk<T>(out), volumes, dt);
-          } else if constexpr (OPEN) {
-            note_stage_kernel<T>(count, grid.x, "k_subgrid_fused_open", K, S, R, early, WIDE);
-            return launch(&k_subgrid_fused_open<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
-                          smk<T>(out), volumes, dt);
-          } else {
-            note_stage_kernel<T>(count, grid.x, "k_subgrid_fused", K, S, R, early, WIDE);
-            return launch(&k_subgrid_fused<T, K, S, R, early, WIDE>, grid, block, 0, s, pl, begin, count, smk<T>(prev), smk<T>(mid),
-                          smk<T>(out), volumes, dt);
-          }
-        },
-        kind, stage, pl.rank == 3, wide, open, far);
+    return with_mode([&](auto MODE) {
+      return dispatch(
+          [&](auto K, auto S, auto RANK3, auto WIDE) {
+            constexpr int R = RANK3 ? 3 : 2;
+            note_stage_kernel<T>(count, grid.x, "k_subgrid_fused", K, S, R, early, WIDE, MODE);
+            return launch(&k_subgrid_fused<T, K, S, R, early, WIDE, MODE>, grid, block, 0, s, pl, begin, count, fmk<T>(prev), fmk<T>(mid),
+                          fmk<T>(out), volumes, dt);
+          },
+          kind, stage, pl.rank == 3, wide);
+    });
   };
   // A launch that covers the whole plan of a 3D mesh: 2x2x2 cubes of same-level blocks through the family kernel, the
   // other blocks through the block kernel (T8GPU_SG_FAMILY=0: every block through the block kernel -- same bits. Measured
@@ -1028,28 +982,19 @@ int subgrid_fused_stage(int kind, int stage, const T8gpuSubgridPlan* plan, int b
   fam.n_rest           = n_rest_here;
   // RANK 3: workgroups of eight wavefronts, `restb` leftover blocks per workgroup behind the cubes; RANK 2: one wavefront
   // per square, four leftover blocks per wavefront
-  const int  restb = plan->rank == 3 ? (sizeof(T) == 8 ? 4 : 8) : 4;   // (k_subgrid_family: RESTB)
+  const int  restb = plan->rank == 3 ? family_rest_blocks<T>() : 4;
   const dim3 grid(plan->n_families + (n_rest_here + restb - 1) / restb), block(plan->rank == 3 ? 512 : 64);
-  return dispatch(
-      [&](auto K, auto S, auto RANK3, auto WIDE, auto NT, auto OPEN, auto FAR) {
-        if constexpr (OPEN && FAR) {
-          const char* name   = RANK3 ? "k_subgrid_family_far" : "k_subgrid_family2_far";
-          const auto  kernel = RANK3 ? &k_subgrid_family_far<T, K, S, WIDE, NT> : &k_subgrid_family2_far<T, K, S, WIDE, NT>;
-          note_stage_kernel<T>(block_count, grid.x, name, K, S, WIDE, NT);
-          return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
-        } else if constexpr (OPEN) {   // (the cubes / squares hold no open-face block: the blocks behind them run the OPEN algorithm)
-          const char* name   = RANK3 ? "k_subgrid_family_open" : "k_subgrid_family2_open";
-          const auto  kernel = RANK3 ? &k_subgrid_family_open<T, K, S, WIDE, NT> : &k_subgrid_family2_open<T, K, S, WIDE, NT>;
-          note_stage_kernel<T>(block_count, grid.x, name, K, S, WIDE, NT);
-          return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
-        } else {
+  // (the cubes / squares hold no open-face block: the blocks behind them run the block algorithm of MODE)
+  return with_mode([&](auto MODE) {
+    return dispatch(
+        [&](auto K, auto S, auto RANK3, auto WIDE, auto NT) {
           const char* name   = RANK3 ? "k_subgrid_family" : "k_subgrid_family2";
-          const auto  kernel = RANK3 ? &k_subgrid_family<T, K, S, WIDE, NT> : &k_subgrid_family2<T, K, S, WIDE, NT>;
-          note_stage_kernel<T>(block_count, grid.x, name, K, S, WIDE, NT);
-          return launch(kernel, grid, block, 0, s, fam, smk<T>(prev), smk<T>(mid), smk<T>(out), volumes, dt);
-        }
-      },
-      kind, stage, plan->rank == 3, wide, nt, open, far);
+          const auto  kernel = RANK3 ? &k_subgrid_family<T, K, S, WIDE, NT, MODE> : &k_subgrid_family2<T, K, S, WIDE, NT, MODE>;
+          note_stage_kernel<T>(block_count, grid.x, name, K, S, WIDE, NT, MODE);
+          return launch(kernel, grid, block, 0, s, fam, fmk<T>(prev), fmk<T>(mid), fmk<T>(out), volumes, dt);
+        },
+        kind, stage, plan->rank == 3, wide, nt);
+  });
 }
 
 }  // namespace t8gpu_hip

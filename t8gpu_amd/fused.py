@@ -274,7 +274,7 @@ class T8gpuSubgridPlan(C.Structure):
                 ("n_interior_blocks", C.c_int32), ("n_deep_blocks", C.c_int32), ("n_blocks_addressed", C.c_int32),
                 ("fam_rec", C.c_void_p), ("rest_rec", C.c_void_p), ("n_families", C.c_int32), ("n_rest", C.c_int32),
                 # ABI 10: open boundaries -- the inflow table (device, [K][16]) and "the plan has outflow / inflow faces"
-                # ABI 12: "... and far-field faces" (the _far kernels)
+                # ABI 12: "... and far-field faces" (the kernels of MODE 2)
                 ("inflow", C.c_void_p), ("has_open_faces", C.c_int32), ("has_farfield_faces", C.c_int32)]
 
 
@@ -304,7 +304,7 @@ class SubgridPlan:
         self.c = c
 
     def attach_inflow(self, table):
-        """the device inflow table (t8gpu_hip_plain_inflow_table_*) the _open / _far kernels read: set once, before any launch"""
+        """the device inflow table (t8gpu_hip_plain_inflow_table_*) the kernels of MODE 1 / 2 read: set once, before any launch"""
         self._keep["inflow"] = table
         self.c.inflow = table.data_ptr()
 

@@ -139,11 +139,11 @@ def test_field_names_and_slots():
 def test_kernel_source_hash_is_the_one_of_the_committed_c4_profile():
     """fields.hip is an output pass, not a stage kernel: it and its helpers stay out of the hashed sources, so the c4
     traffic record (tied to the hash) stays valid. The record is the one scripts/commit_profile.py wrote for
-    profiles/r11_c4_f64_stage.md, taken when the compat tier's boundary kernels moved onto one face routine (compat_faces.hpp,
-    kernels_compat.hip and a host-side helper of fused_common.hpp among the hashed files; the fused kernels are those of r09,
-    their device code unchanged)."""
+    profiles/r12_c4_f64_stage.md, taken when the Subgrid stage kernels became three templates with a MODE argument
+    (kernels_subgrid_fused.hip, and BoundaryMode moved from compat_faces.hpp to fused_common.hpp, among the hashed files; c4
+    launches none of the changed kernels: its kernels are those of r09, their device code unchanged)."""
     records = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
-    tied = [r for r in records.values() if isinstance(r, dict) and r.get("source") == "profiles/r11_c4_f64_stage.md"]
-    assert len(tied) == 1 and tied[0]["kernel_source_hash"] == "93f38f202888225f"
+    tied = [r for r in records.values() if isinstance(r, dict) and r.get("source") == "profiles/r12_c4_f64_stage.md"]
+    assert len(tied) == 1 and tied[0]["kernel_source_hash"] == "84e6587bfd4c805f"
     assert build.kernel_source_hash() == tied[0]["kernel_source_hash"]
     assert os.path.exists(os.path.join(build.CSRC, "hip", "fields.hip"))

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 import _oracle as O
-from _gpu import NP, TOL1, TOL10, perturbed_state, rel_err
+from _gpu import NP, TOL1, TOL10, perturbed_state, rel_err, subgrid_boundary_notes
 from t8gpu_amd import hip
 from t8gpu_amd.solver import PlainSolver
 from t8gpu_amd.synth import SynthMesh
@@ -204,6 +204,9 @@ for g in (PlainSolver(SynthMesh(2, 4, 7, band=0.12).partition(), torch.float64, 
     g.iterate(1e-4)
     torch.cuda.synchronize()
     print(q().decode())
+from _gpu import subgrid_boundary_notes
+for mode, dim, name in subgrid_boundary_notes():
+    print(mode, dim, name, sep="|")
 """
 
 
@@ -226,7 +229,8 @@ def _library_kernels():
 def test_noted_stage_kernel_is_a_kernel_of_the_library(tmp_path):
     """t8gpu_hip_last_stage_kernel (what bench.py matches a committed profile with) names the heaviest launch of the last
     stage call as rocprofv3 prints it. Through every launch path of the plain and Subgrid stages the noted name must be a
-    kernel of the library, and the kernel that path launches."""
+    kernel of the library, and the kernel that path launches. A Subgrid kernel's last template argument is its MODE (0 walls
+    only, 1 open faces, 2 far-field faces as well): the noted name must end in the one the plan calls for."""
     import ctypes
     import os
     import subprocess
@@ -261,6 +265,9 @@ def test_noted_stage_kernel_is_a_kernel_of_the_library(tmp_path):
         g.iterate(1e-4)
         torch.cuda.synchronize()
         noted.append((expect, q().decode()))
+        assert noted[-1][1].endswith(", 0>")
+    family = {3: "k_subgrid_family", 2: "k_subgrid_family2"}
+    modes = [(family[dim], mode, name) for mode, dim, name in subgrid_boundary_notes()]   # the family launch
     # the persistent tile kernel and the Subgrid block kernel: switches read once per process
     here = os.path.dirname(os.path.abspath(__file__))
     script = tmp_path / "child.py"
@@ -268,11 +275,19 @@ def test_noted_stage_kernel_is_a_kernel_of_the_library(tmp_path):
     res = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, T8GPU_PERSISTENT="2", T8GPU_PERSISTENT_WGS="3", T8GPU_SG_FAMILY="0"))
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
-    noted += zip(("k_plain_persistent", "k_subgrid_fused"), res.stdout.splitlines()[-2:])
+    lines = res.stdout.splitlines()[-6:]
+    noted += zip(("k_plain_persistent", "k_subgrid_fused"), lines[:2])
+    assert lines[1].endswith(", 0>")
+    for line in lines[2:]:                                                                  # the block kernel
+        mode, _, name = line.split("|")
+        modes.append(("k_subgrid_fused", int(mode), name))
+    assert sorted(m for _, m, _ in modes) == [1] * 4 + [2] * 4
     kernels = _library_kernels()
     assert any(k.startswith("k_plain_stage<") for k in kernels)
     for expect, name in noted:
         assert name.split("<")[0] == expect and name in kernels, (expect, name)
+    for expect, mode, name in modes:
+        assert name.split("<")[0] == expect and name in kernels and name.endswith(f", {mode}>"), (expect, mode, name)
 
 
 @pytest.mark.parametrize("kind", [hip.KEPES, hip.HLL, hip.HLLC])
