@@ -56,6 +56,12 @@ def main():
                          "correct after it, rebind after every adapt; on several ranks every rank holds all particles and the "
                          "velocities are summed, one all_reduce per phase): positions and status are saved as .npy files beside "
                          "the images (prefix --vtk, or kh) at the end, and every --image-every steps")
+    ap.add_argument("--profile", type=int, default=None, metavar="LEVEL",
+                    help="save profiles against y on 2^LEVEL bins, averaged over x on the device (solver.average_along): mean "
+                         "density and Favre x-velocity, with --stats also reynolds_stress and tke formed from the space- and "
+                         "time-averaged sums (stats.average_along), as .npy files beside the images (prefix --vtk, or kh): at the "
+                         "end, and every --profile-every steps; prints the momentum thickness of the shear layers")
+    ap.add_argument("--profile-every", type=int, default=None, metavar="K")
     args = ap.parse_args()
     indicator, coarsen = None, None
     if args.indicator == "loehner":
@@ -114,6 +120,42 @@ def main():
             if rank == 0:
                 np.save(f"{prefix}_tke_{it:06d}.npy", image.cpu().numpy())
         say(f"images at it {it}: {prefix}_{{schlieren,density}}_{it:06d}.npy", flush=True)
+
+    def all_ranks(t):
+        """the sum of a device tensor over the ranks, on the device again"""
+        if world == 1:
+            return t
+        t = t.cpu() if rehearsal else t
+        dist.all_reduce(t)
+        return t.cuda()
+
+    def save_profiles(s, it):
+        """profiles against y, homogeneous in x (in 3D: and in z, axes=(0, 2)): every rank's partial sums and weights in
+        one block, one all-reduce, one division. The Favre velocity is mean(rho u) / mean(rho); the stresses are formed from
+        the averaged SUMS (results_of), never averaged per cell."""
+        axes, L = (0,), args.profile
+        sums, w = s.average_along(["density", "momentum"], axes, L, partial=True)
+        block = all_ranks(torch.cat([sums["density"][None], sums["momentum"], w[None]]))
+        rho, mx = (block[0] / block[-1]).cpu().numpy(), (block[1] / block[-1]).cpu().numpy()
+        u = mx / rho
+        prefix = args.vtk or "kh"
+        out = {"mean_density": rho, "favre_velocity_x": u}
+        if stats is not None and stats.weight > 0:
+            s15, w15 = stats.average_along(["reynolds_stress", "tke"], axes, L, partial=True)
+            block = all_ranks(torch.cat([s15, w15[None]]))
+            res = stats.results_of(block[:-1] / block[-1], ["reynolds_stress", "tke"])
+            out.update({name: t.cpu().numpy() for name, t in res.items()})
+        mass = float(s.monitor(dist=dist).integrals[0])
+        if rank == 0:
+            os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
+            for name, a in out.items():
+                np.save(f"{prefix}_profile_{name}_{it:06d}.npy", a)
+        # theta = int rho (U1 - u)(u - U2) dy / (rho0 (U1 - U2)^2) with U1, U2 the fastest and slowest stream of the profile:
+        # the sum over the shear layers of the periodic box
+        dy, du = 0.5 ** L, float(u.max() - u.min())
+        theta = float((rho * (u.max() - u) * (u - u.min())).sum() * dy / (rho.mean() * du * du)) if du > 0 else 0.0
+        say(f"profiles at it {it}: {prefix}_profile_{{{','.join(out)}}}_{it:06d}.npy  mass {mass:.17e}  "
+            f"momentum thickness {theta:.6e}", flush=True)
 
     def save_tracers(it):
         if rank == 0:                                    # (every rank holds the same particles)
@@ -176,6 +218,8 @@ def main():
             save_images(solver, it + 1)
         if tr is not None and args.image_every and (it + 1) % args.image_every == 0 and it + 1 < args.steps:
             save_tracers(it + 1)
+        if args.profile is not None and args.profile_every and (it + 1) % args.profile_every == 0 and it + 1 < args.steps:
+            save_profiles(solver, it + 1)
         if it % 100 == 0:
             mon = solver.monitor(dist=dist)
             drift = float(abs(mon.integrals - mass0).max())
@@ -184,6 +228,8 @@ def main():
     assert bool(torch.isfinite(solver.state()).all())
     if args.image:
         save_images(solver, args.steps)
+    if args.profile is not None:
+        save_profiles(solver, args.steps)
     if tr is not None:
         save_tracers(args.steps)
         active, left, lost = tr.counts()

@@ -695,11 +695,23 @@ int t8gpu_hip_subgrid_fields_f64(int rank, int num_blocks, T8gpuVars_f64 state, 
  * pixel and cell): a pixel inside a cell takes w q of that cell, a pixel covering several cells sums them in ascending
  * storage order in double. With weights = NULL sums[k][P] holds sum / weight instead, `fill` where the weight is 0. The order
  * of a sum does not depend on the launch: two calls give the same bits. Ranks combine by adding sums and weights.
+ * t8gpu_hip_sample_average: those per-pixel sums and weights of level `level` added along the mesh axes whose bits are set in
+ * axes_mask (bit a: axis a; a non-empty proper subset of the axes), without the image ever being written.
+ * With n = 2^level, A the averaged and K the kept axes in ascending order: a bin is a pixel of the kept axes, index
+ * sum p_K[i] n^i, and sums[k][bin], weights[bin] are [num_planes][n^|K|] and [n^|K|]. A reduced pixel of a bin has index
+ * r = sum p_A[i] n^i < R = n^|A|. Chunks hold T8GPU_SAMPLE_AVERAGE_CHUNK consecutive r; in chunk c lane j of one wavefront adds
+ * to +0 the pixels r = 4096 c + 64 t + j for t = 0 .. 63 in ascending order (r >= R skipped), the 64 lane values are combined
+ * by the xor butterfly v[j] = v[j] + v[j ^ s], s = 32, 16, 8, 4, 2, 1, and the chunk values of a bin are added to +0 in
+ * ascending chunk order; the same for the weights. With weights = NULL sums[k][bin] holds sum / weight, `fill` where the weight
+ * is 0. For R > 4096 `scratch` must hold n^|K| ceil(R / 4096) (num_planes + 1) doubles (a second small kernel adds the chunks);
+ * otherwise it may be NULL. host_average of t8gpu_amd/sample.py is the definition in numpy.
  * No atomics, no LDS. Return 0 without a launch for num_points = 0 (gather: or num_planes = 0); hipErrorInvalidValue, before any
  * launch, for dim outside {2, 3}, cells_per_axis outside {1, 4}, 2^31 or more owned cells, more than T8GPU_SAMPLE_PLANES
- * planes or a plane with q and d both NULL, a grid extent <= 0, level outside [0, D], uniform without a plane, a NULL array that would be used. */
+ * planes or a plane with q and d both NULL, a grid extent <= 0, level outside [0, D], uniform without a plane, a NULL array that would be used;
+ * average also for dim level > 36, an axes_mask that is empty, full or names an axis >= dim, 2^31 or more wavefronts. */
 #define T8GPU_SAMPLE_DEPTH 20
 #define T8GPU_SAMPLE_PLANES 16
+#define T8GPU_SAMPLE_AVERAGE_CHUNK 4096
 typedef struct T8gpuSamplePlanes_f32 { const float* q[16]; const double* d[16]; } T8gpuSamplePlanes_f32;
 typedef struct T8gpuSamplePlanes_f64 { const double* q[16]; const double* d[16]; } T8gpuSamplePlanes_f64;
 typedef struct T8gpuSampleGrid { double lo[3]; double hi[3]; int32_t n[3]; int32_t pad; } T8gpuSampleGrid;
@@ -721,6 +733,12 @@ int t8gpu_hip_sample_uniform_f32(int dim, int level, const uint64_t* keys, const
 int t8gpu_hip_sample_uniform_f64(int dim, int level, const uint64_t* keys, const int32_t* levels, int num_elements,
                                  int cells_per_axis, int num_planes, T8gpuSamplePlanes_f64 planes, double fill, double* sums,
                                  double* weights, void* stream);
+int t8gpu_hip_sample_average_f32(int dim, int level, int axes_mask, const uint64_t* keys, const int32_t* levels, int num_elements,
+                                 int cells_per_axis, int num_planes, T8gpuSamplePlanes_f32 planes, double fill, double* sums,
+                                 double* weights, double* scratch, void* stream);
+int t8gpu_hip_sample_average_f64(int dim, int level, int axes_mask, const uint64_t* keys, const int32_t* levels, int num_elements,
+                                 int cells_per_axis, int num_planes, T8gpuSamplePlanes_f64 planes, double fill, double* sums,
+                                 double* weights, double* scratch, void* stream);
 
 /* ---- tracer particles on Cartesian forests, advected by Heun's method (csrc/hip/tracers.hip) ---------------
  * A particle is a coordinate x[dim] in double, not a member of a cell. The forest arguments (keys, levels, num_elements,

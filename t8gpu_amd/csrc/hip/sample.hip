@@ -11,7 +11,8 @@
 // elements inside a dyadic pixel are one contiguous index range between two lower bounds.
 //
 // Everything is a gather: no atomics, no LDS, sums in ascending storage order by one lane, so two calls give the same
-// bits whatever the launch shape. Values are cast to double and never interpolated.
+// bits whatever the launch shape. Values are cast to double and never interpolated. The averages along homogeneous axes
+//  add such per-pixel sums across a wavefront, in an order that is part of their definition.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -87,6 +88,73 @@ __global__ __launch_bounds__(64) void k_sample_grid(T8gpuSampleGrid g, const uin
 // coarse as P or coarser holds P (it starts at kp: a itself; or before it: a - 1), or this rank owns nothing of P.
 // For blocks of level l the cells have level l + 2: L <= l is the range case over whole blocks, L = l + 1 takes the 2^dim
 // subcells of P's corner of the block, L >= l + 2 the one subcell that holds P.
+// What a pixel takes from the forest, found once per pixel: the range [a, b) of the range case, or the one element e that
+// holds P (-1: none), the subcells of it that P covers (first index, count per axis) and their common weight w.
+struct PixelCover {
+  int    a, b, e, first, cnt;
+  bool   range;
+  double w;
+};
+
+template <int DIM>
+__device__ __forceinline__ PixelCover pixel_cover(int L, int px, int py, int pz, const uint64_t* __restrict__ keys,
+                                                  const int32_t* __restrict__ levels, int n, int sub) {
+  const int      up = SAMPLE_D - L;
+  const uint64_t kp = key_of<DIM>((uint32_t)px << up, (uint32_t)py << up, DIM == 3 ? (uint32_t)pz << up : 0u);
+  const uint64_t sp = span_of<DIM>(L);
+  PixelCover     c;
+  c.a = count_before<true>(keys, n, kp), c.b = count_before<true>(keys, n, kp + sp);
+  c.range = c.b > c.a && levels[c.a] >= L;
+  c.e = -1, c.first = 0, c.cnt = 1;
+  c.w = 0.0;
+  if (!c.range) {
+    int e = c.b > c.a ? c.a : c.a - 1;
+    if (e >= 0 && kp - keys[e] >= span_of<DIM>(levels[e])) e = -1;
+    if (e >= 0) {
+      const int l = levels[e];
+      if (sub == 1 || L >= l + 2) {
+        c.w = ldexp(1.0, -DIM * L);
+        if (sub != 1) {
+          const int sh = L - l - 2;
+          c.first = ((px >> sh) & 3) + 4 * ((py >> sh) & 3) + (DIM == 3 ? 16 * ((pz >> sh) & 3) : 0);
+        }
+      } else {                                   // L = l + 1: half a block per axis
+        c.w     = ldexp(1.0, -DIM * (l + 2));
+        c.cnt   = 2;
+        c.first = 2 * (px & 1) + 8 * (py & 1) + (DIM == 3 ? 32 * (pz & 1) : 0);
+      }
+    }
+    c.e = e;
+  }
+  return c;
+}
+
+// sum of w q of plane k over the cells of a cover, in ascending storage order; ws receives the sum of w (the same for every k)
+template <class T, int DIM>
+__device__ __forceinline__ double pixel_sum(const PixelCover& c, const int32_t* __restrict__ levels, int sub,
+                                            const sample_planes_t<T>& src, int k, double& ws) {
+  const int S = sub == 1 ? 1 : (DIM == 3 ? 64 : 16);
+  double    s = 0.0;
+  ws = 0.0;
+  if (c.range) {
+    for (int el = c.a; el < c.b; el++) {
+      const double wl = ldexp(1.0, -DIM * (levels[el] + (sub == 1 ? 0 : 2)));
+      for (int i = 0; i < S; i++) {
+        s += wl * plane_value<T>(src, k, (size_t)el * S + i);
+        ws += wl;
+      }
+    }
+  } else if (c.e >= 0) {
+    for (int kk = 0; kk < (DIM == 3 ? c.cnt : 1); kk++)
+      for (int jj = 0; jj < c.cnt; jj++)
+        for (int ii = 0; ii < c.cnt; ii++) {
+          s += c.w * plane_value<T>(src, k, (size_t)c.e * S + c.first + ii + 4 * jj + 16 * kk);
+          ws += c.w;
+        }
+  }
+  return s;
+}
+
 template <class T, int DIM>
 __global__ __launch_bounds__(64) void k_sample_uniform(int L, const uint64_t* __restrict__ keys, const int32_t* __restrict__ levels,
                                                        int n, int sub, int n_planes, sample_planes_t<T> src, double fill,
@@ -96,56 +164,103 @@ __global__ __launch_bounds__(64) void k_sample_uniform(int L, const uint64_t* __
   if (!tile_pixel(side, side, px, py, pz)) return;
   const size_t pixels = (size_t)1 << (DIM * L);
   const size_t i      = (size_t)px + (size_t)side * ((size_t)py + (size_t)side * pz);
-  const int    up     = SAMPLE_D - L;
-  const uint64_t kp = key_of<DIM>((uint32_t)px << up, (uint32_t)py << up, DIM == 3 ? (uint32_t)pz << up : 0u);
-  const uint64_t sp = span_of<DIM>(L);
-  const int    S = sub == 1 ? 1 : (DIM == 3 ? 64 : 16);
-  const int    a = count_before<true>(keys, n, kp), b = count_before<true>(keys, n, kp + sp);
-  const bool   range = b > a && levels[a] >= L;
-  // the one element that may hold P, the subcells of it that P covers (first index, counts per axis), their common weight
-  int    e = -1, first = 0, cnt = 1;
-  double w = 0.0;
-  if (!range) {
-    e = b > a ? a : a - 1;
-    if (e >= 0 && kp - keys[e] >= span_of<DIM>(levels[e])) e = -1;
-    if (e >= 0) {
-      const int l = levels[e];
-      if (sub == 1 || L >= l + 2) {
-        w = ldexp(1.0, -DIM * L);
-        if (sub != 1) {
-          const int sh = L - l - 2;
-          first = ((px >> sh) & 3) + 4 * ((py >> sh) & 3) + (DIM == 3 ? 16 * ((pz >> sh) & 3) : 0);
-        }
-      } else {                                   // L = l + 1: half a block per axis
-        w     = ldexp(1.0, -DIM * (l + 2));
-        cnt   = 2;
-        first = 2 * (px & 1) + 8 * (py & 1) + (DIM == 3 ? 32 * (pz & 1) : 0);
-      }
-    }
-  }
+  const PixelCover c = pixel_cover<DIM>(L, px, py, pz, keys, levels, n, sub);
   double wsum = 0.0;
   for (int k = 0; k < n_planes; k++) {
-    double s = 0.0, ws = 0.0;
-    if (range) {
-      for (int el = a; el < b; el++) {
-        const double wl = ldexp(1.0, -DIM * (levels[el] + (sub == 1 ? 0 : 2)));
-        for (int c = 0; c < S; c++) {
-          s += wl * plane_value<T>(src, k, (size_t)el * S + c);
-          ws += wl;
-        }
-      }
-    } else if (e >= 0) {
-      for (int kk = 0; kk < (DIM == 3 ? cnt : 1); kk++)
-        for (int jj = 0; jj < cnt; jj++)
-          for (int ii = 0; ii < cnt; ii++) {
-            s += w * plane_value<T>(src, k, (size_t)e * S + first + ii + 4 * jj + 16 * kk);
-            ws += w;
-          }
-    }
+    double       ws;
+    const double s = pixel_sum<T, DIM>(c, levels, sub, src, k, ws);
     wsum = ws;
     sums[(size_t)k * pixels + i] = weights ? s : (ws > 0.0 ? s / ws : fill);
   }
   if (weights) weights[i] = wsum;                // (the same sum of w for every plane)
+}
+
+// ---- average: the uniform sums of level L added along the mesh axes of `mask`, one wavefront per (bin, chunk) -----------------
+// A bin is a pixel of the kept axes, index sum p_K[i] side^i over the kept axes K ascending; a reduced pixel of it has index
+// r = sum p_A[i] side^i over the averaged axes A ascending, r < R = side^|A|. Chunk c of a bin holds r in [4096 c, 4096 c + 4096):
+// lane j adds to +0 the pixels r = 4096 c + 64 t + j for t = 0 .. 63 ascending (r >= R: skipped), the 64 lane values meet in the
+// xor butterfly s = 32 .. 1, and the chunk values of a bin are added to +0 in ascending c (here when there is one chunk, else by
+// k_sample_average_finish from `scratch`). host_average of sample.py is this in numpy. The sums sit in registers: the plane loop
+// is unrolled over T8GPU_SAMPLE_PLANES with constant indices.
+constexpr int AVG_CHUNK = T8GPU_SAMPLE_AVERAGE_CHUNK;
+static_assert(AVG_CHUNK == 64 * 64, "a chunk is 64 rounds of one wavefront");
+
+__device__ __forceinline__ double wave_butterfly(double v) {
+  for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_xor(v, s, 64);
+  return v;
+}
+
+template <class T, int DIM>
+__global__ __launch_bounds__(64) void k_sample_average(int L, int mask, uint64_t R, unsigned chunks, const uint64_t* __restrict__ keys,
+                                                       const int32_t* __restrict__ levels, int n, int sub, int n_planes,
+                                                       sample_planes_t<T> src, double fill, size_t bins, double* __restrict__ sums,
+                                                       double* __restrict__ weights, double* __restrict__ scratch) {
+  const unsigned chunk = blockIdx.x % chunks;
+  const uint64_t bin   = blockIdx.x / chunks;
+  const int      lane  = threadIdx.x;
+  const uint32_t low   = (1u << L) - 1u;
+  double         acc[T8GPU_SAMPLE_PLANES];
+  double         wacc = 0.0;
+#pragma unroll
+  for (int k = 0; k < T8GPU_SAMPLE_PLANES; k++) acc[k] = 0.0;
+  for (int t = 0; t < 64; t++) {
+    const uint64_t r = (uint64_t)chunk * AVG_CHUNK + (uint64_t)(64 * t + lane);
+    if (r < R) {
+      uint64_t rr = r, bb = bin;
+      int      p[3] = {0, 0, 0};
+#pragma unroll
+      for (int a = 0; a < DIM; a++) {
+        if ((mask >> a) & 1) {
+          p[a] = (int)(rr & low);
+          rr >>= L;
+        } else {
+          p[a] = (int)(bb & low);
+          bb >>= L;
+        }
+      }
+      const PixelCover c = pixel_cover<DIM>(L, p[0], p[1], p[2], keys, levels, n, sub);
+      double           ws = 0.0;
+#pragma unroll
+      for (int k = 0; k < T8GPU_SAMPLE_PLANES; k++)
+        if (k < n_planes) acc[k] = acc[k] + pixel_sum<T, DIM>(c, levels, sub, src, k, ws);
+      wacc = wacc + ws;
+    }
+  }
+  wacc = wave_butterfly(wacc);
+#pragma unroll
+  for (int k = 0; k < T8GPU_SAMPLE_PLANES; k++)
+    if (k < n_planes) acc[k] = wave_butterfly(acc[k]);
+  if (lane != 0) return;
+  if (chunks > 1) {                              // scratch[bin][chunk][planes + 1], the weight last
+    double* out = scratch + ((size_t)bin * chunks + chunk) * (size_t)(n_planes + 1);
+#pragma unroll
+    for (int k = 0; k < T8GPU_SAMPLE_PLANES; k++)
+      if (k < n_planes) out[k] = acc[k];
+    out[n_planes] = wacc;
+    return;
+  }
+  wacc = 0.0 + wacc;                             // (one chunk added to +0: the same bits, written for the definition's sake)
+#pragma unroll
+  for (int k = 0; k < T8GPU_SAMPLE_PLANES; k++)
+    if (k < n_planes) sums[(size_t)k * bins + bin] = weights ? acc[k] : (wacc > 0.0 ? acc[k] / wacc : fill);
+  if (weights) weights[bin] = wacc;
+}
+
+// one lane per (bin, plane): the chunk values of the plane and of the weight added to +0 in ascending chunk order
+__global__ __launch_bounds__(256) void k_sample_average_finish(size_t bins, unsigned chunks, int n_planes, const double* __restrict__ scratch,
+                                                               double fill, double* __restrict__ sums, double* __restrict__ weights) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= bins * (size_t)n_planes) return;
+  const size_t  bin = i / n_planes;
+  const int     k   = (int)(i % n_planes);
+  const double* in  = scratch + bin * chunks * (size_t)(n_planes + 1);
+  double        s = 0.0, w = 0.0;
+  for (unsigned c = 0; c < chunks; c++) {
+    s = s + in[(size_t)c * (n_planes + 1) + k];
+    w = w + in[(size_t)c * (n_planes + 1) + n_planes];
+  }
+  sums[(size_t)k * bins + bin] = weights ? s : (w > 0.0 ? s / w : fill);
+  if (weights && k == 0) weights[bin] = w;
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
@@ -225,9 +340,50 @@ int sample_uniform(int dim, int level, const uint64_t* keys, const int32_t* leve
   return static_cast<int>(hipGetLastError());
 }
 
+template <class T>
+int sample_average(int dim, int level, int mask, const uint64_t* keys, const int32_t* levels, int n, int sub, int n_planes,
+                   sample_planes_t<T> src, double fill, double* sums, double* weights, double* scratch, void* stream) {
+  if (bad_forest(dim, n, keys, levels, sub) || bad_planes<T>(n_planes, src)) return static_cast<int>(hipErrorInvalidValue);
+  if (level < 0 || level > SAMPLE_D || dim * level > 36) return static_cast<int>(hipErrorInvalidValue);
+  if (n_planes == 0 || !sums) return static_cast<int>(hipErrorInvalidValue);
+  const int full = (1 << dim) - 1;
+  if (mask <= 0 || mask >= full) return static_cast<int>(hipErrorInvalidValue);      // a non-empty proper subset of the axes
+  const int      averaged = __builtin_popcount((unsigned)mask);
+  const uint64_t R        = (uint64_t)1 << (level * averaged);
+  const size_t   bins     = (size_t)1 << (level * (dim - averaged));
+  const uint64_t chunks   = (R + AVG_CHUNK - 1) / AVG_CHUNK;
+  const uint64_t blocks   = bins * chunks;
+  if (blocks >= ((uint64_t)1 << 31) || (chunks > 1 && !scratch)) return static_cast<int>(hipErrorInvalidValue);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dim == 3)
+    hipLaunchKernelGGL((k_sample_average<T, 3>), dim3((unsigned)blocks), dim3(64), 0, s, level, mask, R, (unsigned)chunks, keys, levels, n,
+                       sub, n_planes, src, fill, bins, sums, weights, scratch);
+  else
+    hipLaunchKernelGGL((k_sample_average<T, 2>), dim3((unsigned)blocks), dim3(64), 0, s, level, mask, R, (unsigned)chunks, keys, levels, n,
+                       sub, n_planes, src, fill, bins, sums, weights, scratch);
+  int err = static_cast<int>(hipGetLastError());
+  if (err != 0 || chunks == 1) return err;
+  const size_t lanes = bins * (size_t)n_planes;
+  hipLaunchKernelGGL(k_sample_average_finish, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, bins, (unsigned)chunks, n_planes,
+                     scratch, fill, sums, weights);
+  return static_cast<int>(hipGetLastError());
+}
+
 }  // namespace t8gpu_hip
 
 extern "C" {
+int t8gpu_hip_sample_average_f32(int dim, int level, int axes_mask, const uint64_t* keys, const int32_t* levels, int num_elements,
+                                 int cells_per_axis, int num_planes, T8gpuSamplePlanes_f32 planes, double fill, double* sums,
+                                 double* weights, double* scratch, void* stream) {
+  return t8gpu_hip::sample_average<float>(dim, level, axes_mask, keys, levels, num_elements, cells_per_axis, num_planes, planes, fill,
+                                          sums, weights, scratch, stream);
+}
+int t8gpu_hip_sample_average_f64(int dim, int level, int axes_mask, const uint64_t* keys, const int32_t* levels, int num_elements,
+                                 int cells_per_axis, int num_planes, T8gpuSamplePlanes_f64 planes, double fill, double* sums,
+                                 double* weights, double* scratch, void* stream) {
+  return t8gpu_hip::sample_average<double>(dim, level, axes_mask, keys, levels, num_elements, cells_per_axis, num_planes, planes, fill,
+                                           sums, weights, scratch, stream);
+}
 int t8gpu_hip_sample_locate(int dim, size_t num_points, const double* points, const uint64_t* keys, const int32_t* levels,
                             int num_elements, int cells_per_axis, int32_t* cells, void* stream) {
   return t8gpu_hip::sample_locate(dim, num_points, points, keys, levels, num_elements, cells_per_axis, cells, stream);

@@ -6,8 +6,9 @@ The geometry is one array of Morton keys. With D = DEPTH = 20 the integer coordi
 of a point the bit-interleave of its integer coordinates (x in the lowest bit), the key of an element that of its lower
 corner. In storage order the keys of a SynthMesh partition ascend strictly and are contiguous, key[i + 1] = key[i] +
 2^(dim (D - level[i])), so the cell of a point is upper_bound(keys, key(point)) - 1 plus one containment check, and the
-leaves inside a dyadic pixel are one contiguous index range. `morton_keys` and `host_locate` are numpy and need no GPU;
-`Sampler` is what `_Solver.locate / sample_points / sample_grid / resample_uniform` forward to.
+leaves inside a dyadic pixel are one contiguous index range. `morton_keys`, `host_locate` and `host_average` (the definition
+of the averages along homogeneous axes) are numpy and need no GPU; `Sampler` is what `_Solver.locate /
+sample_points / sample_grid / resample_uniform / average_along` forward to.
 """
 import ctypes as C
 import math
@@ -19,6 +20,7 @@ from .synth import SynthMesh
 
 DEPTH = 20                      # T8GPU_SAMPLE_DEPTH
 MAX_PLANES = 16                 # T8GPU_SAMPLE_PLANES: planes of one launch
+AVERAGE_CHUNK = 4096            # T8GPU_SAMPLE_AVERAGE_CHUNK: reduced pixels one wavefront adds up (host_average)
 # name -> (first plane of a step's five, planes): the conserved names; the derived ones are fields.FIELDS
 STATE = {"density": (0, 1), "momentum": (1, 3), "energy": (4, 1)}
 NAMES = tuple(STATE) + tuple(fields.FIELDS)
@@ -144,6 +146,62 @@ def host_locate(part, points, subgrid=None, keys=None):
             cell += (((idx[:, a] >> sh) & np.uint64(3)).astype(np.int64)) << (2 * a)
     out[ok] = np.where(held, cell, -1).astype(np.int32)
     return out
+
+
+def check_axes(axes, dim):
+    """`axes` (one mesh axis or several) as an ascending tuple: non-empty, without repeats, each in 0..dim-1 and not all of
+    them (the mean over every axis is monitor()'s); ValueError otherwise"""
+    try:
+        given = [axes] if isinstance(axes, (int, np.integer)) else list(axes)
+        ax = [int(a) for a in given]
+        if any(a != g for a, g in zip(ax, given)):
+            raise TypeError
+    except TypeError:
+        raise ValueError(f"axes must be a mesh axis or a tuple of them, got {axes!r}") from None
+    if not ax or len(set(ax)) != len(ax) or any(not 0 <= a < dim for a in ax) or len(ax) >= dim:
+        raise ValueError(f"axes must be a non-empty proper subset of 0..{dim - 1} without repeats, got {axes!r}")
+    return tuple(sorted(ax))
+
+
+def host_average(sums, weights, axes, level, fill=math.nan, partial=False):
+    """The definition of average_along in numpy: sums[planes, n, ...] and weights[n, ...] per pixel of the
+    n = 2^level grid, as resample_uniform(partial=True) gives them (mesh axis a is array axis dim - 1 - a), added along the
+    mesh axes `axes` (check_axes). The result runs over the kept axes in image order, highest kept axis first: sums / weights
+    [planes, bins...], `fill` where the weight is 0, or with partial=True (sums, weights) over the bins.
+    The order of the additions is what the device follows bit for bit. With A the averaged axes ascending, a reduced pixel has
+    index r = sum p_A[i] n^i < R = n^|A|. Chunk c holds the AVERAGE_CHUNK = 4096 indices from 4096 c on: lane j (0..63) adds to
+    +0, for t = 0..63 ascending, the pixel r = 4096 c + 64 t + j (r >= R: +0); the lanes are combined by the xor butterfly
+    v[j] = v[j] + v[j ^ s] for s = 32, 16, 8, 4, 2, 1; the chunk values of a bin are added to +0 in ascending chunk order."""
+    weights = np.asarray(weights, np.float64)
+    dim, n = weights.ndim, 1 << int(level)
+    sums = np.asarray(sums, np.float64)
+    if weights.shape != (n,) * dim or sums.ndim != dim + 1 or sums.shape[1:] != weights.shape:
+        raise ValueError(f"sums [planes, ...] and weights must be level-{level} images, got {sums.shape} and {weights.shape}")
+    avg = check_axes(axes, dim)
+    kept = [a for a in range(dim) if a not in avg]
+    # array axes: the kept ones highest mesh axis first, then the averaged ones highest first, so that r runs lowest axis fastest
+    order = [dim - 1 - a for a in reversed(kept)] + [dim - 1 - a for a in reversed(avg)]
+    bins, R = (n,) * len(kept), n ** len(avg)
+    chunks = -(-R // AVERAGE_CHUNK)
+    x = np.concatenate([sums, weights[None]]).transpose([0] + [1 + o for o in order]).reshape(sums.shape[0] + 1, -1, R)
+    pad = np.zeros(x.shape[:2] + (chunks * AVERAGE_CHUNK,))
+    pad[..., :R] = x
+    pad = pad.reshape(x.shape[:2] + (chunks, 64, 64))               # [..., chunk, t, lane]
+    lanes = np.zeros(x.shape[:2] + (chunks, 64))
+    for t in range(64):
+        lanes = lanes + pad[..., t, :]
+    j = np.arange(64)
+    for s in (32, 16, 8, 4, 2, 1):
+        lanes = lanes + lanes[..., j ^ s]
+    total = np.zeros(x.shape[:2])
+    for c in range(chunks):
+        total = total + lanes[..., c, 0]
+    total = total.reshape((-1,) + bins)
+    s, w = total[:-1], total[-1]
+    if partial:
+        return s, w
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(w > 0.0, s / w, fill)
 
 
 class Sampler:
@@ -311,6 +369,33 @@ class Sampler:
                            C.c_double(fill), self._hip.ptr(out), self._hip.ptr(weights), self._hip.stream_ptr(stream))
             del keep
         res = self._split(names, out, image, extra)
+        return (res, weights) if partial else res
+
+    def average_along(self, names, axes, level, step=None, stream=None, halo=None, fill=math.nan, partial=False, extra=None):
+        import torch
+        level = int(level)
+        if not 0 <= level <= DEPTH:
+            raise ValueError(f"level must lie in 0..{DEPTH}, got {level}")
+        avg = check_axes(axes, self.dim)
+        if self.dim * level > 36:
+            raise ValueError(f"level {level} has 2^{self.dim * level} pixels: one call takes 2^36")
+        kept = self.dim - len(avg)
+        bins, count = (1 << level,) * kept, 1 << (level * kept)
+        chunks = -(-(1 << (level * len(avg))) // AVERAGE_CHUNK)
+        stream = self._stream(stream)
+        extra = check_extra(extra, self.solver.owned_cells)
+        with torch.cuda.stream(stream):
+            names, src, total, keep = self._sources(names, step, stream, halo, extra)
+            if total == 0:
+                raise ValueError("average_along needs at least one name")
+            out = torch.empty((total, count), dtype=torch.float64, device="cuda")
+            weights = torch.empty(bins, dtype=torch.float64, device="cuda") if partial else None
+            scratch = torch.empty((count, chunks, total + 1), dtype=torch.float64, device="cuda") if chunks > 1 else None
+            self._hip.call("t8gpu_hip_sample_average", self.solver.dtype, self.dim, level, sum(1 << a for a in avg), *self._forest(),
+                           total, src, C.c_double(fill), self._hip.ptr(out), self._hip.ptr(weights), self._hip.ptr(scratch),
+                           self._hip.stream_ptr(stream))
+            del keep, scratch                       # (freed on this stream: the next allocation there follows the kernels)
+        res = self._split(names, out, bins, extra)
         return (res, weights) if partial else res
 
 

@@ -397,6 +397,16 @@ class _Solver:
         from . import sample
         return sample.sampler(self).resample_uniform(names, level, step, stream, halo, fill, partial, extra)
 
+    def average_along(self, names, axes, level, step=None, stream=None, halo=None, fill=float("nan"), partial=False, extra=None):
+        """resample_uniform at `level` averaged along the mesh axes `axes` (an int or a tuple: a non-empty proper subset of the
+        axes), without the image being written: {name: float64 device tensor} over the kept axes, highest first
+        -- 3D with axes=(2,) gives [ny, nx], with axes=(0, 2) [ny], 2D with axes=(0,) [ny]; [3, ...] for vectors. Per bin
+        sum(w q) / sum(w) over the pixels of the slab, added in the fixed order sample.host_average states, so two calls give
+        the same bits; `fill` where this rank owns nothing of the slab. partial=True: ({name: sums}, weights) instead, for
+        ranks to add up and divide once."""
+        from . import sample
+        return sample.sampler(self).average_along(names, axes, level, step, stream, halo, fill, partial, extra)
+
     # -- tracer particles (tracers.py, DESIGN.md §15): coordinates advected by Heun's method around the flow step --------------
     def tracers(self, points, stream=None):
         """A tracers.Tracers of points[M, dim] (a host or device array, taken to float64) on this solver's mesh: predict(dt)

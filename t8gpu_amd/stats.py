@@ -77,13 +77,18 @@ class Statistics:
         [3, cells] for mean_momentum and mean_velocity, [6, cells] (xx yy zz xy xz yz) for reynolds_stress. One launch; only
         the planes asked for are written. `out` ({name: tensor of that shape}) receives them instead of new tensors. An
         unknown name raises ValueError (listing the valid ones), and so does a call before any accumulate."""
-        import torch
-        from . import hip
         names = check_names(names)
         if not self.weight > 0.0:
             raise ValueError("results() needs weight > 0: nothing has been accumulated")
+        return self._results(self.sums, (self.solver.owned_cells,), names, self.weight, stream, out)
+
+    @staticmethod
+    def _results(sums, shape, names, weight, stream=None, out=None):
+        """the result kernel over sums [15, cells] (rows contiguous), each result in the shape `shape` of one plane"""
+        import torch
+        from . import hip
         stream = torch.cuda.current_stream() if stream is None else stream
-        cells = self.solver.owned_cells
+        cells = sums.shape[1]
         res, planes = {}, StatsPlanes()
         with torch.cuda.stream(stream):
             for name in names:
@@ -96,11 +101,55 @@ class Statistics:
                     t = torch.empty((count, cells), dtype=torch.float64, device="cuda")
                 for k in range(count):
                     planes.p[first + k] = t[k].data_ptr()
-                res[name] = t[0] if count == 1 else t
+                res[name] = t[0].view(shape) if count == 1 else t.view((count,) + tuple(shape))
         lib = hip.lib()
         lib.t8gpu_hip_stats_results.restype = C.c_int
-        hip.check(lib.t8gpu_hip_stats_results(C.c_size_t(cells), hip.ptr(self.sums), C.c_size_t(self.sums.stride(0)),
-                                              C.c_double(self.weight), planes, hip.stream_ptr(stream)))
+        hip.check(lib.t8gpu_hip_stats_results(C.c_size_t(cells), hip.ptr(sums), C.c_size_t(sums.stride(0)),
+                                              C.c_double(weight), planes, hip.stream_ptr(stream)))
+        return res
+
+    def results_of(self, sums15, names, weight=None, stream=None):
+        """`results` formed from any float64 device tensor sums15 [15, ...] of sums in the slots SLOTS, e.g. the space-averaged
+        sums of average_along(partial=True) after the ranks' all-reduce and the division by the added weights: {name: tensor
+        over the trailing shape}, [3, ...] / [6, ...] as in results. weight (default: this object's) is the time weight the
+        sums carry; it must be > 0 (ValueError)."""
+        import torch
+        names = check_names(names)
+        w = self.weight if weight is None else check_weight(weight)
+        if not w > 0.0:
+            raise ValueError("results_of() needs weight > 0: nothing has been accumulated")
+        ok = isinstance(sums15, torch.Tensor) and sums15.is_cuda and sums15.dtype == torch.float64 and sums15.dim() >= 1 and \
+            sums15.shape[0] == PLANES
+        if not ok:
+            raise ValueError(f"sums15 must be a float64 device tensor [{PLANES}, ...]")
+        shape = tuple(sums15.shape[1:])
+        flat = sums15.reshape(PLANES, -1)
+        if flat.shape[1] and flat.stride(1) != 1:
+            flat = flat.contiguous()
+        return self._results(flat, shape, names, w, stream)
+
+    def average_along(self, names, axes, level, stream=None, fill=math.nan, partial=False):
+        """The statistics `names` of the slabs of solver.average_along(axes, level): the fifteen running sums go
+        through one averaging call as an extra [15, cells] field, are divided by the bin weights, and the result formulas
+        run over the bins -- so the Favre mean, the rms values, the Reynolds stress and tke of a bin are formed from the
+        space-and-time averaged SUMS, not averaged per cell (the formulas are nonlinear; a mean of per-cell stresses would miss
+        the part of the fluctuation that is the cells' means differing along the axis). Bins this rank owns nothing of get
+        `fill`. partial=True: (sums [15, bins...], weights [bins...]) instead; ranks add both up, divide, and call
+        results_of. Raises ValueError before any accumulate, as results does."""
+        import torch
+        names = check_names(names)
+        if not self.weight > 0.0:
+            raise ValueError("average_along() needs weight > 0: nothing has been accumulated")
+        stream = torch.cuda.current_stream() if stream is None else stream
+        got, weights = self.solver.average_along("stats_sums", axes, level, stream=stream, partial=True,
+                                                 extra={"stats_sums": self.sums})
+        if partial:
+            return got["stats_sums"], weights
+        with torch.cuda.stream(stream):
+            res = self.results_of(got["stats_sums"] / weights, names, stream=stream)
+            empty = weights == 0.0
+            for t in res.values():
+                t.masked_fill_(empty, fill)
         return res
 
     def reset(self, stream=None):
