@@ -847,7 +847,9 @@ int t8gpu_hip_stats_results(size_t num_cells, const double* sums, size_t plane_s
  * the output fields above (CSR order; inside a hanging face j-major, i-minor; in-block faces first): two calls, same bits.
  * Plain: one lane per owned element, writes out[num_elements]; dim is the mesh dimension of h (2 for a 2D mesh stored with
  * normal_dim = 3). Subgrid: writes cell_out[num_blocks S] (per subcell, storage order) and block_out[num_blocks] (the maximum
- * over the block's subcells); either may be NULL and is then left alone.
+ * over the block's subcells); either may be NULL and is then left alone. Subgrid: A_s of a sub-face is min(h_c, h_o)^(rank - 1),
+ * from the block volumes like the faces inside a block (on dyadic geometry the bits of face_surfaces / sub-faces; one source
+ * of lengths keeps E scale-free where areas and volumes are rounded separately); face_surfaces must be given and is not read.
  * Returns 0 for n <= 0; hipErrorInvalidValue, before any launch, for a NULL state plane or connectivity pointer, an empty
  * mask, a bit above 3, filter < 0, normal_dim / dim / rank outside {2, 3}.
  * t8gpu_hip_indicator_spread: one buffer layer, out[e] = max(in[e], in[o] over the face neighbours o of e) for the owned

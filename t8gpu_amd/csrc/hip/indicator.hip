@@ -248,8 +248,13 @@ __global__ __launch_bounds__(64) void k_subgrid_indicator(int N, unsigned mask, 
         const int    ob    = fn[ent ^ 1];                                // the block across (may be a ghost block)
         const size_t other = (size_t)ob * S;
         const double sign  = side ? -1.0 : 1.0;
-        const double A     = (double)areas[f] / SF;
-        const double d     = 0.5 * (h + cell_length((double)volumes[ob], RANK) * 0.25);
+        // A sub-face is a face of a subcell of the finer block: its area from that block's VOLUME, as the in-block faces', not
+        // from areas[f] / SF. On dyadic geometry the two are the same bits (cell_length); where areas and volumes are rounded
+        // separately (fp32 storage of a box that is not the unit cube) only one source of lengths keeps E scale-free.
+        const double ho    = cell_length((double)volumes[ob], RANK) * 0.25;
+        const double hf    = fmin(h, ho);
+        const double A     = RANK == 3 ? hf * hf : hf;
+        const double d     = 0.5 * (h + ho);
         for (int t = 0; t < nterm; t++) {        // a hanging face from its coarse side: j-major, i-minor
           const int flat = (fixed << (2 * a)) + ((b1 + (t & 1)) << (2 * t1)) + ((b2 + (t >> 1)) << (2 * t2));
           load_quantities<T>(st, other + flat, mask, qo);

@@ -95,7 +95,9 @@ def subgrid_indicator(u, part, npdt, names, eps):
     off[:, :rank] = np.asarray(part.nb_offset).reshape(F, rank)
     lflat, rflat = sg_face_cells(n, off, np.asarray(part.level_diff) != 0, rank)
     a, b = (l[:, None] * S + lflat).reshape(-1), (r[:, None] * S + rflat).reshape(-1)
-    acc.scatter(a, b, np.repeat(rounded(part.areas, npdt)[:F] / SF, SF), np.repeat(n, SF, axis=0), h, qs, eps)
+    # a sub-face is a subcell face of the finer of the two blocks: its area from that block's volume, as inside the blocks (on
+    # dyadic geometry the bits of areas / SF; lengths from ONE source keep E scale-free where areas and volumes round apart)
+    acc.scatter(a, b, np.repeat(np.minimum(hb[l], hb[r]) ** (rank - 1), SF), np.repeat(n, SF, axis=0), h, qs, eps)
     return acc.value(N * S)
 
 

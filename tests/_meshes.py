@@ -53,6 +53,41 @@ def partition(name, rank=0, nranks=1, periodic=True, sides=None):
     return shape(name, periodic, sides).partition(rank, nranks, subgrid=is_subgrid(name))
 
 
+class Scaled:
+    """A partition of the box [0, s_x] x [0, s_y] (x [0, s_z]) with the connectivity of `part` (see scaled): its own areas,
+    volumes and centres; every other attribute is the one of `part`."""
+
+    def __init__(self, part, s):
+        dim = part.mesh.dim
+        s = np.asarray(s, np.float64)
+        if s.ndim == 0:
+            s = np.full(dim, float(s))
+        elif part.subgrid:
+            raise ValueError("a Subgrid block has one inner sub-face area, derived from its volume: no per-axis stretch")
+        if s.shape != (dim,) or not (s > 0).all():
+            raise ValueError(f"one positive factor, or one per axis of a {dim}D mesh")
+        normals = np.asarray(part.normals, np.float64).reshape(part.F + part.B, part.normal_dim)
+        axis = np.abs(normals).argmax(1)
+        assert (np.abs(normals[np.arange(axis.size), axis]) == 1.0).all() and (np.abs(normals).sum(1) == 1.0).all() and (axis < dim).all()
+        self._part, self.scale = part, s
+        self.areas = np.asarray(part.areas, np.float64) * (s.prod() / s[axis])
+        self.volumes = np.asarray(part.volumes, np.float64) * s.prod()
+        self.centres = np.asarray(part.centres, np.float64).copy()
+        self.centres[:, :dim] *= s
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__["_part"], name)
+
+
+def scaled(part, s):
+    """`part` (a SynthMesh partition: Cartesian, unit square / cube) as the same forest of a box with the edge lengths `s` (one
+    factor, or one per axis): areas[f] * prod(s) / s[axis of f], volumes * prod(s), centres * s; connectivity, normals, the 2:1
+    maps, boundary kinds, halo arrays, mesh and initial state are those of `part`. Every normal must be an exact axis normal.
+    Subgrid partitions take a single factor only (ValueError otherwise): the reference derives the area of a block's inner
+    sub-faces from its volume, so a stretched block has no defined answer."""
+    return Scaled(part, s)
+
+
 def _interior_faces(part):
     """(left, right, axis, positive, hanging) of the F interior faces"""
     F, dim = part.F, part.mesh.dim
